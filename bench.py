@@ -15,6 +15,9 @@ roofline  = the dominant kernel pair (forward negacyclic NTT = COLS phase + ROWS
 cpu_baseline = the CPU oracle (C restatement of SEAL 4.0's algorithms, 1 thread like the reference) on a bounded
             prefix of the same program, rank 0, N = 1 only.
 Launch: python bench.py [--gpus N --steps K --warmup W]   (N > 1: via torch.distributed.run, one rank per GPU).
+A plain run measures the headline only: set-up, W warm-up steps, K timed steps, the result line.  roofline, cpu_baseline, the
+decrypted-error check, config 4 and every other leg run only with --full.  --dump-outputs DIR writes the decrypted result of the
+last timed step (what getOutput() hands a caller) as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -498,6 +501,32 @@ def emit(full: dict, out=None):
     return path
 
 
+DUMP_LIMIT = 64 << 20  # bytes, all files of one --dump-outputs together
+
+
+def read_outputs(hevm, streams: int) -> list:
+    """getOutput() of every stream (decrypted, decoded: what the reference's runner hands its caller), stream 0 selected afterwards"""
+    outs = []
+    for s in range(streams):
+        hevm.select_stream(s)
+        outs.append(hevm.getOutput())
+    hevm.select_stream(0)
+    return outs
+
+
+def dump_outputs(d, outs: list):
+    """--dump-outputs: outs[s] -> d/output.npy (s = 0) and d/output_stream<s>.npy, float64"""
+    arrays = {("output" if s == 0 else f"output_stream{s}"): np.ascontiguousarray(o, dtype=np.float64) for s, o in enumerate(outs)}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit(f"[bench] --dump-outputs: {total} bytes of outputs exceed {DUMP_LIMIT}")
+    path = Path(d)
+    path.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(path / f"{name}.npy", a)
+    print(f"[bench] outputs: {', '.join(f'{n}.npy {a.shape}' for n, a in arrays.items())} in {path}", file=sys.stderr)
+
+
 def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -512,20 +541,27 @@ def build_parser():
     ap.add_argument("--layers", type=int, default=20, help="--program shaped: depth (20 = the traced op mix)")
     ap.add_argument("--streams", type=int, default=1, help="independent ciphertext streams per GPU (throughput mode; 1 = the reference's one image per run)")
     ap.add_argument("--full", action="store_true",
-                    help="also run the A/B legs that only the full record carries: the b6 / b13 lowerings, direct rotation keys, the streams table, "
-                         "real bootstrapping at N = 2^15, config 3 under grouped-digit keys, config 4's key shapes / chains / key sets, the CPU "
-                         "baseline with OpenMP and on the b13 lowering (several minutes more)")
+                    help="also run everything beyond the headline: the decrypted error vs the torch model, the roofline leg, the NTT micro leg, "
+                         "config 3, the per-op leg, the CPU baseline, config 4 in a child process, and the A/B legs that only the full record "
+                         "carries: the b6 / b13 lowerings, direct rotation keys, the streams table, real bootstrapping at N = 2^15, config 3 under "
+                         "grouped-digit keys, config 4's key shapes / chains / key sets, the CPU baseline with OpenMP and on the b13 lowering "
+                         "(several minutes more).  Without it the run measures the headline only")
     ap.add_argument("--out", default=None,
-                    help="where the FULL record goes (default gpurun_out/bench_full.json); stdout's last line is the compact line (<= 4 KB)")
+                    help="where the FULL record goes (with --full, a default side file when not given; a plain run writes one only when "
+                         "given); stdout's last line is the compact line (<= 4 KB)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed -- the decrypted result, getOutput() of every stream -- as "
+                         "DIR/output.npy (stream 0) and DIR/output_stream<s>.npy (float64).  The inputs are the same from run to run; keys and "
+                         "encryption randomness come from the OS, so two runs agree to within CKKS noise (~1e-7 rms), not bit for bit")
     ap.add_argument("--no-lowerings", action="store_true", help="--full: skip the other lowerings of the trace (config.lowerings)")
     ap.add_argument("--no-streams-leg", action="store_true", help="--full: skip the throughput table (1 / 2 / 4 / 8 / 16 streams of the headline program in one VM)")
     ap.add_argument("--config4-lazy-sums", type=int, default=0,
                     help="--program config4: VM option hyb_lazy_sum for the timed stream (0 = the library's default: every rotate instruction "
                          "rounds on its own, the reference's semantics; 1 = one division by P per sum of rotations)")
     ap.add_argument("--no-config4", dest="config4", action="store_false",
-                    help="skip BASELINE config 4's shape (ResNet-20 traced at nt = 2^16, N = 2^17, real bootstrapping; ~1 min, ~180 GB of HBM); "
-                         "it runs by default since round 3, in a child process before this one touches the GPU")
-    ap.add_argument("--config4", dest="config4", action="store_true", help="(default)")
+                    help="--full: skip BASELINE config 4's shape (ResNet-20 traced at nt = 2^16, N = 2^17, real bootstrapping; ~1 min, ~180 GB of "
+                         "HBM); with --full it runs by default, in a child process before this one touches the GPU")
+    ap.add_argument("--config4", dest="config4", action="store_true", help="(default with --full)")
     ap.set_defaults(config4=True)
     ap.add_argument("--broadcast-keys", action="store_true",
                     help="every rank generates its own key set, then rank 0's is shipped to the others (one flat RCCL broadcast per key "
@@ -678,9 +714,12 @@ def main_config4(args, grp):
     barrier_sync()
     elapsed = time.perf_counter() - t0
     stats = hevm.stats()
-    out = hevm.getOutput()[0]
+    outs = read_outputs(hevm, 1)
+    out = outs[0][0]
     elapsed, total = grp.job_totals(elapsed, float(stats["ntts"]) * args.steps)
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, outs)
         rms = float(np.sqrt(np.mean((out[:10] * 32 - fx["torch_result"]) ** 2)))
         print(json.dumps(config4_line(args, world, elapsed, total, stats["ntts"], stats["keyswitches"], key_info, t_setup, rms, len(offs), K)), flush=True)
     hevm.close()
@@ -775,9 +814,9 @@ def main():
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(spawn_ranks(args, argv))
 
-    # rank 0 of a 1-GPU run only: the other legs of the line are N = 1 figures as well
-    config4 = config4_child(args.full) if (args.config4 and args.gpus == 1 and not args.dry_run and "RANK" not in os.environ
-                                  and args.program != "config4") else None
+    # --full, rank 0 of a 1-GPU run only: the other legs of the line are N = 1 figures as well
+    config4 = config4_child(args.full) if (args.full and args.config4 and args.gpus == 1 and not args.dry_run and "RANK" not in os.environ
+                                           and args.program != "config4") else None
 
     from dacapo_amd.dist import Group
 
@@ -859,10 +898,10 @@ def main():
     barrier_sync()
     elapsed = time.perf_counter() - t0
     stats = hevm.stats()
+    outs = read_outputs(hevm, args.streams) if (args.full or args.dump_outputs) else None
     rms = None
-    if fx is not None:  # decrypted logits vs the torch model (examples/tests/ResNet.py:76-81: first 10 slots * 32)
-        hevm.select_stream(0)
-        out = hevm.getOutput()[0]
+    if args.full and fx is not None:  # decrypted logits vs the torch model (examples/tests/ResNet.py:76-81: first 10 slots * 32)
+        out = outs[0][0]
         rms = {"rms_vs_torch": float(np.sqrt(np.mean((out[:10] * 32 - fx["torch_result"]) ** 2))),
                "rms_vs_plaintext_evaluation": float(np.sqrt(np.mean((out - fx["expected"]) ** 2))),
                "reference_published_rms": 9.5e-4}
@@ -876,6 +915,32 @@ def main():
 
     ms_per_step = elapsed / args.steps * 1e3
     value = total_ntts / elapsed
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, outs)
+    line = {
+        "metric": "NTT/s (NTT-equivalents over one run() of the ResNet HEVM program, nt=2^14)",
+        "value": round(value, 1), "unit": "NTT/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "u64",
+        "data": "synthetic" if fx is None else "synthetic image; weights = the reference's resnet20.silu.model",
+        "config": {"workload": workload + ", nt=2^14 slots, N=2^15, 14 x 60-bit primes (SEAL_HEVM.cpp:39-53); one "
+                               "independent ciphertext stream per GPU",
+                   "ops": info["op_mix"], "key_switches_per_step": stats["keyswitches"], "ntt_equivalents_per_step": ntts_per_step,
+                   "streams_per_gpu": args.streams,
+                   "parallelism": f"replicas x{world} (no collective in the op path)", "keys": key_info},
+        "hevm_wall_s": round(ms_per_step / 1e3, 4),
+        "hevm_bootstrap_s_per_step": round(stats["bootstrap_s"], 4),
+        "setup_s_untimed": round(t_setup, 1),
+    }
+    if not args.full:  # the headline only: the legs below, the decrypted-error check and the CPU baseline are --full's
+        hevm.close()
+        if args.out:
+            print(f"[bench] full record: {emit(line, args.out)}", file=sys.stderr)
+        else:
+            print(json.dumps(compact_line(line)), flush=True)
+        grp.close()
+        return
+
     from dacapo_amd import progstats
 
     pst = progstats.walk(hv)
@@ -972,22 +1037,8 @@ def main():
             hv13 = gzip.open(ROOT / "tests" / "golden" / "resnet20.b13.hevm.gz").read()
         cpu = cpu_baseline_leg(cst, hv, image, hv_b13=hv13 if args.full else None, openmp=args.full)
 
-    line = {
-        "metric": "NTT/s (NTT-equivalents over one run() of the ResNet HEVM program, nt=2^14)",
-        "value": round(value, 1), "unit": "NTT/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "u64",
-        "data": "synthetic" if fx is None else "synthetic image; weights = the reference's resnet20.silu.model",
-        "config": {"workload": workload + ", nt=2^14 slots, N=2^15, 14 x 60-bit primes (SEAL_HEVM.cpp:39-53); one "
-                               "independent ciphertext stream per GPU",
-                   "ops": info["op_mix"], "key_switches_per_step": stats["keyswitches"], "ntt_equivalents_per_step": ntts_per_step,
-                   "streams_per_gpu": args.streams,
-                   "lowerings": lowerings,
-                   "with_direct_rotation_keys": direct,
-                   "parallelism": f"replicas x{world} (no collective in the op path)", "keys": key_info},
-        "hevm_wall_s": round(ms_per_step / 1e3, 4),
-        "hevm_bootstrap_s_per_step": round(stats["bootstrap_s"], 4),
-        "setup_s_untimed": round(t_setup, 1),
+    line["config"].update(lowerings=lowerings, with_direct_rotation_keys=direct)
+    line.update({
         "decrypted_error": rms,
         "roofline": roof,
         # the fed regime: S images per run() in one VM (what config 5 multiplies by the GPUs); null with --no-streams-leg / --streams > 1
@@ -1000,7 +1051,7 @@ def main():
         # --no-config4, --gpus > 1 or an external launcher
         "config4_resnet20_nt65536_N131072": config4,
         "cpu_baseline": cpu,
-    }
+    })
     line["ks_traffic"] = ks_traffic
     if cpu:
         line["speedup_vs_cpu_port"] = round(value / cpu["value"], 1)

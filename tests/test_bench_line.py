@@ -8,6 +8,7 @@ import sys
 from contextlib import redirect_stdout
 from pathlib import Path
 
+import numpy as np
 import pytest
 
 ROOT = Path(__file__).resolve().parent.parent
@@ -93,3 +94,26 @@ def test_a_line_without_optional_legs_is_still_valid():
     line = bench.compact_line(full)
     assert "cpu_baseline" not in line and "config4" not in line and line["roofline"]["frac"]
     json.loads(json.dumps(line))
+
+
+def test_plain_run_options():
+    """a plain run is the headline alone: every other leg waits for --full; --dump-outputs is off unless given"""
+    a = bench.build_parser().parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    b = bench.build_parser().parse_args(["--full", "--dump-outputs", "d"])
+    assert b.full is True and b.dump_outputs == "d"
+
+
+def test_dump_outputs_writes_float64_arrays_per_stream(tmp_path):
+    rng = np.random.default_rng(0)
+    outs = [rng.standard_normal((1, 64)), rng.standard_normal((1, 64)).astype(np.float32)]
+    with redirect_stdout(io.StringIO()) as buf:
+        bench.dump_outputs(tmp_path / "o", outs)
+    assert buf.getvalue() == "", "stdout's last line stays the result line"
+    assert sorted(p.name for p in (tmp_path / "o").iterdir()) == ["output.npy", "output_stream1.npy"]
+    for name, want in (("output", outs[0]), ("output_stream1", outs[1])):
+        got = np.load(tmp_path / "o" / f"{name}.npy")
+        assert got.dtype == np.float64 and got.shape == want.shape and (got == want).all()
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(tmp_path / "big", [np.zeros(bench.DUMP_LIMIT // 8 + 1)])
+    assert not (tmp_path / "big").exists()

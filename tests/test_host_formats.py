@@ -200,35 +200,56 @@ def _ref_wire():
     return p if p.exists() else None
 
 
-def test_wire_format_against_the_reference_header(tmp_path):
-    """oracle/_ref/hevm_wire_ref is built from the reference's own include/hecate/Support/HEVMHeader.h (the one source of
-    its HEVM path that compiles here) and reads a .hevm file in the order SEAL_HEVM::loadHEVM does (SEAL_HEVM.cpp:202-234).
-    What it sees must be what our assembler wrote and what our reader returns -- for hand-assembled programs and for the
-    traced fixtures."""
-    import gzip
-    import json
-    import subprocess
-    from pathlib import Path
+# what oracle/_ref/hevm_wire_ref printed for _wire_images() (tools/fixtures/record_wire_ref.py): the reference reader's view of the same bytes,
+# for a checkout built where the reference is not readable
+WIRE_REF = ROOT / "tests" / "golden" / "hevm_wire_ref.json"
 
-    import pytest
+
+def _wire_images():
+    """name -> .hevm bytes: the traced fixtures and two hand-assembled programs"""
+    import gzip
 
     from dacapo_amd import hevm_asm as ha
 
-    exe = _ref_wire()
-    if exe is None:
-        pytest.skip("oracle/_ref/hevm_wire_ref not built (needs /root/reference at build time)")
-    layout = json.loads(subprocess.check_output([str(exe)]))
-    assert (layout["sizeof_HEVMHeader"], layout["sizeof_ConfigBody"], layout["sizeof_HEVMOperation"]) == (24, 40, 8)
-    assert layout["default_magic"] == ha.MAGIC and layout["offsetof_arg_length"] == 8 and layout["offsetof_init_level"] == 32
-    golden = Path(__file__).resolve().parent / "golden"
+    golden = ROOT / "tests" / "golden"
     images = {p.name: gzip.open(p).read() for p in sorted(golden.glob("*.hevm.gz")) + sorted((golden / "suite").glob("*.hevm.gz"))}
     rng = np.random.default_rng(3)
     images["sobel"] = ha.sobel_filter(rng.uniform(0, 1, 4096), slots=4096, init_level=6).assemble()[1]
     images["linreg"] = ha.linear_regression(rng.uniform(-1, 1, 4096), rng.uniform(-1, 1, 4096), slots=4096, init_level=12).assemble()[1]
+    return images
+
+
+def test_wire_format_against_the_reference_header(tmp_path):
+    """oracle/_ref/hevm_wire_ref is built from the reference's own include/hecate/Support/HEVMHeader.h (the one source of
+    its HEVM path that compiles here) and reads a .hevm file in the order SEAL_HEVM::loadHEVM does (SEAL_HEVM.cpp:202-234).
+    What it sees must be what our assembler wrote and what our reader returns -- for hand-assembled programs and for the
+    traced fixtures.  Where the binary is not built, its recorded output (tests/golden/hevm_wire_ref.json, keyed by the
+    sha256 of the bytes it read) stands in for it; where it is, live and recorded output must agree."""
+    import hashlib
+    import json
+    import subprocess
+
+    from dacapo_amd import hevm_asm as ha
+
+    exe = _ref_wire()
+    recorded = json.loads(WIRE_REF.read_text())
+    layout = json.loads(subprocess.check_output([str(exe)])) if exe else recorded["layout"]
+    assert layout == recorded["layout"]
+    assert (layout["sizeof_HEVMHeader"], layout["sizeof_ConfigBody"], layout["sizeof_HEVMOperation"]) == (24, 40, 8)
+    assert layout["default_magic"] == ha.MAGIC and layout["offsetof_arg_length"] == 8 and layout["offsetof_init_level"] == 32
+    images = _wire_images()
     assert len(images) >= 9
     for name, raw in images.items():
-        (tmp_path / "p.hevm").write_bytes(raw)
-        ref = json.loads(subprocess.check_output([str(exe), str(tmp_path / "p.hevm")]))
+        rec = recorded["images"].get(name)
+        if exe:
+            (tmp_path / "p.hevm").write_bytes(raw)
+            ref = json.loads(subprocess.check_output([str(exe), str(tmp_path / "p.hevm")]))
+            if rec is not None and rec["sha256"] == hashlib.sha256(raw).hexdigest():
+                assert ref == rec["reader"], name
+        else:
+            assert rec is not None, f"{name}: no recorded reader output (tools/fixtures/record_wire_ref.py)"
+            assert rec["sha256"] == hashlib.sha256(raw).hexdigest(), f"{name}: bytes differ from the recorded ones (tools/fixtures/record_wire_ref.py)"
+            ref = rec["reader"]
         ours = ha.unpack_hevm(raw)
         assert ref["complete"] and ref["at_end"], name  # the reference reader consumes the file exactly
         assert ref["magic_number"] == ha.MAGIC and ref["hevm_header_size"] == 24

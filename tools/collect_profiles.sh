@@ -12,7 +12,7 @@ cd /tmp && export TMPDIR=/tmp
 kt() { ls $1/*/*kernel_trace.csv | head -1; }
 cc() { ls $1/*/*counter_collection.csv | head -1; }
 # A. kernel trace + stats of the bench command
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -- python3 $ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-lowerings --no-config4 > $OUT/bench_under_profiler.json 2> $OUT/kt.err
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -- python3 $ROOT/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-lowerings --no-streams-leg --no-config4 > $OUT/bench_under_profiler.json 2> $OUT/kt.err
 cp $(ls $OUT/kt/*/*kernel_stats.csv | head -1) $OUT/${R}_kernel_stats.csv
 cd $ROOT
 python tools/summarize/summarize_trace.py $(kt $OUT/kt) > $OUT/${R}_by_kernel_and_grid.txt
