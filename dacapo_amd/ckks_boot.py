@@ -3,7 +3,10 @@
 decrypt / re-encrypt stand-in, SEAL_HEVM.cpp:324-334).  HEaaN is closed, so this is the published algorithm (Cheon-Han-Kim-Kim-Song
 2018; Chen-Chillotti-Song 2019 / Han-Ki 2020 for the factored linear transforms and the double-angle sine), restated for SEAL's
 conventions -- slot k = evaluation at zeta^(3^k), 60-bit primes, hybrid key switching -- and lowered onto the opcodes this runtime
-already executes, plus four extension opcodes (hevm_asm.OP_ENCODE_COMPLEX / OP_CONJ / OP_MODRAISE / OP_SETSCALE):
+already executes, plus four extension opcodes (hevm_asm.OP_ENCODE_COMPLEX / OP_CONJ / OP_MODRAISE / OP_SETSCALE) and, with sse=True, a fifth
+(OP_KEYSWITCH, sparse-secret encapsulation: Bossuat-Troncoso-Pastoriza-Hubaux 2022):
+
+    [KEYSWITCH 0  the 1-prime ciphertext is switched from the main secret s to an ephemeral sparse secret s' (a key modulo q0 P only)]
 
     ModRaise      a ciphertext at 1 prime is read as one at L primes: it now decrypts to  t = p + q0 I,  |I| <~ sqrt(h)   (h = secret weight)
     CoeffToSlot   two ciphertexts whose SLOTS hold the coefficients t_j / q0 (bit-reversed order): u = A0^H z, u' = A0^H conj(D) z,
@@ -15,6 +18,9 @@ already executes, plus four extension opcodes (hevm_asm.OP_ENCODE_COMPLEX / OP_C
                   angles  c <- 2 c^2 - 1.  Every additive term carries an exactly tracked scale (constants are encoded with the
                   compensating factor), so the 2^-35 drift of each rescale (q = 2^60 - delta) never appears as an error.
     SlotToCoeff   z' = A0 y_lo + D A0 y_hi: the same factors in the other order, on the bit-reversed inputs EvalMod left.
+
+With sse=True the main secret may be dense (SEAL's uniform ternary) or of moderate weight: only ModRaise runs under s', so I stays as narrow as
+s' makes it, and `KEYSWITCH 1` right after ModRaise brings the raised ciphertext back to s for the rest.
 
 Levels: 3 + 1 (CoeffToSlot) + 5 + r (EvalMod) + 3 (SlotToCoeff): `boot_levels`.  `simulate` interprets a program (all opcodes, the four extensions
 included) on cleartext slot vectors with the exact scale semantics of the VM -- the reference semantics of the extension opcodes and
@@ -28,8 +34,8 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import hevm_asm as ha
-from .hevm_asm import (OP_ADDCC, OP_ADDCP, OP_BOOTSTRAP, OP_CONJ, OP_ENCODE, OP_ENCODE_COMPLEX, OP_MODRAISE, OP_MODSWITCH, OP_MULCC, OP_MULCP,
-                       OP_NEGATE, OP_RESCALE, OP_ROTATE, OP_SETSCALE)
+from .hevm_asm import (OP_ADDCC, OP_ADDCP, OP_BOOTSTRAP, OP_CONJ, OP_ENCODE, OP_ENCODE_COMPLEX, OP_KEYSWITCH, OP_MODRAISE, OP_MODSWITCH,
+                       OP_MULCC, OP_MULCP, OP_NEGATE, OP_RESCALE, OP_ROTATE, OP_SETSCALE)
 
 
 # ---- parameters ---------------------------------------------------------------------------------------------------------------
@@ -183,8 +189,10 @@ class BootstrapEmitter:
     """Emits the bootstrap of one ciphertext into `b`.  Plaintext registers of the matrices are shared by all bootstraps of a program."""
 
     def __init__(self, b: ha.Builder, logN: int, num_primes: int, target_level: int, r: int = 5, taylor_terms: int = 16, k_range: float = 16.0,
-                 msg_bits: int = 0, diag_bits: int | None = None, out_bits: int = 40, groups: int = 3, cts_bits: int = 60, ks: int = 1, primes=None):
-        """primes: the VM's chain when it is not CoeffModulus::Create(N, {60 x num_primes}) -- round 4: any chain of 45..60-bit primes, in
+                 msg_bits: int = 0, diag_bits: int | None = None, out_bits: int = 40, groups: int = 3, cts_bits: int = 60, ks: int = 1, primes=None,
+                 sse: bool = False):
+        """sse: sparse-secret encapsulation -- ModRaise is wrapped in KEYSWITCH 0 / KEYSWITCH 1 (the VM needs option boot_secret_hw).
+        primes: the VM's chain when it is not CoeffModulus::Create(N, {60 x num_primes}) -- round 4: any chain of 45..60-bit primes, in
         particular a HEaaN-style mixed one (mixed_prime_chain).  Every scale below is tracked with the exact primes; the handful of places
         that used to say "60" now read the width of the prime they mean (self.qb)."""
         self.b, self.logN, self.N, self.n = b, logN, 1 << logN, 1 << (logN - 1)
@@ -192,7 +200,7 @@ class BootstrapEmitter:
         assert len(self.primes) == num_primes
         self.top = num_primes - ks  # ks special primes at the end of the chain (1 in SEAL's scheme; more with grouped-digit key switching)
         diag_bits = (self.qb(self.top) - 5) if diag_bits is None else diag_bits  # matrix / coefficient plaintexts: 55 bits next to 60-bit primes
-        self.target, self.r, self.terms, self.k_range = target_level, r, taylor_terms, k_range
+        self.target, self.r, self.terms, self.k_range, self.sse = target_level, r, taylor_terms, k_range, sse
         self.msg_bits, self.diag_bits, self.out_bits, self.groups, self.cts_bits = msg_bits, diag_bits, out_bits, groups, cts_bits
         assert taylor_terms in (8, 16), "the polynomial in theta^2 is evaluated as a complete binary tree"
         # round 3: one more level than round 2 -- CoeffToSlot now ends with two rescales (see `bootstrap`)
@@ -386,7 +394,11 @@ class BootstrapEmitter:
             reg = b._encode(0xFFFF, 1, up)
             ct = self._op(OP_MULCP, ct, 1, ct.s * 2.0**up, reg)
         delta = ct.s                                             # p = delta * mu ; after ModRaise t = p + q0 I
+        if self.sse:                                             # s -> s': I is as wide as the ephemeral secret makes it
+            ct = self._op(OP_KEYSWITCH, ct, 1, ct.s, 0)
         ct = self._op(OP_MODRAISE, ct, self.top, 1.0, self.top)  # from here s is relative to z = slots(t)
+        if self.sse:                                             # s' -> s at the top level: the rest runs under the main secret
+            ct = self._op(OP_KEYSWITCH, ct, self.top, ct.s, 1)
         # Noise budget (round 3; measured with the CPU oracle, tools/experiments/boot_precision.py).  What a bootstrap must preserve is
         # eps_j = p_j / q0 ~ 2^-(10 + msg_bits) / sqrt(N) per coefficient next to I_j ~ 2, so three absolute error sources that a
         # ciphertext at scale 2^40 would never notice decide the result: (a) key-switch noise of the baby-step rotations (~2^17 per slot
@@ -498,11 +510,15 @@ def _quantise(raw, logN: int):
 
 
 # ---- cleartext interpreter with the VM's scale semantics -------------------------------------------------------------------------
-def simulate(hevm: bytes, cst: bytes, inputs, logN: int, primes, secret_weight: int = 64, seed: int = 1, return_trace=False):
+def simulate(hevm: bytes, cst: bytes, inputs, logN: int, primes, secret_weight: int = 64, seed: int = 1, return_trace=False,
+             boot_secret_weight: int = 32):
     """Runs a program on slot vectors: every register holds raw = slots(polynomial) (complex, length N/2) and the VM's scale label.
-    ModRaise adds q0 * I for a random I distributed like <c1, s> / q0 for a ternary secret of the given weight; everything else is
-    noise-free CKKS.  Returns the decoded results (raw / label)."""
+    ModRaise adds q0 * I for a random I distributed like <c1, s> / q0 for a ternary secret of the given weight -- boot_secret_weight, the
+    ephemeral secret's, when the program uses sparse-secret encapsulation (opcode 20, the identity here) -- and secret_weight otherwise;
+    everything else is noise-free CKKS.  Returns the decoded results (raw / label)."""
     h = ha.unpack_hevm(hevm)
+    if (h["ops"][:, 0] == OP_KEYSWITCH).any():
+        secret_weight = boot_secret_weight
     consts = ha.unpack_cst(cst)
     n = 1 << (logN - 1)
     rng = np.random.default_rng(seed)
@@ -525,7 +541,7 @@ def simulate(hevm: bytes, cst: bytes, inputs, logN: int, primes, secret_weight: 
             c = v[:half] + 1j * v[half:]
             plain[dst] = [_quantise(c[idx % half] * s, logN), s]
             continue
-        if opc > OP_SETSCALE or opc == 5:
+        if opc > OP_KEYSWITCH or opc == 5:
             continue
         raw, s, l = reg[lhs]
         if opc == OP_ROTATE:
@@ -558,6 +574,7 @@ def simulate(hevm: bytes, cst: bytes, inputs, logN: int, primes, secret_weight: 
             raw, l = raw + embed(I * float(primes[0]), logN), rhs
         elif opc == OP_SETSCALE:
             s = float(consts[rhs][0])
+        # OP_KEYSWITCH: the same message under another secret -- the identity on slot vectors
         reg[dst] = [raw, s, l]
         if return_trace:
             trace.append((opc, dst, l, s))
@@ -566,14 +583,14 @@ def simulate(hevm: bytes, cst: bytes, inputs, logN: int, primes, secret_weight: 
 
 
 # ---- a bootstrap on its own (tools/legs/boot_demo.py, bench.py, tests) ------------------------------------------------------------------
-def single_bootstrap_program(logN: int, target: int = 3, r: int = 5, msg_bits: int = 0, ks: int = 1, primes=None):
+def single_bootstrap_program(logN: int, target: int = 3, r: int = 5, msg_bits: int = 0, ks: int = 1, primes=None, sse: bool = False):
     """(num_primes, cst, hevm, rotation offsets, emitter) of the program `one ciphertext at 1 prime, scale 2^40 -> bootstrap -> output`;
     ks = number of special primes of the chain (the VM must be created with ks_special = ks); primes: the VM's chain when it is not the
     all-60-bit one (target + boot_levels(r) + ks of them)"""
     K = target + boot_levels(r) + ks
     b = ha.Builder(slots=1 << (logN - 1), init_level=1, shadow=False)
     x = b.input(None, level=1, scale_bits=40)
-    em = BootstrapEmitter(b, logN, K, target, r=r, msg_bits=msg_bits, ks=ks, primes=primes)
+    em = BootstrapEmitter(b, logN, K, target, r=r, msg_bits=msg_bits, ks=ks, primes=primes, sse=sse)
     y, _ = em.bootstrap(x, 2.0**40)
     b.output(y)
     cst, hv, _ = b.assemble()
@@ -586,18 +603,20 @@ def rotation_offsets(hevm: bytes):
 
 
 # ---- compiled programs: opcode 10 -> real bootstrapping ------------------------------------------------------------------------------
-def lower_bootstraps(hevm: bytes, cst: bytes, logN: int, num_primes: int, msg_bits: int = 4, r: int = 5, ks: int = 1, primes=None):
+def lower_bootstraps(hevm: bytes, cst: bytes, logN: int, num_primes: int, msg_bits: int = 4, r: int = 5, ks: int = 1, primes=None,
+                     sse: bool = False):
     """Rewrites a program (e.g. one emitted by the reference's compiler) so that every opcode 10 -- `bootstrap`, a decrypt / re-encrypt
     stand-in in the SEAL runtime (SEAL_HEVM.cpp:324-334), the real thing in the HEaaN runtime (HEAAN_HEVM.cpp:386-399) -- becomes the
     real bootstrapping sequence of this module.  Everything else is re-emitted unchanged (same instructions, same constants, registers
     re-allocated).  All opcode 10 of the program must restore the same number of primes t, and the chain must hold num_primes =
-    t + boot_levels(r) + ks primes (ks special ones).  Returns (hevm', cst')."""
+    t + boot_levels(r) + ks primes (ks special ones).  sse: every bootstrap's ModRaise runs under the ephemeral sparse secret (opcode 20
+    around it; the VM needs option boot_secret_hw).  Returns (hevm', cst')."""
     h = ha.unpack_hevm(hevm)
     consts = ha.unpack_cst(cst)
     slots = 1 << (logN - 1)
     qbits = [int(q).bit_length() for q in primes] if primes is not None else [60] * num_primes
     b = ha.Builder(slots=slots, init_level=int(h["init_level"]), shadow=False,
-                   real_boot=dict(num_primes=num_primes, msg_bits=msg_bits, r=r, ks=ks, primes=primes))
+                   real_boot=dict(num_primes=num_primes, msg_bits=msg_bits, r=r, ks=ks, primes=primes, sse=sse))
     b.constants = [np.asarray(c, dtype=np.float64) for c in consts]
     b._const_index = {c.tobytes(): i for i, c in enumerate(b.constants)}
     cur = {}
@@ -611,7 +630,7 @@ def lower_bootstraps(hevm: bytes, cst: bytes, logN: int, num_primes: int, msg_bi
             b.ops.append(ha._Op(opc, reg, lhs, rhs, False, False))
             plain_of[dst], plain_bits[dst] = reg, rhs & 0x3FF
             continue
-        if opc > OP_SETSCALE or opc == 5 or (10 < opc < OP_CONJ):
+        if opc > OP_KEYSWITCH or opc == 5 or (10 < opc < OP_CONJ):
             continue
         x = cur[lhs]
         lvl, bits = x.level, x.scale_bits

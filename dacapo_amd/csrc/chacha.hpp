@@ -37,6 +37,7 @@ enum RngDomain : uint32_t {
     RNG_ENC_U = 6,     // Encryptor: ternary u
     RNG_ENC_E0 = 7,    // Encryptor: errors
     RNG_ENC_E1 = 8,
+    RNG_ESK = 9,       // ephemeral sparse secret of sparse-secret encapsulation (option boot_secret_hw)
     RNG_TEST = 15,
 };
 

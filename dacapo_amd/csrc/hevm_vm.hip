@@ -469,6 +469,7 @@ void HEVM::init_context(int logN, int K, const u64 *primes, int dir_ksp, int dir
     max_batch = std::max(1, (int)option(OPT_MAX_BATCH));
     chain_fusion = option(OPT_CHAIN_FUSION) != 0;
     secret_weight = (int)option(OPT_SECRET_HW);
+    boot_secret_weight = (int)option(OPT_BOOT_SECRET_HW);
     rot_compose = option(OPT_ROT_COMPOSE) != 0;
     online_encode = option(OPT_ONLINE_ENCODE) != 0 && use_plan && !host_encoder;
     lanes.resize(1);
@@ -482,9 +483,11 @@ void HEVM::init_context(int logN, int K, const u64 *primes, int dir_ksp, int dir
 }
 
 // KeyGenerator::generate_one_kswitch_key for every digit: key[j] = (-(a_j s + e_j) + [limb j](P mod q_j) s', a_j)
-void HEVM::gen_kswitch_key(u64 *key, const u64 *new_key, u64 key_id)
+void HEVM::gen_kswitch_key(u64 *key, const u64 *new_key, u64 key_id) { gen_kswitch_key_in(*ctx, key, keys.sk, new_key, key_id); }
+
+// ... in context `c` (the VM's own, or the boot context of sparse-secret encapsulation) under the secret key_sk ([c.K][N], NTT form)
+void HEVM::gen_kswitch_key_in(Context &c, u64 *key, const u64 *key_sk, const u64 *new_key, u64 key_id)
 {
-    Context &c = *ctx;
     const size_t N = c.N;
     const int K = c.K;
     const dim3 gu((unsigned)(N / (kRngCoefs * kVmThreads)), (unsigned)K), gs((unsigned)(N / (kRngCoefs * kVmThreads))),
@@ -497,8 +500,85 @@ void HEVM::gen_kswitch_key(u64 *key, const u64 *new_key, u64 key_id)
         DC_LAUNCH(sample_small_kernel, gs, dim3(kVmThreads), 0, S(), c0, N, K, 1, rng.secret, object, (u32)RNG_KSK_E, c.d_mods);
         launch_ntt(c, false, c0, (long)N, K, nullptr, 0, 0, S());
         const int lo = c.hybrid() ? j * c.alpha : j, hi = c.hybrid() ? std::min(lo + c.alpha, L) : j + 1;
-        DC_LAUNCH(ezs_final_kernel, g2, dim3(kVmThreads), 0, S(), c0, c1, keys.sk, new_key, lo, hi, c.d_pmod, N, c.d_mods);
+        DC_LAUNCH(ezs_final_kernel, g2, dim3(kVmThreads), 0, S(), c0, c1, key_sk, new_key, lo, hi, c.d_pmod, N, c.d_mods);
     }
+}
+
+// Sparse ternary secret with exactly `weight` non-zero coefficients, [K][N] in coefficient form.  Positions and signs from the secret
+// ChaCha20 key in domain `domain` (RNG_SK: the main secret of option secret_hw; RNG_ESK: the ephemeral one of option boot_secret_hw), drawn
+// on the host.
+void HEVM::fill_sparse_secret(u64 *dst, int weight, u32 domain)
+{
+    const Context &c = *ctx;
+    const size_t N = c.N;
+    const int K = c.K;
+    if (weight < 1 || (size_t)weight > N / 2) {
+        fprintf(stderr, "[dacapo_amd] a sparse secret of weight %d is not sparse for N = %zu\n", weight, N);
+        abort();
+    }
+    std::vector<int8_t> coef(N, 0);
+    u64 w[8];
+    int placed = 0;
+    for (u64 blk = 0; placed < weight; blk++) {
+        rng_words8(rng.secret, 0, blk, 0, 1, domain, w);
+        for (int e = 0; e < 8 && placed < weight; e++) {
+            const size_t idx = (size_t)((w[e] >> 8) % N); // N is a power of two: unbiased
+            if (coef[idx]) continue;
+            coef[idx] = (w[e] & 1) ? 1 : -1;
+            placed++;
+        }
+    }
+    std::vector<u64> h((size_t)K * N);
+    for (int i = 0; i < K; i++)
+        for (size_t k = 0; k < N; k++) h[(size_t)i * N + k] = coef[k] == 0 ? 0 : coef[k] > 0 ? 1 : c.primes[(size_t)i] - 1;
+    DC_HIP_CHECK(hipMemcpyAsync(dst, h.data(), h.size() * 8, hipMemcpyHostToDevice, S()));
+    DC_HIP_CHECK(hipStreamSynchronize(S()));
+    // the host copies of the secret are wiped before they are released (explicit_bzero: stores the optimiser may not drop as dead)
+    explicit_bzero(h.data(), h.size() * sizeof(u64));
+    explicit_bzero(coef.data(), coef.size());
+    explicit_bzero(w, sizeof(w));
+}
+
+void HEVM::ensure_boot_context()
+{
+    if (bctx) return;
+    const Context &c = *ctx;
+    std::vector<u64> p(1, c.primes[0]);
+    for (int i = c.K - c.ksp; i < c.K; i++) p.push_back(c.primes[(size_t)i]);
+    bctx.reset(new Context(c.logN, 1 + c.ksp, (int)option(OPT_PRIME_BITS), p.data(), c.ksp, c.alpha));
+    bctx->ensure_scratch();
+}
+
+// Sparse-secret encapsulation (Bossuat, Troncoso-Pastoriza, Hubaux, ACNS 2022): an ephemeral secret s' of weight boot_secret_weight, and
+//   swk_down  s -> s'  modulo q0 and the special primes only (the boot context): s' never appears in an RLWE sample of the full modulus
+//   swk_up    s' -> s  over the whole chain (s' encrypted under s)
+// s' is erased and freed before this returns.
+void HEVM::generate_boot_switch_keys()
+{
+    Context &c = *ctx;
+    ensure_boot_context();
+    Context &b = *bctx;
+    const size_t N = c.N;
+    const int K = c.K, ksp = c.ksp;
+    u64 *esk = dalloc((size_t)K * N);
+    fill_sparse_secret(esk, boot_secret_weight, RNG_ESK);
+    launch_ntt(c, false, esk, (long)N, K, nullptr, 0, 0, S());
+    keys.swk_up = dalloc(key_elems());
+    gen_kswitch_key_in(c, keys.swk_up, keys.sk, esk, 10);
+    // both secrets restricted to {q0, special primes}: limb 0 and the last ksp limbs of the NTT form (the transform is per prime)
+    const size_t bl = (size_t)b.K * N;
+    u64 *bsec = dalloc(2 * bl), *bnew = bsec + bl;
+    DC_HIP_CHECK(hipMemcpyAsync(bsec, esk, N * 8, hipMemcpyDeviceToDevice, S()));
+    DC_HIP_CHECK(hipMemcpyAsync(bsec + N, esk + (size_t)(K - ksp) * N, (size_t)ksp * N * 8, hipMemcpyDeviceToDevice, S()));
+    DC_HIP_CHECK(hipMemcpyAsync(bnew, keys.sk, N * 8, hipMemcpyDeviceToDevice, S()));
+    DC_HIP_CHECK(hipMemcpyAsync(bnew + N, keys.sk + (size_t)(K - ksp) * N, (size_t)ksp * N * 8, hipMemcpyDeviceToDevice, S()));
+    keys.swk_down = dalloc((size_t)b.key_digits() * 2 * bl);
+    gen_kswitch_key_in(b, keys.swk_down, bsec, bnew, 9);
+    DC_HIP_CHECK(hipMemsetAsync(esk, 0, (size_t)K * N * 8, S()));
+    DC_HIP_CHECK(hipMemsetAsync(bsec, 0, 2 * bl * 8, S()));
+    DC_HIP_CHECK(hipStreamSynchronize(S()));
+    (void)vm_free(esk);
+    (void)vm_free(bsec);
 }
 
 void HEVM::add_galois_key(u32 elt)
@@ -523,31 +603,9 @@ void HEVM::generate_keys(const RngKeys &rng_, bool secret, bool pub, bool eval)
     const dim3 gu((unsigned)(N / (kRngCoefs * kVmThreads)), (unsigned)K), gs((unsigned)(N / (kRngCoefs * kVmThreads))),
         g2((unsigned)(N / (2 * kVmThreads)), (unsigned)K);
     keys.sk = dalloc((size_t)K * N);
-    if (secret_weight > 0) {
-        // Sparse ternary secret with exactly `secret_weight` non-zero coefficients (what bootstrappable parameter sets use: the ModRaise
-        // overflow I of ckks_boot.py is ~ sqrt(h / 12) wide).  Positions and signs from the secret ChaCha20 key, drawn on the host.
-        if ((size_t)secret_weight > N / 2) {
-            fprintf(stderr, "[dacapo_amd] option secret_hw=%d is not sparse for N = %zu\n", secret_weight, N);
-            abort();
-        }
-        std::vector<int8_t> coef(N, 0);
-        u64 w[8];
-        int placed = 0;
-        for (u64 blk = 0; placed < secret_weight; blk++) {
-            rng_words8(rng.secret, 0, blk, 0, 1, RNG_SK, w);
-            for (int e = 0; e < 8 && placed < secret_weight; e++) {
-                const size_t idx = (size_t)((w[e] >> 8) % N); // N is a power of two: unbiased
-                if (coef[idx]) continue;
-                coef[idx] = (w[e] & 1) ? 1 : -1;
-                placed++;
-            }
-        }
-        std::vector<u64> h((size_t)K * N);
-        for (int i = 0; i < K; i++)
-            for (size_t k = 0; k < N; k++) h[(size_t)i * N + k] = coef[k] == 0 ? 0 : coef[k] > 0 ? 1 : c.primes[(size_t)i] - 1;
-        DC_HIP_CHECK(hipMemcpyAsync(keys.sk, h.data(), h.size() * 8, hipMemcpyHostToDevice, S()));
-        DC_HIP_CHECK(hipStreamSynchronize(S()));
-    } else
+    if (secret_weight > 0) // (what bootstrappable parameter sets use: the ModRaise overflow I of ckks_boot.py is ~ sqrt(h / 12) wide)
+        fill_sparse_secret(keys.sk, secret_weight, RNG_SK);
+    else
         DC_LAUNCH(sample_small_kernel, gs, dim3(kVmThreads), 0, S(), keys.sk, N, K, 0, rng.secret, (u64)0, (u32)RNG_SK, c.d_mods);
     launch_ntt(c, false, keys.sk, (long)N, K, nullptr, 0, 0, S());
     if (pub) {
@@ -579,6 +637,7 @@ void HEVM::generate_keys(const RngKeys &rng_, bool secret, bool pub, bool eval)
             pos = (pos * pos) & (m - 1);
             neg = (neg * neg) & (m - 1);
         }
+        if (boot_secret_weight > 0) generate_boot_switch_keys();
     }
     DC_HIP_CHECK(hipStreamSynchronize(S()));
 }
@@ -604,6 +663,23 @@ static u64 *to_dev(const u64 *h, size_t elems)
 
 sealio::ParmsId HEVM::parms_id_at(int limbs) const { return sealio::parms_id(ctx->N, ctx->primes.data(), (size_t)limbs); }
 
+// one KSwitchKeys entry: its digit count, then every digit as a PublicKey ([2][c.K][N] under parms_id `id`)
+static void put_key_entry(sealio::Writer &w, const Context &c, const sealio::ParmsId &id, const u64 *dkey)
+{
+    const size_t per_digit = (size_t)2 * c.K * c.N;
+    sealio::CtHeader h;
+    h.id = id, h.is_ntt = true, h.size = 2, h.N = c.N, h.limbs = (uint64_t)c.K, h.correction_factor = 1, h.scale = 1.0;
+    w.put<uint64_t>((uint64_t)c.key_digits());
+    const std::vector<u64> key = from_dev(dkey, (size_t)c.key_digits() * per_digit);
+    for (int j = 0; j < c.key_digits(); j++) { // PublicKey::save = Ciphertext::save (own header, compr none)
+        sealio::Writer one;
+        one.buf.reserve(per_digit * 8 + 128);
+        put_ciphertext(one, h, key.data() + (size_t)j * per_digit);
+        w.put_header(one.buf.size());
+        w.put_bytes(one.buf.data(), one.buf.size());
+    }
+}
+
 // KSwitchKeys::save_members: keys_[index][digit] = PublicKey; present[index] = device key [K-1][2][K][N] or absent
 static void put_kswitch_keys(sealio::Writer &w, const Context &c, const sealio::ParmsId &key_id, size_t dim1,
                              const std::map<size_t, const u64 *> &present)
@@ -612,23 +688,13 @@ static void put_kswitch_keys(sealio::Writer &w, const Context &c, const sealio::
     w.buf.reserve(w.buf.size() + 64 + dim1 * 8 + present.size() * (size_t)c.key_digits() * (per_digit * 8 + 128));
     w.put(key_id);
     w.put<uint64_t>(dim1);
-    sealio::CtHeader h;
-    h.id = key_id, h.is_ntt = true, h.size = 2, h.N = c.N, h.limbs = (uint64_t)c.K, h.correction_factor = 1, h.scale = 1.0;
     for (size_t index = 0; index < dim1; index++) {
         auto it = present.find(index);
         if (it == present.end()) {
             w.put<uint64_t>(0);
             continue;
         }
-        w.put<uint64_t>((uint64_t)c.key_digits());
-        const std::vector<u64> key = from_dev(it->second, (size_t)c.key_digits() * per_digit);
-        for (int j = 0; j < c.key_digits(); j++) { // PublicKey::save = Ciphertext::save (own header, compr none)
-            sealio::Writer one;
-            one.buf.reserve(per_digit * 8 + 128);
-            put_ciphertext(one, h, key.data() + (size_t)j * per_digit);
-            w.put_header(one.buf.size());
-            w.put_bytes(one.buf.data(), one.buf.size());
-        }
+        put_key_entry(w, c, key_id, it->second);
     }
 }
 
@@ -683,6 +749,27 @@ void HEVM::save_keys(const std::string &dir)
         fclose(f);
     } else
         remove(side.c_str()); // (a directory rewritten in SEAL mode must not keep an older sidecar)
+    // Sparse-secret encapsulation (extension): the two PUBLIC switching keys in SEAL's KSwitchKeys container under the key-level parms_id,
+    // entry 0 = s -> s' over {q0, special primes} (its digits carry that chain's parms_id and 1 + ks_special limbs), entry 1 = s' -> s over
+    // the whole chain; the ephemeral secret itself is never written.  boot.txt records its weight, as hybrid.txt records the key mode.
+    const std::string bside = join(dir, "boot.txt"), bfile = join(dir, "boot_swk.seal");
+    if (keys.swk_down && keys.swk_up) {
+        sealio::Writer w;
+        w.put(key_id);
+        w.put<uint64_t>(2);
+        put_key_entry(w, *bctx, boot_parms_id(), keys.swk_down);
+        put_key_entry(w, c, key_id, keys.swk_up);
+        write_object_file(bfile, w.buf, mode);
+        FILE *f = fopen(bside.c_str(), "w");
+        if (!f || fprintf(f, "boot_secret_hw=%d\n# sparse-secret encapsulation keys in boot_swk.seal (dacapo_amd extension, opcode 20)\n", boot_secret_weight) < 0) {
+            fprintf(stderr, "[dacapo_amd] cannot write %s\n", bside.c_str());
+            abort();
+        }
+        fclose(f);
+    } else {
+        remove(bside.c_str());
+        remove(bfile.c_str());
+    }
 }
 
 // one PublicKey of a key-switch key, or pub.seal: checks it against the context and returns its [2][K][N] limbs
@@ -693,6 +780,21 @@ static const u64 *get_key_ciphertext(sealio::Reader &members, const Context &c, 
     if (h.size != 2 || h.N != c.N || h.limbs != (uint64_t)c.K || !h.is_ntt) members.fail("key polynomial dimensions do not match parm.seal");
     if (h.id != key_id) members.fail("parms_id is not the key-level id of parm.seal (key generated under other parameters?)");
     return data;
+}
+
+// one KSwitchKeys entry of exactly c.key_digits() digits under parms_id `id`: a device key [digits][2][c.K][N]
+static u64 *get_key_entry(sealio::Reader &r, const Context &c, const sealio::ParmsId &id)
+{
+    if (r.get<uint64_t>() != (uint64_t)c.key_digits()) r.fail("decomposition digit count differs from this context's");
+    const size_t per_digit = (size_t)2 * c.K * c.N;
+    u64 *key = dalloc((size_t)c.key_digits() * per_digit);
+    for (int j = 0; j < c.key_digits(); j++) {
+        std::vector<uint8_t> owned;
+        sealio::Reader m = open_object(r, owned);
+        const u64 *data = get_key_ciphertext(m, c, id);
+        DC_HIP_CHECK(hipMemcpy(key + (size_t)j * per_digit, data, per_digit * 8, hipMemcpyHostToDevice));
+    }
+    return key;
 }
 
 // KSwitchKeys::load_members: calls sink(index, digits [K-1][2][K][N] on the device) for every non-empty entry
@@ -789,6 +891,23 @@ void HEVM::load_keys(const std::string &dir, bool need_secret, bool need_public,
         std::vector<uint8_t> file, owned;
         sealio::Reader m = open_file("gal.seal", file, owned);
         get_kswitch_keys(m, c, key_id, [&](size_t index, u64 *key) { keys.galois[(u32)(2 * index + 1)] = key; });
+        if (FILE *f = fopen(join(dir, "boot.txt").c_str(), "r")) { // sparse-secret encapsulation keys (save_keys): evaluation keys, server side
+            int h = 0;
+            const bool ok = fscanf(f, "boot_secret_hw=%d", &h) == 1 && h > 0;
+            fclose(f);
+            if (!ok) {
+                fprintf(stderr, "[dacapo_amd] %s/boot.txt is malformed (expected \"boot_secret_hw=<h>\" with h > 0)\n", dir.c_str());
+                abort();
+            }
+            boot_secret_weight = h;
+            ensure_boot_context();
+            std::vector<uint8_t> bfile_bytes, bowned;
+            sealio::Reader b = open_file("boot_swk.seal", bfile_bytes, bowned);
+            if (b.get<sealio::ParmsId>() != key_id) b.fail("parms_id is not the key-level id of parm.seal");
+            if (b.get<uint64_t>() != 2) b.fail("expected two switching keys (s -> s', s' -> s)");
+            keys.swk_down = get_key_entry(b, *bctx, boot_parms_id());
+            keys.swk_up = get_key_entry(b, c, key_id);
+        }
     }
     rng = rng_keys_from_os(); // encryption randomness of this VM: fresh from the OS, unrelated to whatever generated the loaded keys
 }
@@ -1527,6 +1646,28 @@ void HEVM::op_modraise(int dst, int src, int target)
     modraise(*ctx, W().ks_digits, &it, 1, target, S());
     d.level = target, d.scale = s.scale;
 }
+// extension opcode 20 (hevm_asm.OP_KEYSWITCH, sparse-secret encapsulation): dst = lhs switched s -> s' (rhs = 0, at 1 prime, in the boot
+// context) or s' -> s (rhs = 1, any level).  A key-switch hop with the identity automorphism; level and scale unchanged.
+void HEVM::op_keyswitch(int dst, int src, int which)
+{
+    hevm_ctxt &s = reg(src);
+    hevm_ctxt &d = reg(dst);
+    if (!keys.swk_down || !keys.swk_up || which < 0 || which > 1) {
+        fprintf(stderr, "[dacapo_amd] keyswitch %d: %s\n", which,
+                which < 0 || which > 1 ? "rhs must be 0 (s -> s') or 1 (s' -> s)" : "the VM has no boot switching keys (option boot_secret_hw)");
+        abort();
+    }
+    if (which == 0) {
+        if (s.level != 1) {
+            fprintf(stderr, "[dacapo_amd] keyswitch 0: the key down to the ephemeral secret exists modulo q0 only; the operand sits at %d primes\n", s.level);
+            abort();
+        }
+        rotate_hop(*bctx, bctx->ws0, view(d), view(s), 1u, keys.swk_down, 1, S());
+    } else
+        rotate_hop(*ctx, W(), view(d), view(s), 1u, keys.swk_up, s.level, S());
+    n_keyswitch++, n_ntt += ks_ntts(s.level);
+    d.level = s.level, d.scale = s.scale;
+}
 void HEVM::op_setscale(int dst, int src, int const_idx)
 {
     hevm_ctxt &s = reg(src);
@@ -1702,6 +1843,7 @@ void HEVM::dispatch(const WireOp &op)
     case kOpConj: op_conj(op.dst, op.lhs); break;
     case kOpModRaise: op_modraise(op.dst, op.lhs, op.rhs); break;
     case kOpSetScale: op_setscale(op.dst, op.lhs, op.rhs); break;
+    case kOpKeySwitch: op_keyswitch(op.dst, op.lhs, op.rhs); break;
     default: break; // 0 = Encode (done in preprocess), 0xFFFF buffer marker and unknown opcodes are no-ops
     }
 }
@@ -1721,7 +1863,7 @@ void HEVM::execute()
                       << std::endl;
         }
         if (op.opcode <= 10) op_counts[op.opcode]++;
-        if (op.opcode == 0 || (op.opcode > 10 && (op.opcode < kOpConj || op.opcode > kOpSetScale))) continue;
+        if (op.opcode == 0 || (op.opcode > 10 && (op.opcode < kOpConj || op.opcode > kOpKeySwitch))) continue;
         dispatch(op);
     }
     bump_epoch(S());
@@ -1882,6 +2024,14 @@ void *hevm_context(void *vm)
     return h->ckks_handle;
 }
 const uint64_t *hevm_relin_key(void *vm) { return V(vm)->keys.relin; }
+int hevm_boot_switch_keys(void *vm, const uint64_t **down, const uint64_t **up, int *down_limbs)
+{
+    auto h = V(vm);
+    if (down) *down = h->keys.swk_down;
+    if (up) *up = h->keys.swk_up;
+    if (down_limbs) *down_limbs = h->keys.swk_down ? 1 + h->ctx->ksp : 0;
+    return h->keys.swk_down && h->keys.swk_up ? 1 : 0;
+}
 const uint64_t *hevm_galois_key(void *vm, uint32_t elt)
 {
     auto &g = V(vm)->keys.galois;
@@ -1964,6 +2114,8 @@ int hevm_key_buffers(void *vm, uint64_t **ptrs, uint64_t *words, int cap)
     for (const auto &kv : h->keys.galois) elts.push_back(kv.first);
     std::sort(elts.begin(), elts.end());
     for (u32 e : elts) v.push_back({ h->keys.galois.at(e), h->key_elems() });
+    if (h->keys.swk_down) v.push_back({ h->keys.swk_down, h->swk_down_elems() });
+    if (h->keys.swk_up) v.push_back({ h->keys.swk_up, h->key_elems() });
     for (int i = 0; i < (int)v.size() && i < cap; i++) ptrs[i] = v[(size_t)i].first, words[i] = (uint64_t)v[(size_t)i].second;
     return (int)v.size();
 }

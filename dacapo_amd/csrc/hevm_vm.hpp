@@ -76,11 +76,20 @@ struct KeySet {
     u64 *pk = nullptr;    // [2][K][N]
     u64 *relin = nullptr; // [K-1][2][K][N]
     std::map<u32, u64 *> galois;
+    // sparse-secret encapsulation (option boot_secret_hw > 0; opcode 20): swk_down switches s -> s' and exists only modulo q0 and the special
+    // primes ([1][2][1 + ksp][N], the boot context's layout, HEVM::bctx); swk_up switches s' -> s over the whole chain ([digits][2][K][N]).
+    // The ephemeral sparse secret s' itself is dropped as soon as both exist.
+    u64 *swk_down = nullptr;
+    u64 *swk_up = nullptr;
 };
 
 class HEVM {
   public:
     std::unique_ptr<Context> ctx;
+    // sparse-secret encapsulation: the chain {q0, special primes} as a context of its own (a level-1 key switch of `ctx` is exactly a key switch
+    // of this context), so that swk_down is stored over those 1 + ksp primes only and runs through the ordinary key-switch kernels
+    std::unique_ptr<Context> bctx;
+    void ensure_boot_context();
     std::unique_ptr<HostEncoder> encoder;
     KeySet keys;
     bool debug = false;
@@ -253,6 +262,7 @@ class HEVM {
     mutable std::vector<int> rot_offsets;   // offsets with a key, in the search order; rebuilt when the key set changes
     mutable std::set<int> rot_offset_set;
     mutable size_t rot_offsets_epoch = (size_t)-1;
+    int boot_secret_weight = 0; // option boot_secret_hw = h': key generation also draws an ephemeral secret of weight h' and the two switching keys
     int secret_weight = 0; // option secret_hw = h: key generation draws a ternary secret with exactly h non-zero coefficients (0: uniform ternary, SEAL's)
     bool chain_fusion = true; // option chain_fusion = 0: every step runs all of its own launches
     hipStream_t aux_stream = nullptr;
@@ -279,10 +289,15 @@ class HEVM {
     void init_context(int logN, int K, const u64 *primes, int dir_ksp = 0, int dir_alpha = 0);
     void generate_keys(const RngKeys &rng, bool secret, bool pub, bool eval);
     void gen_kswitch_key(u64 *key, const u64 *new_key, u64 key_id);
+    void gen_kswitch_key_in(Context &c, u64 *key, const u64 *key_sk, const u64 *new_key, u64 key_id); // key under key_sk for new_key, in context c
+    void fill_sparse_secret(u64 *dst, int weight, u32 domain);   // [K][N] coefficient form: exactly `weight` coefficients +-1
+    void generate_boot_switch_keys();
+    size_t swk_down_elems() const { return (size_t)2 * (1 + ctx->ksp) * ctx->N; }
     void add_galois_key(u32 elt);
     void save_keys(const std::string &dir);
     void load_keys(const std::string &dir, bool need_secret, bool need_public, bool need_eval);
     sealio::ParmsId parms_id_at(int limbs) const; // SEAL parms_id of the chain truncated to `limbs` primes (limbs = K: key level)
+    sealio::ParmsId boot_parms_id() const { return sealio::parms_id(bctx->N, bctx->primes.data(), (size_t)bctx->K); } // {q0, special primes}
     void save_ctxt(size_t reg, const std::string &path);
     void load_ctxt(size_t reg, const std::string &path);
 
@@ -310,6 +325,7 @@ class HEVM {
     void op_conj(int dst, int src);
     void op_modraise(int dst, int src, int target);
     void op_setscale(int dst, int src, int const_idx);
+    void op_keyswitch(int dst, int src, int which);
     std::vector<u32> rotate_hops(int steps) const;
 
     CtView view(const hevm_ctxt &c) const { return CtView{ c.data, (long)c.poly_stride }; }

@@ -118,7 +118,7 @@ int main(int argc, char **argv)
             // what load_program does next with the result: index the register files by every operand
             std::vector<char> cipher(pr.cipher_registers, 0), plain((size_t)pr.config.num_ptxt_buffer, 0);
             for (const WireOp &op : pr.ops) {
-                if (op.opcode > 10 && (op.opcode < kOpEncodeComplex || op.opcode > kOpSetScale)) continue;
+                if (op.opcode > 10 && (op.opcode < kOpEncodeComplex || op.opcode > kOpKeySwitch)) continue;
                 if (op.opcode == 0 || op.opcode == kOpEncodeComplex) {
                     plain.at(op.dst) = 1;
                     continue;

@@ -266,6 +266,27 @@ void HEVM::build_plan()
             cur[op.dst] = nv;
             break;
         }
+        case kOpKeySwitch: { // sparse-secret encapsulation: a key-switch hop with the identity automorphism and a key of its own
+            const int a = need(op.lhs, "keyswitch");
+            const Val s = P.vals[(size_t)a];
+            if (!keys.swk_down || !keys.swk_up || op.rhs > 1) {
+                fprintf(stderr, "[dacapo_amd] keyswitch %d: %s\n", (int)op.rhs,
+                        op.rhs > 1 ? "rhs must be 0 (s -> s') or 1 (s' -> s)" : "the VM has no boot switching keys (option boot_secret_hw)");
+                abort();
+            }
+            if (op.rhs == 0 && s.level != 1) {
+                fprintf(stderr, "[dacapo_amd] keyswitch 0: the key down to the ephemeral secret exists modulo q0 only; the operand sits at %d primes\n",
+                        s.level);
+                abort();
+            }
+            const int nv = new_val(s.level, s.scale);
+            Pop &p = add_pop(P_ROT, s.level, { a }, nv);
+            p.elt = 1u, p.key = op.rhs == 0 ? keys.swk_down : keys.swk_up;
+            if (op.rhs == 0) p.target_level = -1; // its step runs in the boot context (a bucket of its own: issue_step)
+            P.n_keyswitch++, P.n_ntt += ks_ntts(s.level);
+            cur[op.dst] = nv;
+            break;
+        }
         case kOpSetScale: { // a relabelled view of the same buffer
             const int a = need(op.lhs, "setscale");
             const Val s = P.vals[(size_t)a];
@@ -531,7 +552,7 @@ void HEVM::build_plan()
                     if (st < 0 || (ai >= 0 && st != ai)) continue;
                     const Step &A = P.steps[(size_t)st];
                     const bool kinds = (B.kind == P_RESCALE && A.kind == P_MULCC && A.level == B.level) ||
-                                       (B.kind == P_BOOT && ((A.kind == P_RESCALE && A.level - 1 == B.level) || (A.kind == P_ROT && A.level == B.level))) ||
+                                       (B.kind == P_BOOT && ((A.kind == P_RESCALE && A.level - 1 == B.level) || (A.kind == P_ROT && A.target >= 0 && A.level == B.level))) ||
                                        (B.kind == P_MULCC && A.kind == P_RESCALE && A.level - 1 == B.level);
                     if (!kinds || A.fused_consumer >= 0 || A.wave >= B.wave) continue;
                     if (B.kind == P_MULCC) { // the other operand: the same value, or complete before A starts
@@ -1133,7 +1154,7 @@ void HEVM::issue_step(const Step &st, hipStream_t q)
     Plan &P = plan;
     const BatchWs &w = P.ws[st.lane];
     switch (st.kind) {
-    case P_ROT: b_rotate_hops(c, w, P.d_ks + st.first, st.count, st.level, q, st.h, st.unique); break;
+    case P_ROT: b_rotate_hops(st.target < 0 ? *bctx : c, w, P.d_ks + st.first, st.count, st.level, q, st.h, st.unique); break;
     case P_ROTSUM: hyb_rotate_sum(c, w, P.d_ks + st.first, st.count, P.d_ks + st.gfirst, st.gcount, st.level, q, st.unique); break;
     case P_MULCC: b_mul_relin(c, w, P.d_mul + st.first, keys.relin, st.count, st.level, q, st.h); break;
     case P_RESCALE: b_rescale(c, w, P.d_rs + st.first, st.count, st.level, q, P.d_sum_srcs, st.h); break;

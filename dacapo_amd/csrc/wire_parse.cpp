@@ -76,7 +76,7 @@ bool parse_program(const void *data, size_t len, bool header_only, const std::ve
         // Operand validation, once: the reference indexes its register vectors unchecked (SEAL_HEVM.cpp:268-334); here a program
         // may name cipher registers beyond num_ctxt_buffer (the file grows with them) but never a plaintext register that does not exist.
         for (const WireOp &op : out.ops) {
-            if (op.opcode > 10 && (op.opcode < kOpEncodeComplex || op.opcode > kOpSetScale)) continue;
+            if (op.opcode > 10 && (op.opcode < kOpEncodeComplex || op.opcode > kOpKeySwitch)) continue;
             if (op.opcode == kOpSetScale) { // its operand is a constant that must exist NOW (the run path indexes it unchecked), hold a value, and be a scale
                 if (op.rhs >= constants.size() || constants[op.rhs].empty() || !(constants[op.rhs][0] > 0.0) || !std::isfinite(constants[op.rhs][0]))
                     return err = fmt(".hevm: setscale needs constant %lld of %lld to hold a finite positive scale (load the constants before the program)",

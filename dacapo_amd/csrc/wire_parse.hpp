@@ -32,7 +32,7 @@ struct WireOp {
     uint16_t opcode, dst, lhs, rhs;
 };
 // extension opcodes (dacapo_amd/hevm_asm.py OP_ENCODE_COMPLEX ...): not emitted by the reference's compiler, skipped by its VMs
-constexpr uint16_t kOpEncodeComplex = 16, kOpConj = 17, kOpModRaise = 18, kOpSetScale = 19;
+constexpr uint16_t kOpEncodeComplex = 16, kOpConj = 17, kOpModRaise = 18, kOpSetScale = 19, kOpKeySwitch = 20;
 static_assert(sizeof(WireHeader) == 24 && sizeof(WireConfigBody) == 40 && sizeof(WireOp) == 8, "HEVM wire format");
 
 namespace wire {

@@ -33,6 +33,7 @@ OP_ENCODE_COMPLEX = 16  # dst = plain reg, lhs = constant index (vector [re..., 
 OP_CONJ = 17            # dst = complex conjugate of lhs (Galois element 2N - 1, a key of the default set)
 OP_MODRAISE = 18        # dst = lhs (1 prime) re-read modulo the first rhs primes: decrypts to p + q0 * I
 OP_SETSCALE = 19        # dst = lhs with its scale label set to constants[rhs][0]
+OP_KEYSWITCH = 20       # dst = lhs switched to another secret: rhs = 0 s -> s' (1 prime only), 1 s' -> s (sparse-secret encapsulation)
 
 
 def write_cst(path, constants):
@@ -216,7 +217,8 @@ class Builder:
         self.carry_scale = carry_scale
         self.boot_level = init_level if boot_level is None else boot_level
         # real_boot = dict(num_primes=K, r=5, msg_bits=7): `bootstrap` emits REAL CKKS bootstrapping (dacapo_amd/ckks_boot.py: ModRaise,
-        # CoeffToSlot, EvalMod, SlotToCoeff over extension opcodes 16-19) instead of opcode 10, the SEAL VM's decrypt / re-encrypt stand-in
+        # CoeffToSlot, EvalMod, SlotToCoeff over extension opcodes 16-19) instead of opcode 10, the SEAL VM's decrypt / re-encrypt stand-in;
+        # sse=True: ModRaise runs under the ephemeral sparse secret (opcode 20 around it; the VM needs option boot_secret_hw)
         self.real_boot, self._boot_emitter, self._scale_mirror = real_boot, None, None
         self._memo: dict = {}  # lazy policy: (kind, value id, arg) -> value, so a shared operand is rescaled/bootstrapped once
         self.values: list[Value] = []
@@ -335,7 +337,8 @@ class Builder:
         logN = self.slots.bit_length()  # slots = N / 2
         if self._boot_emitter is None:
             self._boot_emitter = ckks_boot.BootstrapEmitter(self, logN, rb["num_primes"], t, r=rb.get("r", 5), msg_bits=rb.get("msg_bits", 0),
-                                                            out_bits=self.waterline, ks=rb.get("ks", 1), primes=rb.get("primes"))
+                                                            out_bits=self.waterline, ks=rb.get("ks", 1), primes=rb.get("primes"),
+                                                            sse=rb.get("sse", False))
             self._scale_mirror = ckks_boot.ScaleMirror(self, self._boot_emitter.primes)
         em = self._boot_emitter
         assert t == em.target, "every real bootstrap of a program restores the same number of primes"

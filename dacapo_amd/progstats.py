@@ -21,7 +21,7 @@ from __future__ import annotations
 
 from collections import Counter
 
-from .hevm_asm import (OP_ADDCC, OP_ADDCP, OP_BOOTSTRAP, OP_CONJ, OP_ENCODE, OP_ENCODE_COMPLEX, OP_MODRAISE, OP_MODSWITCH, OP_MULCC, OP_MULCP,
+from .hevm_asm import (OP_ADDCC, OP_ADDCP, OP_BOOTSTRAP, OP_CONJ, OP_ENCODE, OP_ENCODE_COMPLEX, OP_KEYSWITCH, OP_MODRAISE, OP_MODSWITCH, OP_MULCC, OP_MULCP,
                        OP_NEGATE, OP_RESCALE, OP_ROTATE, OP_SETSCALE, unpack_hevm)
 
 
@@ -65,7 +65,7 @@ def walk(hevm: bytes, logN: int = 15, direct_keys: bool = False) -> dict:
     limbs = 0  # algorithmic bytes in units of P_limb
     ks_hist, rs_hist, boot_hist, op_bytes = Counter(), Counter(), Counter(), Counter()
     for opc, dst, lhs, rhs in h["ops"].tolist():
-        if opc in (OP_ENCODE, OP_ENCODE_COMPLEX) or opc > OP_SETSCALE or BOOTSTRAP_GAP(opc):
+        if opc in (OP_ENCODE, OP_ENCODE_COMPLEX) or opc > OP_KEYSWITCH or BOOTSTRAP_GAP(opc):
             continue
         l = lvl[lhs]
         out_l, b = l, 0
@@ -102,7 +102,8 @@ def walk(hevm: bytes, logN: int = 15, direct_keys: bool = False) -> dict:
             out_l = rhs
             boot_hist[(l, rhs)] += 1
             b = 2 * l + 2 * rhs
-        elif opc == OP_CONJ:      # extension: conjugation = one key switch with the key of Galois element 2N - 1
+        elif opc in (OP_CONJ, OP_KEYSWITCH):  # extensions: conjugation = one key switch with the key of Galois element 2N - 1; opcode 20 =
+            # one key switch with a boot switching key (sparse-secret encapsulation), priced like a hop at the operand's level
             ks += 1
             ks_hist[l] += 1
             ntts += (l + 1) * (l + 2)

@@ -88,6 +88,9 @@ def bind_vm_lib(path):
     L.hevm_key_digest.argtypes = [ctypes.c_void_p]
     L.hevm_key_digest.restype = ctypes.c_uint64
     L.hevm_keys_replaced.argtypes = [ctypes.c_void_p]
+    L.hevm_boot_switch_keys.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
+                                        ctypes.POINTER(ctypes.c_int)]
+    L.hevm_boot_switch_keys.restype = ctypes.c_int
     L.hevm_galois_key.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
     L.hevm_galois_key.restype = ctypes.c_void_p
     L.hevm_plain.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double)]

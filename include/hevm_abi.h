@@ -105,8 +105,12 @@ void *hevm_context(void *vm);
 const uint64_t *hevm_relin_key(void *vm);
 const uint64_t *hevm_galois_key(void *vm, uint32_t elt);
 const uint64_t *hevm_public_key(void *vm);
+/* option "boot_secret_hw" (sparse-secret encapsulation, opcode 20): device pointers to the two PUBLIC switching keys.  *down = s -> s', only
+ * modulo q0 and the special primes: [1][2][*down_limbs][N] with *down_limbs = 1 + ks_special, limb 0 = q0; *up = s' -> s, laid out like a
+ * Galois key.  Returns 1 when the VM holds both, else 0 (pointers NULL). */
+int hevm_boot_switch_keys(void *vm, const uint64_t **down, const uint64_t **up, int *down_limbs);
 /* Key replication over VM replicas (one VM per GPU): the VM's key buffers in a canonical order (secret, public,
- * relinearisation, Galois keys by ascending element) -- device pointers and sizes in 64-bit words; returns their number (call with
+ * relinearisation, Galois keys by ascending element, the two boot switching keys if present) -- device pointers and sizes in 64-bit words; returns their number (call with
  * cap = 0 to size the arrays).  hevm_key_digest: a 64-bit digest of all of them, computed on the device.  hevm_keys_replaced: call
  * after overwriting the buffers from outside (bench.py --broadcast-keys: one flat RCCL broadcast per buffer from GPU 0). */
 int hevm_key_buffers(void *vm, uint64_t **ptrs, uint64_t *words, int cap);

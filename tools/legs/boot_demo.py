@@ -2,7 +2,9 @@
 """Real CKKS bootstrapping on the MI355X: one ciphertext at 1 prime -> `target` primes, through the extension opcodes and
 dacapo_amd/ckks_boot.py.   python tools/legs/boot_demo.py [logN=15] [r=5] [direct_keys=1] [target=3] [ks_special=1] [ks_alpha=ks_special] [--opt name=value ...]
 ks_special > 1: grouped-digit hybrid key switching (hybrid_ks.hip), the chain gets that many special primes.
-BASELINE config 4's geometry: python tools/legs/boot_demo.py 17 5 1 14 8 7"""
+BASELINE config 4's geometry: python tools/legs/boot_demo.py 17 5 1 14 8 7
+--sse <main weight>:<ephemeral weight> (e.g. 0:32 = SEAL's dense secret): sparse-secret encapsulation (options secret_hw / boot_secret_hw, opcode
+20 around ModRaise); without it the keys are generated under a weight-64 secret."""
 import os
 import sys
 import time
@@ -15,6 +17,12 @@ from dacapo_amd import ckks_boot as cb  # noqa: E402
 from dacapo_amd import hevm_asm as ha  # noqa: E402
 from dacapo_amd import runner  # noqa: E402
 
+sse_weights = None
+if "--sse" in sys.argv:
+    i = sys.argv.index("--sse")
+    sse_weights = tuple(int(w) for w in sys.argv[i + 1].split(":"))
+    assert len(sse_weights) == 2 and sse_weights[1] > 0, "--sse <main weight>:<ephemeral weight>"
+    del sys.argv[i:i + 2]
 sys.argv = runner.apply_cli_options(sys.argv)
 logN = int(sys.argv[1]) if len(sys.argv) > 1 else 15
 r = int(sys.argv[2]) if len(sys.argv) > 2 else 5
@@ -22,15 +30,16 @@ direct = int(sys.argv[3]) if len(sys.argv) > 3 else 1
 target = int(sys.argv[4]) if len(sys.argv) > 4 else 3
 ks = int(sys.argv[5]) if len(sys.argv) > 5 else 1
 alpha = int(sys.argv[6]) if len(sys.argv) > 6 else ks
-K, cst, hv, offs_all, em = cb.single_bootstrap_program(logN, target=target, r=r, ks=ks)
+K, cst, hv, offs_all, em = cb.single_bootstrap_program(logN, target=target, r=r, ks=ks, sse=sse_weights is not None)
 slots = 1 << (logN - 1)
 info = {'num_ops': len(ha.unpack_hevm(hv)['ops']), 'num_ptxt': ha.unpack_hevm(hv)['num_ptxt']}
+print(f"{'SSE: main secret weight %d (0: dense), ephemeral %d' % sse_weights if sse_weights else 'secret weight 64'}")
 print(f"N=2^{logN}, {K} primes ({ks} special), target {target}, r={r}: {info['num_ops']} instructions, {info['num_ptxt']} plaintexts, {len(cst)/1e6:.0f} MB of constants")
 msg = np.random.default_rng(3).uniform(-1, 1, slots)
 sim = cb.simulate(hv, cst, [msg], logN, em.primes)[0]
 print("cleartext simulation: max error", np.abs(sim - msg).max())
 t0 = time.time()
-hevm = runner.HEVM(fresh=True, logN=logN, num_primes=K, ks_special=ks, ks_alpha=alpha, vm_options={"secret_hw": 64})
+hevm = runner.HEVM(fresh=True, logN=logN, num_primes=K, ks_special=ks, ks_alpha=alpha, vm_options={"secret_hw": 64} if sse_weights is None else {"secret_hw": sse_weights[0], "boot_secret_hw": sse_weights[1]})
 print(f"context + keys: {time.time()-t0:.1f} s")
 if direct:
     offs = offs_all

@@ -8,6 +8,9 @@ rescalingFactor 51) -- on the generic-width build; the lowering must then have b
 lowering: another lowering of the same trace (tests/golden/<fixture>.<lowering>.hevm.gz, same constants), e.g. b14 = bootstraps placed at the
 model script's own hints, restoring 14 primes (38 bootstraps instead of 541); ks_special > 1: grouped-digit hybrid key switching with that
 many special primes (dacapo_amd/csrc/hybrid_ks.hip), which is what makes a 31-level chain affordable at N = 2^17.
+--sse <main weight>:<ephemeral weight> (e.g. 192:32, or 0:32 for SEAL's dense uniform ternary secret): sparse-secret encapsulation -- the keys
+are generated under a main secret of that weight and every ModRaise runs under an ephemeral sparse secret (options secret_hw / boot_secret_hw,
+opcode 20 around ModRaise); without it the whole key set is generated under a weight-64 secret.
 With fixture resnet20_nt16 (the same model traced at the reference script's own nt = 2^16 slots, examples/benchmarks/ResNet.py:50) and
 logN 17 this is the HEaaN runtime's ring (HEAAN_HEVM.cpp:55-56): ~100 GB of one-prime-per-digit Galois keys, sized for one MI355X."""
 import json
@@ -31,6 +34,12 @@ also = []
 while "--also-opt" in sys.argv:
     i = sys.argv.index("--also-opt")
     also.append({kv.partition("=")[0]: int(kv.partition("=")[2], 0) for kv in sys.argv[i + 1].split(",")})
+    del sys.argv[i:i + 2]
+sse_weights = None
+if "--sse" in sys.argv:
+    i = sys.argv.index("--sse")
+    sse_weights = tuple(int(w) for w in sys.argv[i + 1].split(":"))
+    assert len(sse_weights) == 2 and sse_weights[1] > 0, "--sse <main weight>:<ephemeral weight>"
     del sys.argv[i:i + 2]
 sys.argv = runner.apply_cli_options(sys.argv)  # --opt name=value (csrc/options.hpp)
 
@@ -62,7 +71,7 @@ elif chain == "mixed_app":
 else:
     primes = None
 t0 = time.time()
-fx["hevm"], fx["cst"] = cb.lower_bootstraps(fx["hevm"], fx["cst"], logN, KB, msg_bits=msg_bits, ks=ks, primes=primes)
+fx["hevm"], fx["cst"] = cb.lower_bootstraps(fx["hevm"], fx["cst"], logN, KB, msg_bits=msg_bits, ks=ks, primes=primes, sse=sse_weights is not None)
 print(f"opcode 10 -> real bootstrapping: {time.time()-t0:.1f} s", flush=True)
 h = ha.unpack_hevm(fx["hevm"])
 ops = h["ops"]
@@ -80,7 +89,8 @@ bounded = direct >= 49
 def one_run(extra_vm_options):
     """one VM: keys, load + preprocess, two runs (the second timed), the decrypted logits; the VM is destroyed before returning"""
     t0 = time.time()
-    hevm = runner.HEVM(fresh=True, logN=logN, num_primes=KB, ks_special=ks, ks_alpha=alpha, vm_options=dict({"secret_hw": 64, "rot_compose": int(bounded)}, **extra_vm_options),
+    hevm = runner.HEVM(fresh=True, logN=logN, num_primes=KB, ks_special=ks, ks_alpha=alpha, vm_options=dict({"secret_hw": 64, "rot_compose": int(bounded)} if sse_weights is None else
+                       {"secret_hw": sse_weights[0], "boot_secret_hw": sse_weights[1], "rot_compose": int(bounded)}, **extra_vm_options),
                        primes=primes)
     n_keys = 0
     if bounded:
