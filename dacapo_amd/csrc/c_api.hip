@@ -1,6 +1,8 @@
 // Kernel-level C ABI (include/dacapo_ckks.h): thin extern "C" shims over the launchers.
 #include "../../include/dacapo_ckks.h"
 
+#include <vector>
+
 #include "kernels.hpp"
 #include "plan.hpp"
 
@@ -76,6 +78,9 @@ int dc_context_max_level(const dc_context *ctx) { return ctx->c->max_level(); }
 void dc_context_destroy(dc_context *ctx)
 {
     if (ctx && ctx->item_ring) (void)hipFree(ctx->item_ring);
+    if (ctx)
+        for (void *p : { ctx->hoist_items, (void *)ctx->hoist_acc, (void *)ctx->hoist_tmp })
+            if (p) (void)hipFree(p);
     if (ctx && ctx->owned) delete ctx->c;
     delete ctx;
 }
@@ -202,6 +207,42 @@ void dc_ct_rotate_hop(dc_context *ctx, uint64_t *dst, long dst_stride, const uin
     const KsItem it{ V(src, src_stride), V(dst, dst_stride), galois_key, galois_elt, 0 };
     const KsItem *d = static_cast<const KsItem *>(item_slot(ctx, &it, sizeof(it), S(stream)));
     b_rotate_hops(*ctx->c, batch_ws(ctx->c->ws0), d, 1, ell, S(stream));
+}
+// `count` hops of one source on one decomposition (hoist_ks.hip).  The decomposition lives in the context's default workspace (one source);
+// what grows with the hop count -- the item table, the accumulators, the mod-down terms -- is kept in the handle and grown on demand
+// (growing waits for the device: hipFree).
+void dc_ct_rotate_hoisted(dc_context *ctx, uint64_t *const *dsts, long dst_stride, const uint64_t *src, long src_stride,
+                          const uint32_t *galois_elts, const uint64_t *const *galois_keys, int count, int ell, void *stream)
+{
+    Context &c = *ctx->c;
+    if (c.hybrid()) {
+        fprintf(stderr, "[dacapo_amd] dc_ct_rotate_hoisted: this context switches keys with grouped digits, where dc_ct_rotate_hop already takes "
+                        "the digits before the automorphism; the call is for SEAL-layout keys\n");
+        abort();
+    }
+    if (count < 1 || count > 65535 || ell < 1 || ell > c.max_level()) {
+        fprintf(stderr, "[dacapo_amd] dc_ct_rotate_hoisted: %d hops at level %d (1..65535 hops, level 1..%d)\n", count, ell, c.max_level());
+        abort();
+    }
+    auto grow = [](auto *&p, size_t &cap, size_t need) {
+        if (need <= cap) return;
+        if (p) DC_HIP_CHECK(hipFree(p));
+        p = nullptr;
+        DC_HIP_CHECK(hipMalloc(&p, need));
+        cap = need;
+    };
+    const size_t B = (size_t)count, N = c.N;
+    grow(ctx->hoist_items, ctx->hoist_item_cap, (B + 1) * sizeof(KsItem));
+    grow(ctx->hoist_acc, ctx->hoist_acc_cap, B * 2 * ((size_t)ell + 1) * N * sizeof(u64));
+    grow(ctx->hoist_tmp, ctx->hoist_tmp_cap, B * 2 * (size_t)ell * N * sizeof(u64));
+    std::vector<KsItem> h(B + 1);
+    for (size_t b = 0; b < B; b++) h[b] = KsItem{ V(src, src_stride), V(dsts[b], dst_stride), galois_keys[b], galois_elts[b], 0 };
+    h[B] = KsItem{ V(src, src_stride), V(src, src_stride), nullptr, 1u, 0 }; // the source, for the decomposition's loader
+    DC_HIP_CHECK(hipMemcpyAsync(ctx->hoist_items, h.data(), h.size() * sizeof(KsItem), hipMemcpyHostToDevice, S(stream)));
+    DC_HIP_CHECK(hipStreamSynchronize(S(stream))); // (the host table goes out of scope)
+    const KsItem *d = static_cast<const KsItem *>(ctx->hoist_items);
+    const BatchWs w{ c.ws0.ct_tmp, c.ws0.ks_digits, c.ws0.ks_ext, ctx->hoist_acc, ctx->hoist_tmp };
+    hoist_rotate_hops(c, w, d, d + B, count, 1, ell, S(stream));
 }
 void dc_ct_rescale(dc_context *ctx, uint64_t *dst, long dst_stride, const uint64_t *src, long src_stride, int ell, void *stream)
 {

@@ -7,4 +7,8 @@ struct dc_context {
     bool owned; // false when the context belongs to an HEVM (hevm_context())
     void *item_ring = nullptr; // device slots for the one-item tables of the fused composite ops (c_api.hip)
     unsigned item_next = 0;
+    // dc_ct_rotate_hoisted: item table [hops + 1], accumulators [hops][2][l+1][N] and mod-down terms [hops][2][l][N], grown on demand
+    void *hoist_items = nullptr;
+    dacapo::u64 *hoist_acc = nullptr, *hoist_tmp = nullptr;
+    size_t hoist_item_cap = 0, hoist_acc_cap = 0, hoist_tmp_cap = 0;
 };

@@ -452,6 +452,13 @@ void HEVM::init_context(int logN, int K, const u64 *primes, int dir_ksp, int dir
         }
         ksp = dir_ksp, alpha = dir_alpha;
     }
+    ks_hoist = option(OPT_KS_HOIST) != 0;
+    // (checked before the context exists: nothing has been allocated or launched)
+    if (ks_hoist && (ksp > 1 || alpha > 1)) {
+        fprintf(stderr, "[dacapo_amd] option ks_hoist = 1 is for SEAL-layout keys (ks_special = 1); with ks_special = %d, ks_alpha = %d key switching uses "
+                        "grouped digits, which already shares a source's decomposition among its hops\n", ksp, alpha);
+        abort();
+    }
     // prime_bits = b (45..60; the generic-width build only): the chain CoeffModulus::Create(N, {b, b, ...}) instead of the reference's
     // 60-bit one (SEAL_HEVM.cpp:48-53) -- e.g. 51 for rescale primes of the HEaaN configuration's width
     const int bits = (int)option(OPT_PRIME_BITS);
@@ -1510,6 +1517,23 @@ std::vector<int> HEVM::compose_rotation(int steps) const
 
 #define ks_ntts(ell) ks_ntt_count(*ctx, (ell))
 
+// one hop of a rotate / conj instruction in the loop: the default sequence, or (option ks_hoist) the hoisted definition with a decomposition
+// of its own -- the same limbs as a plan step that shares it (hoist_ks.hip).  dst may be src there.
+void HEVM::rotate_hop_vm(CtView dst, CtView src, u32 elt, const u64 *key, int ell)
+{
+    n_hops++, n_decomp++;
+    if (!ks_hoist) {
+        rotate_hop(*ctx, W(), dst, src, elt, key, ell, S());
+        return;
+    }
+    if (!d_hoist_items) DC_HIP_CHECK(vm_malloc(&d_hoist_items, 2 * sizeof(KsItem)));
+    const KsItem h[2] = { KsItem{ src, dst, key, elt, 0 }, KsItem{ src, src, nullptr, 1u, 0 } };
+    DC_HIP_CHECK(hipMemcpyAsync(d_hoist_items, h, sizeof h, hipMemcpyHostToDevice, S())); // (stream order: after the previous hop's kernels)
+    DC_HIP_CHECK(hipStreamSynchronize(S()));
+    const Workspace &w = W();
+    hoist_rotate_hops(*ctx, BatchWs{ w.ct_tmp, w.ks_digits, w.ks_ext, w.ks_acc, w.ks_tmp }, d_hoist_items, d_hoist_items + 1, 1, 1, ell, S());
+}
+
 void HEVM::op_rotate(int dst, int src, int offset)
 {
     hevm_ctxt &s = reg(src);
@@ -1519,7 +1543,7 @@ void HEVM::op_rotate(int dst, int src, int offset)
     const int ell = s.level;
     const hevm_ctxt *cur = &s;
     for (u32 elt : hops) {
-        rotate_hop(*ctx, W(), view(d), view(*cur), elt, keys.galois.at(elt), ell, S());
+        rotate_hop_vm(view(d), view(*cur), elt, keys.galois.at(elt), ell);
         cur = &d;
         n_keyswitch++, n_ntt += ks_ntts(ell);
     }
@@ -1630,7 +1654,7 @@ void HEVM::op_conj(int dst, int src)
         fprintf(stderr, "[dacapo_amd] conj: no Galois key for the conjugation\n");
         abort();
     }
-    rotate_hop(*ctx, W(), view(d), view(s), elt, keys.galois.at(elt), s.level, S());
+    rotate_hop_vm(view(d), view(s), elt, keys.galois.at(elt), s.level);
     n_keyswitch++, n_ntt += ks_ntts(s.level);
     d.level = s.level, d.scale = s.scale;
 }
@@ -1853,6 +1877,7 @@ void HEVM::execute()
 {
     memset(op_counts, 0, sizeof(op_counts));
     n_keyswitch = n_ntt = 0;
+    n_hops = n_decomp = 0;
     t_bootstrap = 0.0;
     int i = (int)((header.hevm_header_size + config.config_body_length) / 8), j = 0;
     for (const WireOp &op : ops) {
@@ -2232,6 +2257,13 @@ void hevm_last_run_stats(void *vm, int64_t *op_counts, int64_t *keyswitches, int
     if (op_counts) memcpy(op_counts, h->op_counts, sizeof(h->op_counts));
     if (keyswitches) *keyswitches = h->n_keyswitch;
     if (ntts) *ntts = h->n_ntt;
+}
+
+void hevm_last_run_hoist_stats(void *vm, int64_t *hops, int64_t *decompositions)
+{
+    auto h = V(vm);
+    if (hops) *hops = h->n_hops;
+    if (decompositions) *decompositions = h->n_decomp;
 }
 
 // option hyb_lazy_sum: which rotate instructions of the loaded program the plan of the last run() executed as lazy sums (one division by P

@@ -166,6 +166,7 @@ class HEVM {
         u32 elt = 0;
         const u64 *key = nullptr;
         int plain = -1, target_level = 0;
+        int rot = 0; // P_ROT: 1 a hop of a rotate / conj instruction, 2 the same on the hoisted path (option ks_hoist; target_level = -2: a bucket of its own); 0 opcode 20's switch
         int rs_add = -1, rs_mul = -1; // P_RESCALE: plain registers of a folded addcp / mulcp (operand = (srcs + add) * mul)
         bool rs_sum = false;          // P_RESCALE: srcs/src_plain are the terms of a folded n-ary sum
         int boot_drop = -1;           // P_BOOT: prime index of a folded rescale (operand read before the division), or -1
@@ -190,6 +191,7 @@ class HEVM {
         int fused_consumer = -1;            // index of the step whose first phase this step's last kernel computes
         int gfirst = 0, gcount = 0;         // P_SUM: the step's items as groups that share sources (plan.hpp SumGroup), when it runs that way; P_ROTSUM: its groups (in d_ks)
         int unique = 0;                     // P_ROT, grouped-digit mode: distinct source ciphertexts among the items (shared decompositions)
+                                            // ... and option ks_hoist (target == -2): the same count; d_ks[gfirst .. gfirst + unique) are the sources' items
         // what the step's launches read and write, by pool buffer (a value and its modswitch views share one): the edges of the explicitly
         // built graph (option plan_graph = 2, capture_plan_dag)
         std::vector<const u64 *> reads, writes;
@@ -231,6 +233,7 @@ class HEVM {
         std::vector<hipEvent_t> events; // fork/join pairs of the waves that use the auxiliary stream
         std::vector<u64 *> pool; // every pool buffer ever allocated (reused across plans)
         int64_t n_keyswitch = 0, n_ntt = 0;
+        int64_t n_hops = 0, n_decomp = 0; // rotation hops and the decompositions computed for them (hevm_last_run_hoist_stats)
         size_t launches = 0, max_live = 0;
         hipGraph_t graph = nullptr;
         hipGraphExec_t graph_exec = nullptr;
@@ -264,6 +267,11 @@ class HEVM {
     mutable size_t rot_offsets_epoch = (size_t)-1;
     int boot_secret_weight = 0; // option boot_secret_hw = h': key generation also draws an ephemeral secret of weight h' and the two switching keys
     int secret_weight = 0; // option secret_hw = h: key generation draws a ternary secret with exactly h non-zero coefficients (0: uniform ternary, SEAL's)
+    // option ks_hoist = 1 (SEAL-layout keys): every rotation hop takes c1's digits BEFORE the automorphism (hoist_ks.hip), and the hops of a
+    // plan step that read one source share its decomposition.  Changes the rounding: off by default.
+    bool ks_hoist = false;
+    KsItem *d_hoist_items = nullptr; // the loop's (plan = 0) two-entry item table: the hop and its source
+    void rotate_hop_vm(CtView dst, CtView src, u32 elt, const u64 *key, int ell);
     bool chain_fusion = true; // option chain_fusion = 0: every step runs all of its own launches
     hipStream_t aux_stream = nullptr;
     // option hyb_double_hoist = 1 (with hyb_lazy_sum): rotations multiplied by a plaintext join the lazy sums; the plaintexts' special-prime limbs
@@ -280,6 +288,7 @@ class HEVM {
     // statistics of the last run()
     int64_t op_counts[11] = { 0 };
     int64_t n_keyswitch = 0, n_ntt = 0;
+    int64_t n_hops = 0, n_decomp = 0; // hevm_last_run_hoist_stats
     double t_bootstrap = 0.0; // host wall time spent inside opcode 10
 
     VmAllocs allocs;   // device memory held by this VM (hevm_destroy)

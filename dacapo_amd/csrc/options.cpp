@@ -37,6 +37,7 @@ static const OptDef kDefs[OPT_COUNT] = {
     { "hyb_fuse", 2 },
     { "hyb_lazy_sum", 0 },
     { "hyb_double_hoist", 0 },
+    { "ks_hoist", 0 },
     { "seal_compr", 0 },
     { "trace", 0 },
     { "step_profile", 0 },

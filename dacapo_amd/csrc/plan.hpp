@@ -105,6 +105,10 @@ void b_mul_relin(Context &c, const BatchWs &w, const MulItem *d_items, const u64
                  const Handoff &h = Handoff{});
 void b_rescale(Context &c, const BatchWs &w, const RsItem *d_items, int B, int ell, hipStream_t s, const SumSrc *d_srcs = nullptr,
                const Handoff &h = Handoff{});
+// hoisted rotations on SEAL-layout keys (hoist_ks.hip; option ks_hoist, dc_ct_rotate_hoisted): B hops over U <= B decompositions, digits taken
+// BEFORE the automorphism (oracle orc_rotate_ks_hybrid at one special prime).  d_items[b].slot indexes d_sources[0 .. U): items with the
+// identity element whose src is the source ciphertext.  w is sized as for B default hops.
+void hoist_rotate_hops(Context &c, const BatchWs &w, const KsItem *d_items, const KsItem *d_sources, int B, int U, int ell, hipStream_t s);
 bool chain_fusion_supported(); // the continuation kernels exist for the default launch sequences only
 // grouped-digit hybrid key switching (hybrid_ks.hip; Context::hybrid()): b_rotate_hops / b_mul_relin / keyswitch route here
 void hyb_rotate_hops(Context &c, const BatchWs &w, const KsItem *d_items, int B, int ell, hipStream_t s, int unique = 0);

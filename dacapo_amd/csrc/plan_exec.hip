@@ -51,6 +51,7 @@ void HEVM::build_plan()
     P.graph_exec = nullptr, P.graph = nullptr;
     P.vals.clear(), P.pops.clear(), P.steps.clear();
     P.n_keyswitch = P.n_ntt = 0;
+    P.n_hops = P.n_decomp = 0;
     const size_t nreg = ciphers.size();
     const int S = streams; // independent ciphertext streams executed side by side (items of every step are replicated)
     std::vector<int> cur(nreg, -1);
@@ -113,6 +114,7 @@ void HEVM::build_plan()
                 const int nv = new_val(s.level, in_scale);
                 Pop &p = add_pop(P_ROT, s.level, { v }, nv);
                 p.elt = elt, p.key = keys.galois.at(elt);
+                p.rot = ks_hoist ? 2 : 1, p.target_level = ks_hoist ? -2 : 0; // (hoisted hops: steps of their own, issue_step)
                 p.op = (int)(&op - ops.data()), p.direct = &elt == &hops.back(); // (the LAST hop of the instruction: the one whose result the program sees)
                 P.n_keyswitch++, P.n_ntt += ks_ntts(s.level);
                 if (rot_compose) {
@@ -249,6 +251,7 @@ void HEVM::build_plan()
             const int nv = new_val(s.level, s.scale);
             Pop &p = add_pop(P_ROT, s.level, { a }, nv);
             p.elt = elt, p.key = keys.galois.at(elt);
+            p.rot = ks_hoist ? 2 : 1, p.target_level = ks_hoist ? -2 : 0;
             P.n_keyswitch++, P.n_ntt += ks_ntts(s.level);
             cur[op.dst] = nv;
             break;
@@ -489,7 +492,14 @@ void HEVM::build_plan()
             // order and read the key out of L2 (fused_ks.hip f_ks_frows_mac_kernel).  The order of a step's items is free: every item names
             // its own source and destination, and a linked consumer step is re-ordered to follow its producer below (4b).  Grouped-digit
             // steps keep program order (their items are grouped by SOURCE, which shares the decomposition).
-            if (kind == P_ROT && !c.hybrid() && option(OPT_KS_ITEMS_FAST))
+            // Hoisted steps (option ks_hoist) are source-major, then by key: consecutive items read the same decomposition's tiles, and a
+            // source's hops stay in one step unless max_batch cuts between them (each side then computes the decomposition).
+            if (kind == P_ROT && std::get<2>(kv.first) == -2)
+                std::stable_sort(kv.second.begin(), kv.second.end(), [&](int x, int y) {
+                    const Pop &a = O[(size_t)x], &b = O[(size_t)y];
+                    return a.srcs[0] != b.srcs[0] ? a.srcs[0] < b.srcs[0] : a.elt < b.elt;
+                });
+            else if (kind == P_ROT && !c.hybrid() && option(OPT_KS_ITEMS_FAST))
                 std::stable_sort(kv.second.begin(), kv.second.end(), [&](int x, int y) { return O[(size_t)x].elt < O[(size_t)y].elt; });
             const bool heavy = kind == P_ROT || kind == P_MULCC || kind == P_RESCALE || kind == P_BOOT || kind == P_ROTSUM;
             const size_t chunk = std::max<size_t>(1, (heavy ? (size_t)max_batch : (size_t)4096) / (size_t)S);
@@ -759,14 +769,25 @@ void HEVM::build_plan()
             {
                 // grouped-digit mode: hops of one source ciphertext share its decomposition (inverse NTT, mod-up, NTT of the raised limbs):
                 // bootstrapping's baby steps, a convolution's taps.  slot = index of the source among the step's distinct sources.
+                // Option ks_hoist (st.target == -2) shares it the same way on SEAL-layout keys: the decompositions live in the step's lifted-digit
+                // scratch, [distinct sources][l*l][N] of the [items][l*l][N] that max_batch reserves -- a step has at most as many sources as items,
+                // so max_batch is the cap.  The sources' own items (identity element: the decomposition's loader) follow the hops' in the table.
+                const bool hoisted = st.target == -2;
                 std::map<const u64 *, u32> slot_of;
+                std::vector<KsItem> sources;
                 for (int pi : step_pops[s])
                     for (int q = 0; q < S; q++) {
                         const CtView sv = view(O[(size_t)pi].srcs[0], q);
-                        const u32 slot = c.hybrid() ? slot_of.emplace(sv.p, (u32)slot_of.size()).first->second : 0u;
+                        if (hoisted && !slot_of.count(sv.p)) sources.push_back(KsItem{ sv, sv, nullptr, 1u, 0 });
+                        const u32 slot = (c.hybrid() || hoisted) ? slot_of.emplace(sv.p, (u32)slot_of.size()).first->second : 0u;
                         h_ks.push_back(KsItem{ sv, view(O[(size_t)pi].dst, q), O[(size_t)pi].key, O[(size_t)pi].elt, slot });
                     }
                 st.unique = (int)slot_of.size();
+                st.gfirst = (int)h_ks.size(), st.gcount = (int)sources.size();
+                h_ks.insert(h_ks.end(), sources.begin(), sources.end());
+                for (int pi : step_pops[s])
+                    if (O[(size_t)pi].rot) P.n_hops += S, P.n_decomp += hoisted ? 0 : S;
+                if (hoisted) P.n_decomp += st.unique;
             }
             break;
         case P_ROTSUM: { // the rotations of every group, adjacent; then one entry per group: dst, first item (relative), item count
@@ -787,6 +808,7 @@ void HEVM::build_plan()
                     }
                 }
             st.unique = (int)slot_of.size();
+            P.n_hops += (int64_t)(h_ks.size() - (size_t)st.first), P.n_decomp += (int64_t)(h_ks.size() - (size_t)st.first);
             st.gfirst = (int)h_ks.size(), st.gcount = (int)groups.size();
             h_ks.insert(h_ks.end(), groups.begin(), groups.end());
             break;
@@ -1154,7 +1176,12 @@ void HEVM::issue_step(const Step &st, hipStream_t q)
     Plan &P = plan;
     const BatchWs &w = P.ws[st.lane];
     switch (st.kind) {
-    case P_ROT: b_rotate_hops(st.target < 0 ? *bctx : c, w, P.d_ks + st.first, st.count, st.level, q, st.h, st.unique); break;
+    case P_ROT:
+        if (st.target == -2) { // option ks_hoist: st.unique decompositions for st.count hops
+            hoist_rotate_hops(c, w, P.d_ks + st.first, P.d_ks + st.gfirst, st.count, st.unique, st.level, q);
+            break;
+        }
+        b_rotate_hops(st.target < 0 ? *bctx : c, w, P.d_ks + st.first, st.count, st.level, q, st.h, st.unique); break;
     case P_ROTSUM: hyb_rotate_sum(c, w, P.d_ks + st.first, st.count, P.d_ks + st.gfirst, st.gcount, st.level, q, st.unique); break;
     case P_MULCC: b_mul_relin(c, w, P.d_mul + st.first, keys.relin, st.count, st.level, q, st.h); break;
     case P_RESCALE: b_rescale(c, w, P.d_rs + st.first, st.count, st.level, q, P.d_sum_srcs, st.h); break;
@@ -1403,6 +1430,7 @@ void HEVM::run_plan()
     for (const WireOp &op : ops)
         if (op.opcode <= 10) op_counts[op.opcode]++;
     n_keyswitch = P.n_keyswitch, n_ntt = P.n_ntt;
+    n_hops = P.n_hops, n_decomp = P.n_decomp;
     t_bootstrap = 0.0;
     const long ps = (long)c.K * (long)c.N;
     if (plan_graph) { // the plan is a fixed launch sequence: recorded once (normally by preprocess()), replayed as one graph launch

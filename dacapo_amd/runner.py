@@ -100,6 +100,7 @@ def bind_vm_lib(path):
     L.hevm_load_mem.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_char_p, ctypes.c_uint64]
     L.hevm_last_run_stats.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
                                        ctypes.POINTER(ctypes.c_int64)]
+    L.hevm_last_run_hoist_stats.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
     L.hevm_plan_lazy_groups.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32), ctypes.c_int64]
     L.hevm_plan_lazy_groups.restype = ctypes.c_int64
     L.hevm_set_streams.argtypes = [ctypes.c_void_p, ctypes.c_int]
@@ -224,7 +225,7 @@ class HEVM:
         ks_special / ks_alpha (extension): grouped-digit hybrid key switching -- the last ks_special primes are special, a digit is
         ks_alpha (default ks_special) data primes.  1 / 1 = the reference's SEAL scheme.  vm_options: further VM options of
         csrc/options.hpp (plan, plan_graph, secret_hw, logn, primes, ...), in force while this VM is created; the previous values are put
-        back afterwards (a VM keeps what it was created with).  primes (extension, seeded VMs): an explicit chain, e.g. a HEaaN-style
+        back afterwards (a VM keeps what it was created with); e.g. {"ks_hoist": 1}: hoisted rotations on SEAL-layout keys (hoist_stats()).  primes (extension, seeded VMs): an explicit chain, e.g. a HEaaN-style
         mixed one (60-bit base and special primes around 51-bit rescale primes); a chain with primes narrower than 60 bits -- given here or
         through vm_options["prime_bits"] -- runs on the generic-width build of the same sources (libSEAL_HEVM_gw.so)."""
         reinit_lw()
@@ -387,6 +388,12 @@ class HEVM:
             out.append(list(buf[i + 1 : i + 1 + buf[i]]))
             i += 1 + buf[i]
         return out
+
+    def hoist_stats(self):
+        """option ks_hoist: rotation hops of the last run() and the decompositions computed for them (equal with the option off)"""
+        hops, dec = ctypes.c_int64(), ctypes.c_int64()
+        self.lw.hevm_last_run_hoist_stats(self.vm, ctypes.byref(hops), ctypes.byref(dec))
+        return {"hops": hops.value, "decompositions": dec.value}
 
     def stats(self):
         counts = (ctypes.c_int64 * 11)()

@@ -99,6 +99,14 @@ void dc_ct_mul_relin(dc_context *ctx, uint64_t *dst, long dst_stride, const uint
 /* Evaluator::apply_galois_inplace: one hop of Evaluator::rotate_vector   SEAL_HEVM.cpp:273 */
 void dc_ct_rotate_hop(dc_context *ctx, uint64_t *dst, long dst_stride, const uint64_t *src, long src_stride,
                       uint32_t galois_elt, const uint64_t *galois_key, int ell, void *stream);
+/* EXTENSION (not SEAL's rounding): `count` hops of ONE source ciphertext sharing one decomposition -- the digits of c1 are taken before the
+ * automorphism (inverse NTT, every digit lifted to every modulus, forward NTT: once per call) and each hop reads them through its Galois
+ * permutation: oracle orc_rotate_ks_hybrid at one special prime / one prime per digit, limb for limb, for every count.  dsts / elts / keys:
+ * host arrays of length count; keys in dc_ct_rotate_hop's layout.  A dst may be src; the dsts must be distinct.  SEAL-layout contexts only
+ * (a grouped-digit context aborts with a message: its dc_ct_rotate_hop already hoists).  Scratch is kept in the context, sized on first use.
+ * The item table is copied synchronously: the call waits for earlier work on `stream`. */
+void dc_ct_rotate_hoisted(dc_context *ctx, uint64_t *const *dsts, long dst_stride, const uint64_t *src, long src_stride,
+                          const uint32_t *galois_elts, const uint64_t *const *galois_keys, int count, int ell, void *stream);
 /* Evaluator::rescale_to_next: level ell -> ell-1   SEAL_HEVM.cpp:283 */
 void dc_ct_rescale(dc_context *ctx, uint64_t *dst, long dst_stride, const uint64_t *src, long src_stride, int ell,
                    void *stream);

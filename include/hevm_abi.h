@@ -125,6 +125,11 @@ const uint64_t *hevm_plain_special(void *vm, int64_t i);
 void hevm_load_mem(void *vm, const void *cst, uint64_t cst_len, const void *hevm, uint64_t hevm_len);
 /* per-opcode launch statistics of the last run(): counts[11], NTT-equivalents executed */
 void hevm_last_run_stats(void *vm, int64_t *op_counts /*[11]*/, int64_t *keyswitches, int64_t *ntts);
+/* option "ks_hoist" (SEAL-layout keys, off by default): rotation hops the last run() executed -- every hop of a rotate or conj instruction,
+ * per stream; opcode 20's switches are not rotations -- and the decompositions (inverse NTT, lift, forward NTT of c1's digits) computed for
+ * them.  With the option on, the hops of a plan step that read one source ciphertext share one decomposition; with it off, or under option
+ * "plan" = 0, every hop computes its own and the two numbers are equal. */
+void hevm_last_run_hoist_stats(void *vm, int64_t *hops, int64_t *decompositions);
 /* option "hyb_lazy_sum" (grouped-digit mode, off by default): the rotate instructions the last run()'s plan executed as lazy sums -- the
  * accumulators of a group's key switches added in the raised basis, ONE division by P per group.  out = [n_0, op ...,
  * n_1, op ...]: per group its size and its rotations' instruction indices.  Returns the length of that list (written if cap suffices), 0 without

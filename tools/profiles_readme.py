@@ -229,6 +229,7 @@ rows = [bench_row6("r06"), traffic_row("r06"), step_row("r06"), valu_row("r06"),
         f"| `r06_ntt_full_check.txt` | single-crossing kernel / two-launch tiles, µs, by limb count: {check_lines('r06_ntt_full_check.txt')} | `tools/legs/ntt_full_check.py <limbs> 20` |",
         f"| `r06_kernel_stats.csv`, `r06_by_kernel_and_grid.txt`, `r06_timeline.txt`, `r06_top_kernels.json`, `r06_roofline_leg_launches.txt` | the bench command under the kernel trace: {first_lines('r06_timeline.txt', 'last run', 1)} | `rocprofv3 --kernel-trace --stats … -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-config4` |",
         "| `r06_hybrid_ks_kernels.txt`, `r06_boot_kernel_bytes.txt`, `r06_per_op.json`, `r06_per_op_kernel_stats.csv`, `r06_lowering_sweep.txt`, `r06_per_op_sweep.txt`, `r06_chain_latency.txt`, `r06_profiled_SEAL_MI355X.json` | as in round 5 on this build | see round 5's rows |"]
+rows.append("| `ks_hoist_ab.txt` | hoisted rotations on SEAL-layout keys (option `ks_hoist`, after round 6): `dc_ct_rotate_hoisted` for r = 1, 2, 4, 8 hops of one source against r × `dc_ct_rotate_hop` under device events at N = 2^15 / 13 primes and N = 2^16 / 24 primes, and `run()` of the headline and of its 13-prime lowering with the option off and on: time, hops, decompositions, rms against the torch logits; which programs gain is stated in the file | `python tools/legs/ks_hoist_ab.py --out profiles/ks_hoist_ab.txt` |")
 print("\n".join(r for r in rows if r))
 print()
 print("## Round 5 (everything `r05_*`; one `gpurun` call of `tools/collect_profiles.sh r05` on the committed build -- the JSON files that `bench.py` reads carry "
