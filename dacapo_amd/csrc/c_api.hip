@@ -1,6 +1,7 @@
 // Kernel-level C ABI (include/dacapo_ckks.h): thin extern "C" shims over the launchers.
 #include "../../include/dacapo_ckks.h"
 
+#include <algorithm>
 #include <vector>
 
 #include "kernels.hpp"
@@ -79,7 +80,7 @@ void dc_context_destroy(dc_context *ctx)
 {
     if (ctx && ctx->item_ring) (void)hipFree(ctx->item_ring);
     if (ctx)
-        for (void *p : { ctx->hoist_items, (void *)ctx->hoist_acc, (void *)ctx->hoist_tmp })
+        for (void *p : { ctx->hoist_items, (void *)ctx->hoist_acc, (void *)ctx->hoist_tmp, (void *)ctx->hoist_digits, (void *)ctx->hoist_ext })
             if (p) (void)hipFree(p);
     if (ctx && ctx->owned) delete ctx->c;
     delete ctx;
@@ -243,6 +244,60 @@ void dc_ct_rotate_hoisted(dc_context *ctx, uint64_t *const *dsts, long dst_strid
     const KsItem *d = static_cast<const KsItem *>(ctx->hoist_items);
     const BatchWs w{ c.ws0.ct_tmp, c.ws0.ks_digits, c.ws0.ks_ext, ctx->hoist_acc, ctx->hoist_tmp };
     hoist_rotate_hops(c, w, d, d + B, count, 1, ell, S(stream));
+}
+// dst = sum_k [plains[k] .] galois_k(srcs[k]) with ONE division by P (hoist_ks.hip hoist_rotate_sum): equal source pointers share a
+// decomposition, which is why the decompositions need scratch of their own here ([distinct sources][l][N] digits and [..][l*l][N] lifted limbs,
+// kept in the handle like the rest and grown on demand).
+void dc_ct_rotate_sum_hoisted(dc_context *ctx, uint64_t *dst, long dst_stride, const uint64_t *const *srcs, long src_stride,
+                              const uint32_t *galois_elts, const uint64_t *const *galois_keys, const uint64_t *const *plains,
+                              const uint64_t *const *plains_sp, int count, int ell, void *stream)
+{
+    Context &c = *ctx->c;
+    if (c.hybrid()) {
+        fprintf(stderr, "[dacapo_amd] dc_ct_rotate_sum_hoisted: this context switches keys with grouped digits (ks_special > 1); the call is for "
+                        "SEAL-layout keys\n");
+        abort();
+    }
+    if (count < 1 || count > 65535 || ell < 1 || ell > c.max_level()) {
+        fprintf(stderr, "[dacapo_amd] dc_ct_rotate_sum_hoisted: %d members at level %d (1..65535 members, level 1..%d)\n", count, ell, c.max_level());
+        abort();
+    }
+    auto grow = [](auto *&p, size_t &cap, size_t need) {
+        if (need <= cap) return;
+        if (p) DC_HIP_CHECK(hipFree(p));
+        p = nullptr;
+        DC_HIP_CHECK(hipMalloc(&p, need));
+        cap = need;
+    };
+    const size_t B = (size_t)count, N = c.N;
+    // members source-major (stable: equal sources keep the caller's order); then the group; then the distinct sources
+    std::vector<size_t> order(B);
+    for (size_t b = 0; b < B; b++) order[b] = b;
+    std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return srcs[x] < srcs[y]; });
+    std::vector<KsItem> h, sources;
+    for (size_t b : order) {
+        const u64 *pl = plains ? plains[b] : nullptr, *psp = plains_sp ? plains_sp[b] : nullptr;
+        if ((pl == nullptr) != (psp == nullptr)) {
+            fprintf(stderr, "[dacapo_amd] dc_ct_rotate_sum_hoisted: member %zu has one of plains / plains_sp only\n", b);
+            abort();
+        }
+        const CtView sv = V(srcs[b], src_stride);
+        if (sources.empty() || sources.back().src.p != sv.p) sources.push_back(KsItem{ sv, sv, nullptr, 1u, 0 });
+        h.push_back(KsItem{ sv, V(dst, dst_stride), galois_keys[b], galois_elts[b], (u32)(sources.size() - 1), pl, psp });
+    }
+    const size_t U = sources.size();
+    h.push_back(KsItem{ V(dst, dst_stride), V(dst, dst_stride), nullptr, 0u, (u32)B });
+    h.insert(h.end(), sources.begin(), sources.end());
+    grow(ctx->hoist_items, ctx->hoist_item_cap, h.size() * sizeof(KsItem));
+    grow(ctx->hoist_acc, ctx->hoist_acc_cap, 2 * ((size_t)ell + 1) * N * sizeof(u64));
+    grow(ctx->hoist_tmp, ctx->hoist_tmp_cap, 2 * (size_t)ell * N * sizeof(u64));
+    grow(ctx->hoist_digits, ctx->hoist_digits_cap, U * (size_t)ell * N * sizeof(u64));
+    grow(ctx->hoist_ext, ctx->hoist_ext_cap, U * (size_t)ell * ell * N * sizeof(u64));
+    DC_HIP_CHECK(hipMemcpyAsync(ctx->hoist_items, h.data(), h.size() * sizeof(KsItem), hipMemcpyHostToDevice, S(stream)));
+    DC_HIP_CHECK(hipStreamSynchronize(S(stream))); // (the host table goes out of scope)
+    const KsItem *d = static_cast<const KsItem *>(ctx->hoist_items);
+    const BatchWs w{ nullptr, ctx->hoist_digits, ctx->hoist_ext, ctx->hoist_acc, ctx->hoist_tmp };
+    hoist_rotate_sum(c, w, d, d + B + 1, count, (int)U, d + B, 1, ell, S(stream));
 }
 void dc_ct_rescale(dc_context *ctx, uint64_t *dst, long dst_stride, const uint64_t *src, long src_stride, int ell, void *stream)
 {

@@ -11,4 +11,7 @@ struct dc_context {
     void *hoist_items = nullptr;
     dacapo::u64 *hoist_acc = nullptr, *hoist_tmp = nullptr;
     size_t hoist_item_cap = 0, hoist_acc_cap = 0, hoist_tmp_cap = 0;
+    // dc_ct_rotate_sum_hoisted uses the same three, plus the decompositions of its distinct sources: digits [U][l][N], lifted limbs [U][l*l][N]
+    dacapo::u64 *hoist_digits = nullptr, *hoist_ext = nullptr;
+    size_t hoist_digits_cap = 0, hoist_ext_cap = 0;
 };

@@ -459,6 +459,17 @@ void HEVM::init_context(int logN, int K, const u64 *primes, int dir_ksp, int dir
                         "grouped digits, which already shares a source's decomposition among its hops\n", ksp, alpha);
         abort();
     }
+    ks_lazy = (int)option(OPT_KS_LAZY_SUM);
+    if (ks_lazy && (ksp > 1 || alpha > 1)) {
+        fprintf(stderr, "[dacapo_amd] option ks_lazy_sum = %d is for SEAL-layout keys (ks_special = 1); with ks_special = %d, ks_alpha = %d the lazy sums "
+                        "of grouped-digit key switching are options hyb_lazy_sum / hyb_double_hoist\n", ks_lazy, ksp, alpha);
+        abort();
+    }
+    if (ks_lazy && !ks_hoist) {
+        fprintf(stderr, "[dacapo_amd] option ks_lazy_sum = %d needs ks_hoist = 1: a lazy sum is defined on digits taken before the automorphism "
+                        "(ks_hoist = 0 here)\n", ks_lazy);
+        abort();
+    }
     // prime_bits = b (45..60; the generic-width build only): the chain CoeffModulus::Create(N, {b, b, ...}) instead of the reference's
     // 60-bit one (SEAL_HEVM.cpp:48-53) -- e.g. 51 for rescale primes of the HEaaN configuration's width
     const int bits = (int)option(OPT_PRIME_BITS);
@@ -472,7 +483,7 @@ void HEVM::init_context(int logN, int K, const u64 *primes, int dir_ksp, int dir
     host_encoder = option(OPT_HOST_ENCODER) != 0;
     fold_rescale_into_boot = option(OPT_FOLD_RESCALE_BOOT) != 0;
     lazy_sums = option(OPT_HYB_LAZY_SUM) != 0;
-    double_hoist = lazy_sums && option(OPT_HYB_DOUBLE_HOIST) != 0;
+    double_hoist = (lazy_sums && option(OPT_HYB_DOUBLE_HOIST) != 0) || ks_lazy == 2; // (preprocess keeps the constants and the encode items)
     max_batch = std::max(1, (int)option(OPT_MAX_BATCH));
     chain_fusion = option(OPT_CHAIN_FUSION) != 0;
     secret_weight = (int)option(OPT_SECRET_HW);
@@ -2266,8 +2277,8 @@ void hevm_last_run_hoist_stats(void *vm, int64_t *hops, int64_t *decompositions)
     if (decompositions) *decompositions = h->n_decomp;
 }
 
-// option hyb_lazy_sum: which rotate instructions of the loaded program the plan of the last run() executed as lazy sums (one division by P
-// per group).  out = [n_0, op, ..., op, n_1, op, ...]: per group its size and the instruction indices of its rotations, ascending.  Returns
+// options hyb_lazy_sum / ks_lazy_sum: which rotate instructions of the loaded program the plan of the last run() executed as lazy sums (one
+// division by P per group; under ks_lazy_sum on SEAL-layout keys, hoist_ks.hip hoist_rotate_sum).  out = [n_0, op, ..., op, n_1, op, ...]: per group its size and the instruction indices of its rotations, ascending.  Returns
 // the number of int32 values the list takes (written only if cap is large enough), 0 without groups, -1 before the first run().
 int64_t hevm_plan_lazy_groups(void *vm, int32_t *out, int64_t cap)
 {

@@ -189,7 +189,7 @@ class HEVM {
         int wave = 0, lane = 0;             // steps of one wave are independent: lane 1 runs on the auxiliary stream
         Handoff h;                          // link to a fused producer (h.in) / consumer (h.cont, h.out) step, plan.hpp
         int fused_consumer = -1;            // index of the step whose first phase this step's last kernel computes
-        int gfirst = 0, gcount = 0;         // P_SUM: the step's items as groups that share sources (plan.hpp SumGroup), when it runs that way; P_ROTSUM: its groups (in d_ks)
+        int gfirst = 0, gcount = 0;         // P_SUM: the step's items as groups that share sources (plan.hpp SumGroup), when it runs that way; P_ROTSUM: its groups (in d_ks; option ks_lazy_sum: the distinct sources' items follow them)
         int unique = 0;                     // P_ROT, grouped-digit mode: distinct source ciphertexts among the items (shared decompositions)
                                             // ... and option ks_hoist (target == -2): the same count; d_ks[gfirst .. gfirst + unique) are the sources' items
         // what the step's launches read and write, by pool buffer (a value and its modswitch views share one): the edges of the explicitly
@@ -270,6 +270,9 @@ class HEVM {
     // option ks_hoist = 1 (SEAL-layout keys): every rotation hop takes c1's digits BEFORE the automorphism (hoist_ks.hip), and the hops of a
     // plan step that read one source share its decomposition.  Changes the rounding: off by default.
     bool ks_hoist = false;
+    // option ks_lazy_sum (with ks_hoist): 1 sums of bare rotations share one division by P, 2 rotations times a plaintext join them too
+    // (plan_exec.hip section 2b; hoist_ks.hip hoist_rotate_sum)
+    int ks_lazy = 0;
     KsItem *d_hoist_items = nullptr; // the loop's (plan = 0) two-entry item table: the hop and its source
     void rotate_hop_vm(CtView dst, CtView src, u32 elt, const u64 *key, int ell);
     bool chain_fusion = true; // option chain_fusion = 0: every step runs all of its own launches

@@ -16,6 +16,11 @@
 //   f_irows_rot_c1 (identity element)  ->  [icols] + lift + fcols (fused_ks.hip, U items)  ->  launch_ntt_rows_fwd over the U l*l limbs (stores)
 //   f_ks_gmac (B items: gather + inner products + base term + first inverse phase of the special prime)
 //   [icols] -> f_dr_(icols_)lift_fcols -> f_frows_final        the default sequence's tail, unchanged
+//
+// Lazy sums (option ks_lazy_sum, dc_ct_rotate_sum_hoisted): G sums  dst_g = sum_k [pt_k] galois_k(src_k)  of B members over U sources divide by P
+// ONCE per sum.  The decomposition stage is the same; f_ks_gsum takes the place of f_ks_gmac -- a workgroup walks the members of its group and
+// leaves ONE accumulator pair per group -- and the tail runs over 2G polynomials instead of 2B.  The definition is the oracle's
+// orc_rotate_acc_hybrid per member, Oracle.lazy_mul_plain / lazy_add, and one orc_moddown_hybrid per group, limb for limb.
 #include "ntt_tile.hpp"
 #include "plan.hpp"
 #include "tile_dispatch.hpp"
@@ -152,42 +157,229 @@ static void f_ks_gmac(const Context &c, const u64 *L, const KsItem *items, u64 *
 #undef DC_GMAC
 }
 
+// The group form of f_ks_gmac_kernel: grid = (tiles, l + 2 - MERGE, G) or, groups_fast, (tiles, G, l + 2 - MERGE).  Workgroup (tile, y, g) owns the
+// tile's coefficients of output modulus slot m of GROUP g (groups[g]: dst, elt = first member in items, slot = member count) and walks the
+// members: per member the pair indices once, the digits gathered through the member's own permutation from the member's own source's
+// decomposition (items[k].slot), the inner products with the member's key, and the base term P galois_k(c0_k) on acc_0 of a data prime -- here
+// one more PRODUCT (c0 . P) instead of a reduced start value, because a member may join accumulators that are already in use.
+//   bare member:        its products go straight into the group's accumulators s0, s1;
+//   plaintext member:   they go into accumulators a0, a1 of its own, which are reduced to canonical words and multiplied by the plaintext's
+//                       limb at m (plain [level][N] on a data prime, plain_sp [1][N] on the special one): one more mac per accumulator.
+// An Acc128 holds 16 products of canonical residues.  What has landed in an accumulator since its last fold is COUNTED (ns for the group's pair,
+// na for a member's; wave-uniform) and the pair is folded to canonical words -- which then count as one product -- before a 17th would join:
+// 63 members x l digits pass through one pair.  Every stored limb is canonical and modular sums are exact in any order, so the result does not
+// depend on where the folds fall.  The finish is f_ks_gmac_kernel's.
+template <int K, int LOGE, bool MERGE>
+__global__ __launch_bounds__(kTileThreads) void f_ks_gsum_kernel(const u64 *__restrict__ L, const KsItem *__restrict__ items,
+                                                                  const KsItem *__restrict__ groups, u64 *__restrict__ acc, int ell, int Kp,
+                                                                  const DModulus *__restrict__ mods, const u64 *__restrict__ itw, int logN,
+                                                                  const u64 *__restrict__ pmod, int groups_fast)
+{
+    __shared__ __attribute__((aligned(16))) u64 lds[TileGeo<LOGE>::LDS_ELEMS];
+    constexpr int E = 1 << LOGE, NP = num_passes<LOGE>(K);
+    static_assert(E >= 2, "pairs");
+    const int y = groups_fast ? blockIdx.z : blockIdx.y, g = groups_fast ? blockIdx.y : blockIdx.z, sp = Kp - 1;
+    const int m = y < ell ? y : ell, psel = (MERGE && y == ell) ? -1 : y - ell; // psel < 0: both accumulators
+    const int pm = m == ell ? sp : m;
+    const size_t N = (size_t)1 << logN;
+    const DModulus M = mods[pm];
+    const KsItem gr = groups[g];
+    const KsItem *mem = items + gr.elt;
+    const int cnt = (int)gr.slot;
+    const int g0 = tile_gidx<K, LOGE, false>(NP - 1, logN, blockIdx.x, 0);
+    const u64 P = m < ell ? pmod[m] : 0;
+    auto fold = [&](Acc128(&x0)[E], Acc128(&x1)[E]) {
+#pragma unroll
+        for (int e = 0; e < E; e++) {
+            const u64 f0 = x0[e].reduce(M), f1 = x1[e].reduce(M);
+            x0[e].clear(), x1[e].clear();
+            x0[e].lo = f0, x1[e].lo = f1;
+        }
+    };
+    auto room = [&](Acc128(&x0)[E], Acc128(&x1)[E], int &n) { // one more product per accumulator is about to land
+        if (n == 16) fold(x0, x1), n = 1;
+        n++;
+    };
+    Acc128 s0[E], s1[E];
+#pragma unroll
+    for (int e = 0; e < E; e++) s0[e].clear(), s1[e].clear();
+    int ns = 0;
+    for (int k = 0; k < cnt; k++) {
+        const KsItem it = mem[k];
+        u32 gi[E / 2];
+#pragma unroll
+        for (int h = 0; h < E / 2; h++) gi[h] = hoist_galois_idx((u32)(g0 + 2 * h), it.elt, logN);
+        auto gather = [&](u64(&x)[E], const u64 *__restrict__ p) {
+#pragma unroll
+            for (int h = 0; h < E / 2; h++) {
+                const u64x2 v = *reinterpret_cast<const u64x2 *>(p + (gi[h] & ~1u));
+                x[2 * h] = (gi[h] & 1u) ? v.y : v.x, x[2 * h + 1] = (gi[h] & 1u) ? v.x : v.y;
+            }
+        };
+        const u64 *Ls = L + (size_t)it.slot * ell * ell * N;
+        auto products = [&](Acc128(&x0)[E], Acc128(&x1)[E], int &n) { // the member's base term and inner products into (x0, x1)
+            if (m < ell) {
+                u64 cv[E];
+                gather(cv, it.src.limb(0, m, N));
+                room(x0, x1, n);
+#pragma unroll
+                for (int e = 0; e < E; e++) x0[e].mac(cv[e], P);
+            }
+            for (int j = 0; j < ell; j++) {
+                const u64 *src = j == m ? it.src.limb(1, j, N) : Ls + ((size_t)j * ell + (m < j ? m : m - 1)) * N;
+                const u64 *k0 = it.key + (((size_t)j * 2 + 0) * Kp + pm) * N + g0, *k1 = it.key + (((size_t)j * 2 + 1) * Kp + pm) * N + g0;
+                u64 x[E];
+                gather(x, src);
+                room(x0, x1, n);
+                if (psel != 1) {
+#pragma unroll
+                    for (int h = 0; h < E / 2; h++) {
+                        const u64x2 kv = *reinterpret_cast<const u64x2 *>(k0 + 2 * h);
+                        x0[2 * h].mac(x[2 * h], kv.x), x0[2 * h + 1].mac(x[2 * h + 1], kv.y);
+                    }
+                }
+                if (psel != 0) {
+#pragma unroll
+                    for (int h = 0; h < E / 2; h++) {
+                        const u64x2 kv = *reinterpret_cast<const u64x2 *>(k1 + 2 * h);
+                        x1[2 * h].mac(x[2 * h], kv.x), x1[2 * h + 1].mac(x[2 * h + 1], kv.y);
+                    }
+                }
+            }
+        };
+        if (!it.plain) {
+            products(s0, s1, ns);
+            continue;
+        }
+        Acc128 a0[E], a1[E];
+#pragma unroll
+        for (int e = 0; e < E; e++) a0[e].clear(), a1[e].clear();
+        int na = 0;
+        products(a0, a1, na);
+        const u64 *pt = (m < ell ? it.plain + (size_t)m * N : it.plain_sp) + g0;
+        room(s0, s1, ns);
+#pragma unroll
+        for (int h = 0; h < E / 2; h++) {
+            const u64x2 w = *reinterpret_cast<const u64x2 *>(pt + 2 * h);
+            if (psel != 1) s0[2 * h].mac(a0[2 * h].reduce(M), w.x), s0[2 * h + 1].mac(a0[2 * h + 1].reduce(M), w.y);
+            if (psel != 0) s1[2 * h].mac(a1[2 * h].reduce(M), w.x), s1[2 * h + 1].mac(a1[2 * h + 1].reduce(M), w.y);
+        }
+    }
+    if (m < ell) {
+        u64 *ac = acc + (size_t)g * 2 * (ell + 1) * N;
+        u64 *o0 = ac + ((size_t)0 * (ell + 1) + m) * N + g0, *o1 = ac + ((size_t)1 * (ell + 1) + m) * N + g0;
+#pragma unroll
+        for (int h = 0; h < E / 2; h++) {
+            u64x2 r0, r1;
+            r0.x = s0[2 * h].reduce(M), r0.y = s0[2 * h + 1].reduce(M), r1.x = s1[2 * h].reduce(M), r1.y = s1[2 * h + 1].reduce(M);
+            *reinterpret_cast<u64x2 *>(o0 + 2 * h) = r0, *reinterpret_cast<u64x2 *>(o1 + 2 * h) = r1;
+        }
+    } else { // the special prime's accumulators continue in registers into the inverse ROWS phase the mod-down starts with
+        auto nold = [](int) -> u64 { return 0; };
+        const int p_lo = MERGE ? 0 : psel, p_hi = MERGE ? 1 : psel;
+        for (int p = p_lo; p <= p_hi; p++) {
+            u64 r[E];
+#pragma unroll
+            for (int e = 0; e < E; e++) r[e] = p == 0 ? s0[e].reduce(M) : s1[e].reduce(M);
+            u64 *o = acc + (((size_t)g * 2 + p) * (ell + 1) + ell) * N;
+            if (p != p_lo) __syncthreads(); // the previous tile's last LDS image has been read by everyone
+            ntt_tile_x<K, LOGE, false, true, false, true, false>(r, M, itw + ((size_t)sp << logN), logN, blockIdx.x, nold,
+                                                                 [=](int gidx, u64 v) { o[gidx] = v; }, lds);
+        }
+    }
+}
+
+// geometry and merging chosen as f_ks_gmac chooses them, with groups in the place of hops
+static void f_ks_gsum(const Context &c, const u64 *L, const KsItem *items, const KsItem *groups, u64 *acc, int G, int ell, hipStream_t s)
+{
+#define DC_GSUM(LEV)                                                                                                                      \
+    {                                                                                                                                     \
+        constexpr int LE = LEV;                                                                                                           \
+        const long wgs = (long)(c.N >> TileGeo<LE>::LOG) * (ell + 2) * G;                                                                \
+        const int merge = wgs >= (long)option(OPT_KS_MERGE_SPECIAL_MIN_WGS) ? 1 : 0;                                                      \
+        const int groups_fast = (G > 1 && G <= 65535 && option(OPT_KS_ITEMS_FAST)) ? 1 : 0;                                              \
+        const dim3 grid((unsigned)(c.N >> TileGeo<LE>::LOG), (unsigned)(groups_fast ? G : ell + 2 - merge), (unsigned)(groups_fast ? ell + 2 - merge : G)); \
+        if (merge) {                                                                                                                      \
+            DC_K_SWITCH(c.k2, DC_LAUNCH((f_ks_gsum_kernel<KK, LE, true>), grid, dim3(kTileThreads), 0, s, L, items, groups, acc, ell, c.K, \
+                                        c.d_mods, c.d_itw, c.logN, c.d_pmod, groups_fast));                                               \
+        } else {                                                                                                                          \
+            DC_K_SWITCH(c.k2, DC_LAUNCH((f_ks_gsum_kernel<KK, LE, false>), grid, dim3(kTileThreads), 0, s, L, items, groups, acc, ell, c.K, \
+                                        c.d_mods, c.d_itw, c.logN, c.d_pmod, groups_fast));                                               \
+        }                                                                                                                                 \
+    }
+    if (use_tiny_tiles(c.N, (long)(ell + 2) * G))
+        DC_GSUM(1)
+    else
+        DC_GSUM(2)
+#undef DC_GSUM
+}
+
 // B hops over U decompositions.  d_items[b].slot names the hop's source among d_sources[0 .. U) (items with the identity element whose
 // src is the source ciphertext).  Scratch: w.digits [U][l][N], w.ext [U][l*l][N] (the decompositions), w.acc [B][2][l+1][N], w.tmp [B][2][l][N]
 // -- U <= B, so a BatchWs sized for B default hops holds it.  A hop's destination may be its source: every read of a source precedes the
 // last launch, the only one that writes a destination.
-void hoist_rotate_hops(Context &c, const BatchWs &w, const KsItem *d_items, const KsItem *d_sources, int B, int U, int ell, hipStream_t s)
+static void hoist_check(const Context &c, const char *who, int B, int U, int G, int ell)
 {
     if (c.hybrid()) {
         fprintf(stderr, "[dacapo_amd] hoisted rotations are for SEAL-layout keys: grouped-digit key switching (ks_special > 1) already shares "
                         "the decomposition among the hops of a source\n");
         abort();
     }
-    if (B < 1 || U < 1 || U > B || ell < 1 || ell > c.max_level()) {
-        fprintf(stderr, "[dacapo_amd] hoist_rotate_hops: %d hops over %d sources at level %d\n", B, U, ell);
+    if (B < 1 || U < 1 || U > B || G < 1 || G > B || ell < 1 || ell > c.max_level()) {
+        fprintf(stderr, "[dacapo_amd] %s: %d hops over %d sources in %d sums at level %d\n", who, B, U, G, ell);
         abort();
     }
+}
+
+// decompose: U x l digits, each lifted to its l other moduli, stored in NTT form in w.ext
+static void hoist_decompose(Context &c, const BatchWs &w, const KsItem *d_sources, int U, int ell, hipStream_t s)
+{
     const size_t N = c.N;
-    const int sp = c.K - 1;
-    const long big = (long)option(OPT_KS_BIG_TILES);
-    // decompose: U x l digits, each lifted to its l other moduli, stored in NTT form
     f_irows_rot_c1(c, d_sources, ell, w.digits, U, s);
-    if ((long)(N >> 10) * U * ell * ell >= big) {
+    if ((long)(N >> 10) * U * ell * ell >= (long)option(OPT_KS_BIG_TILES)) {
         launch_ntt_cols_inv(c, w.digits, (long)N, U * ell, nullptr, 0, ell, s);
         f_ks_lift_fcols(c, w.digits, w.ext, U, ell, s);
     } else
         f_ks_icols_lift_fcols(c, w.digits, w.ext, U, ell, s);
     launch_ntt_rows_fwd(c, w.ext, (long)N, U * ell * ell, c.ks_prime_idx(ell), 0, ell * ell, s);
-    // per hop: inner products through the Galois map, then the default sequence's mod-down
-    f_ks_gmac(c, w.ext, d_items, w.acc, B, ell, s);
+}
+
+// the default sequence's mod-down over R accumulator pairs w.acc [R][2][l+1][N] (the special prime's limbs after their first inverse phase, the
+// base terms folded in); d_dsts[r].dst is where pair r goes
+static void hoist_moddown(Context &c, const BatchWs &w, const KsItem *d_dsts, int R, int ell, hipStream_t s)
+{
+    const size_t N = c.N;
+    const int sp = c.K - 1;
     u64 *acc_last = w.acc + (size_t)ell * N;
     const long acc_ps = (long)(ell + 1) * (long)N;
-    if ((long)(N >> 10) * B * ell * ell >= big) {
-        launch_ntt_cols_inv(c, acc_last, acc_ps, 2 * B, nullptr, sp, 1, s);
-        f_dr_lift_fcols(c, acc_last, acc_ps, w.tmp, 2 * B, ell, sp, s);
+    if ((long)(N >> 10) * R * ell * ell >= (long)option(OPT_KS_BIG_TILES)) {
+        launch_ntt_cols_inv(c, acc_last, acc_ps, 2 * R, nullptr, sp, 1, s);
+        f_dr_lift_fcols(c, acc_last, acc_ps, w.tmp, 2 * R, ell, sp, s);
     } else
-        f_dr_icols_lift_fcols(c, acc_last, acc_ps, w.tmp, 2 * B, ell, sp, s);
-    f_frows_final(c, 0, w.tmp, d_items, w.acc, 2 * B, ell, sp, s, RsItem{}, nullptr, nullptr, Handoff{}, true);
+        f_dr_icols_lift_fcols(c, acc_last, acc_ps, w.tmp, 2 * R, ell, sp, s);
+    f_frows_final(c, 0, w.tmp, d_dsts, w.acc, 2 * R, ell, sp, s, RsItem{}, nullptr, nullptr, Handoff{}, true);
+}
+
+void hoist_rotate_hops(Context &c, const BatchWs &w, const KsItem *d_items, const KsItem *d_sources, int B, int U, int ell, hipStream_t s)
+{
+    hoist_check(c, "hoist_rotate_hops", B, U, 1, ell);
+    hoist_decompose(c, w, d_sources, U, ell, s);
+    // per hop: inner products through the Galois map, then the default sequence's mod-down
+    f_ks_gmac(c, w.ext, d_items, w.acc, B, ell, s);
+    hoist_moddown(c, w, d_items, B, ell, s);
+}
+
+// G lazy sums of B members over U decompositions: d_groups[g] = { dst: the sum's destination, elt: its first member in d_items, slot: its
+// member count } (a group's members are adjacent; their own dst is unused), d_items[b].slot / d_sources as above, d_items[b].plain / plain_sp the
+// plaintext multiplying member b in the raised basis, or null.  Scratch: w.digits / w.ext as above, w.acc [G][2][l+1][N], w.tmp [G][2][l][N]
+// -- U, G <= B.  A destination may be one of the sources: only the last launch writes, and it reads no source.
+void hoist_rotate_sum(Context &c, const BatchWs &w, const KsItem *d_items, const KsItem *d_sources, int B, int U, const KsItem *d_groups, int G,
+                      int ell, hipStream_t s)
+{
+    hoist_check(c, "hoist_rotate_sum", B, U, G, ell);
+    hoist_decompose(c, w, d_sources, U, ell, s);
+    f_ks_gsum(c, w.ext, d_items, d_groups, w.acc, G, ell, s);
+    hoist_moddown(c, w, d_groups, G, ell, s);
 }
 
 } // namespace dacapo

@@ -38,6 +38,7 @@ static const OptDef kDefs[OPT_COUNT] = {
     { "hyb_lazy_sum", 0 },
     { "hyb_double_hoist", 0 },
     { "ks_hoist", 0 },
+    { "ks_lazy_sum", 0 },
     { "seal_compr", 0 },
     { "trace", 0 },
     { "step_profile", 0 },

@@ -109,6 +109,11 @@ void b_rescale(Context &c, const BatchWs &w, const RsItem *d_items, int B, int e
 // BEFORE the automorphism (oracle orc_rotate_ks_hybrid at one special prime).  d_items[b].slot indexes d_sources[0 .. U): items with the
 // identity element whose src is the source ciphertext.  w is sized as for B default hops.
 void hoist_rotate_hops(Context &c, const BatchWs &w, const KsItem *d_items, const KsItem *d_sources, int B, int U, int ell, hipStream_t s);
+// lazy sums on the same decompositions (option ks_lazy_sum, dc_ct_rotate_sum_hoisted): G sums of B members, ONE division by P per sum (oracle
+// orc_rotate_acc_hybrid per member, Oracle.lazy_mul_plain / lazy_add, one orc_moddown_hybrid per group).  d_groups[g] as for hyb_rotate_sum:
+// dst, elt = first member, slot = member count; a member's plain / plain_sp ([level][N] / [1][N]) multiply it in the raised basis, or null
+void hoist_rotate_sum(Context &c, const BatchWs &w, const KsItem *d_items, const KsItem *d_sources, int B, int U, const KsItem *d_groups, int G,
+                      int ell, hipStream_t s);
 bool chain_fusion_supported(); // the continuation kernels exist for the default launch sequences only
 // grouped-digit hybrid key switching (hybrid_ks.hip; Context::hybrid()): b_rotate_hops / b_mul_relin / keyswitch route here
 void hyb_rotate_hops(Context &c, const BatchWs &w, const KsItem *d_items, int B, int ell, hipStream_t s, int unique = 0);

@@ -391,7 +391,12 @@ void HEVM::build_plan()
     // result than n rotate instructions, limb-wise, which is why the option is off by default and why the rule is narrow and exported
     // (hevm_plan_lazy_groups; the oracle VM replays exactly these groups): a member is the LAST hop of a rotate instruction (the only one under a
     // direct key) whose result nothing else reads, entering the sum as it is (no plaintext factor); a sum needs at least two of them.
-    if (lazy_sums && hyb_lazy_sum_supported(c)) {
+    // Option ks_lazy_sum opens the same pass to SEAL-layout keys (hoist_ks.hip hoist_rotate_sum; needs ks_hoist: the definition takes the digits
+    // before the automorphism).  A member there is a hoisted hop (rot == 2) that is the last hop of a ROTATE instruction -- never a conj hop,
+    // never opcode 20's switch, which set neither `direct` nor an instruction -- and a term times a plaintext joins under value 2 only.
+    const bool seal_sums = !c.hybrid() && ks_lazy != 0;
+    const bool taps_join = c.hybrid() ? double_hoist : ks_lazy == 2;
+    if ((lazy_sums && hyb_lazy_sum_supported(c)) || seal_sums) {
         for (size_t ci = 0; ci < O.size(); ci++) {
             if (O[ci].dead) continue;
             if (!(O[ci].kind == P_SUM || ((O[ci].kind == P_RESCALE || O[ci].kind == P_BOOT) && O[ci].rs_sum))) continue;
@@ -400,13 +405,14 @@ void HEVM::build_plan()
                 // a term times a plaintext joins only under option hyb_double_hoist: its product is then taken in the raised basis, which needs
                 // the plaintext over the special primes too (encoded below, from the resident constants)
                 if (!O[ci].src_plain.empty() && O[ci].src_plain[k] >= 0 &&
-                    !(double_hoist && !online_encode && !host_encoder && dh_items.count(O[ci].src_plain[k]) && plains.at((size_t)O[ci].src_plain[k]).level >= O[ci].level))
+                    !(taps_join && !online_encode && !host_encoder && dh_items.count(O[ci].src_plain[k]) && plains.at((size_t)O[ci].src_plain[k]).level >= O[ci].level))
                     continue;
                 const int sidx = O[ci].srcs[k];
                 const Val &sv = V[(size_t)sidx];
                 const int dp = sv.root == sidx ? sv.def_pop : -1;
                 if (dp < 0) continue;
                 const Pop &r = O[(size_t)dp];
+                if (seal_sums && !(r.rot == 2 && r.op >= 0 && ops[(size_t)r.op].opcode == 1)) continue;
                 if (r.kind == P_ROT && !r.dead && r.direct && r.dst == sidx && sv.uses == 1 && !sv.pinned && r.level == O[ci].level) terms.push_back(k);
             }
             if (terms.size() < 2) continue;
@@ -415,6 +421,7 @@ void HEVM::build_plan()
             const size_t keep = terms.back();
             Pop grp = O[(size_t)V[(size_t)O[ci].srcs[keep]].def_pop];
             grp.kind = P_ROTSUM, grp.srcs.clear(), grp.direct = false, grp.op = -1;
+            grp.rot = 0, grp.target_level = 0; // (a hoisted hop's bucket mark is not the group's)
             for (size_t k : terms) {
                 Pop &r = O[(size_t)V[(size_t)O[ci].srcs[k]].def_pop];
                 grp.srcs.push_back(r.srcs[0]), grp.elts.push_back(r.elt), grp.keys.push_back(r.key), grp.ops.push_back(r.op);
@@ -793,14 +800,19 @@ void HEVM::build_plan()
         case P_ROTSUM: { // the rotations of every group, adjacent; then one entry per group: dst, first item (relative), item count
             st.first = (int)h_ks.size();
             std::map<const u64 *, u32> slot_of;
-            std::vector<KsItem> groups;
+            std::vector<KsItem> groups, sources;
             for (int pi : step_pops[s])
                 for (int q = 0; q < S; q++) {
                     const Pop &rp = O[(size_t)pi];
                     const CtView dst = view(rp.dst, q);
                     groups.push_back(KsItem{ dst, dst, nullptr, (u32)(h_ks.size() - (size_t)st.first), (u32)rp.srcs.size() });
-                    for (size_t k = 0; k < rp.srcs.size(); k++) {
+                    // (option ks_lazy_sum: group-major, then by source -- a group's members that read one decomposition are adjacent)
+                    std::vector<size_t> order(rp.srcs.size());
+                    for (size_t k = 0; k < order.size(); k++) order[k] = k;
+                    if (!c.hybrid()) std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return rp.srcs[x] < rp.srcs[y]; });
+                    for (size_t k : order) {
                         const CtView sv = view(rp.srcs[k], q);
+                        if (!c.hybrid() && !slot_of.count(sv.p)) sources.push_back(KsItem{ sv, sv, nullptr, 1u, 0 });
                         const u32 slot = slot_of.emplace(sv.p, (u32)slot_of.size()).first->second;
                         const int pl = rp.plains.empty() ? -1 : rp.plains[k];
                         h_ks.push_back(KsItem{ sv, dst, rp.keys[k], rp.elts[k], slot, pl >= 0 ? plains.at((size_t)pl).d : nullptr,
@@ -808,9 +820,12 @@ void HEVM::build_plan()
                     }
                 }
             st.unique = (int)slot_of.size();
-            P.n_hops += (int64_t)(h_ks.size() - (size_t)st.first), P.n_decomp += (int64_t)(h_ks.size() - (size_t)st.first);
+            // (SEAL-layout keys: one decomposition per distinct source of the step; grouped digits report one per hop, as before)
+            P.n_hops += (int64_t)(h_ks.size() - (size_t)st.first);
+            P.n_decomp += c.hybrid() ? (int64_t)(h_ks.size() - (size_t)st.first) : (int64_t)st.unique;
             st.gfirst = (int)h_ks.size(), st.gcount = (int)groups.size();
             h_ks.insert(h_ks.end(), groups.begin(), groups.end());
+            h_ks.insert(h_ks.end(), sources.begin(), sources.end()); // (option ks_lazy_sum: the decompositions' loader items, behind the groups)
             break;
         }
         case P_MULCC:
@@ -1182,7 +1197,12 @@ void HEVM::issue_step(const Step &st, hipStream_t q)
             break;
         }
         b_rotate_hops(st.target < 0 ? *bctx : c, w, P.d_ks + st.first, st.count, st.level, q, st.h, st.unique); break;
-    case P_ROTSUM: hyb_rotate_sum(c, w, P.d_ks + st.first, st.count, P.d_ks + st.gfirst, st.gcount, st.level, q, st.unique); break;
+    case P_ROTSUM:
+        if (!c.hybrid()) { // option ks_lazy_sum: st.gcount sums of st.count members over st.unique decompositions
+            hoist_rotate_sum(c, w, P.d_ks + st.first, P.d_ks + st.gfirst + st.gcount, st.count, st.unique, P.d_ks + st.gfirst, st.gcount, st.level, q);
+            break;
+        }
+        hyb_rotate_sum(c, w, P.d_ks + st.first, st.count, P.d_ks + st.gfirst, st.gcount, st.level, q, st.unique); break;
     case P_MULCC: b_mul_relin(c, w, P.d_mul + st.first, keys.relin, st.count, st.level, q, st.h); break;
     case P_RESCALE: b_rescale(c, w, P.d_rs + st.first, st.count, st.level, q, P.d_sum_srcs, st.h); break;
     case P_SUM:

@@ -78,6 +78,7 @@ def _bind(path):
         L.dc_ct_mul_relin.argtypes = [vp, u64p, lng, u64p, lng, u64p, lng, u64p, i32, vp]
         L.dc_ct_rotate_hop.argtypes = [vp, u64p, lng, u64p, lng, C.c_uint32, u64p, i32, vp]
         L.dc_ct_rotate_hoisted.argtypes = [vp, vp, lng, u64p, lng, vp, vp, i32, i32, vp]
+        L.dc_ct_rotate_sum_hoisted.argtypes = [vp, u64p, lng, vp, lng, vp, vp, vp, vp, i32, i32, vp]
         L.dc_ct_rescale.argtypes = [vp, u64p, lng, u64p, lng, i32, vp]
         L.dc_ct_modswitch.argtypes = [vp, u64p, lng, u64p, lng, i32, i32, vp]
         L.dc_keyswitch.argtypes = [vp, u64p, lng, u64p, u64p, u64p, u64p, i32, vp]

@@ -225,7 +225,7 @@ class HEVM:
         ks_special / ks_alpha (extension): grouped-digit hybrid key switching -- the last ks_special primes are special, a digit is
         ks_alpha (default ks_special) data primes.  1 / 1 = the reference's SEAL scheme.  vm_options: further VM options of
         csrc/options.hpp (plan, plan_graph, secret_hw, logn, primes, ...), in force while this VM is created; the previous values are put
-        back afterwards (a VM keeps what it was created with); e.g. {"ks_hoist": 1}: hoisted rotations on SEAL-layout keys (hoist_stats()).  primes (extension, seeded VMs): an explicit chain, e.g. a HEaaN-style
+        back afterwards (a VM keeps what it was created with); e.g. {"ks_hoist": 1}: hoisted rotations on SEAL-layout keys (hoist_stats()), {"ks_hoist": 1, "ks_lazy_sum": 2}: sums of rotations with one mod-down each (lazy_groups()).  primes (extension, seeded VMs): an explicit chain, e.g. a HEaaN-style
         mixed one (60-bit base and special primes around 51-bit rescale primes); a chain with primes narrower than 60 bits -- given here or
         through vm_options["prime_bits"] -- runs on the generic-width build of the same sources (libSEAL_HEVM_gw.so)."""
         reinit_lw()
@@ -377,7 +377,8 @@ class HEVM:
         return hevm_ctxt.from_address(self.lw.getCtxt(self.vm, reg))
 
     def lazy_groups(self):
-        """option hyb_lazy_sum: the plan's lazy sums as lists of rotate-instruction indices (hevm_plan_lazy_groups); [] before the first run"""
+        """options hyb_lazy_sum (grouped digits) / ks_lazy_sum (SEAL-layout keys, with ks_hoist): the plan's lazy sums as lists of
+        rotate-instruction indices (hevm_plan_lazy_groups); [] before the first run and under plan = 0"""
         n = self.lw.hevm_plan_lazy_groups(self.vm, None, 0)
         if n <= 0:
             return []

@@ -107,6 +107,17 @@ void dc_ct_rotate_hop(dc_context *ctx, uint64_t *dst, long dst_stride, const uin
  * The item table is copied synchronously: the call waits for earlier work on `stream`. */
 void dc_ct_rotate_hoisted(dc_context *ctx, uint64_t *const *dsts, long dst_stride, const uint64_t *src, long src_stride,
                           const uint32_t *galois_elts, const uint64_t *const *galois_keys, int count, int ell, void *stream);
+/* EXTENSION (not SEAL's rounding): dst = sum_k [plains[k] .] galois_k(srcs[k]) with ONE division by P -- the members' inner products (and
+ * their base terms) are added in the raised basis, a member with a plaintext multiplied by it there, and the sum is brought down once: per
+ * member oracle orc_rotate_acc_hybrid at one special prime / one prime per digit, Oracle.lazy_mul_plain / lazy_add, then one
+ * orc_moddown_hybrid, limb for limb.  srcs / elts / keys / plains / plains_sp: host arrays of length count.  plains[k]: the plaintext's limbs
+ * over the data primes [>= ell][N], plains_sp[k]: the same encoded polynomial's limb at the special prime [N], both NTT form (both or neither);
+ * either array may be NULL altogether and single entries may be NULL: a bare term.  Equal srcs pointers share one decomposition; dst may be one
+ * of the sources.  SEAL-layout contexts only (a grouped-digit context aborts with a message).  Scratch is kept in the context, sized on
+ * first use.  The item table is copied synchronously: the call waits for earlier work on `stream`. */
+void dc_ct_rotate_sum_hoisted(dc_context *ctx, uint64_t *dst, long dst_stride, const uint64_t *const *srcs, long src_stride,
+                              const uint32_t *galois_elts, const uint64_t *const *galois_keys, const uint64_t *const *plains,
+                              const uint64_t *const *plains_sp, int count, int ell, void *stream);
 /* Evaluator::rescale_to_next: level ell -> ell-1   SEAL_HEVM.cpp:283 */
 void dc_ct_rescale(dc_context *ctx, uint64_t *dst, long dst_stride, const uint64_t *src, long src_stride, int ell,
                    void *stream);

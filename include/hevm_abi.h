@@ -118,8 +118,9 @@ uint64_t hevm_key_digest(void *vm);
 void hevm_keys_replaced(void *vm);
 /* device pointer + level + scale of plaintext register i after preprocess() */
 const uint64_t *hevm_plain(void *vm, int64_t i, int32_t *level, double *scale);
-/* option "hyb_double_hoist": device pointer to plaintext register i's limbs over the chain's special primes [ks_special][N] (NTT form) once
- * the plan has encoded them -- the registers that multiply a rotation inside a lazy sum -- else NULL.  Test infrastructure, like hevm_plain. */
+/* options "hyb_double_hoist" / "ks_lazy_sum" = 2: device pointer to plaintext register i's limbs over the chain's special primes
+ * [ks_special][N] (NTT form; [1][N] on SEAL-layout keys) once the plan has encoded them -- the registers that multiply a rotation inside a
+ * lazy sum -- else NULL.  Test infrastructure, like hevm_plain. */
 const uint64_t *hevm_plain_special(void *vm, int64_t i);
 /* load a program from memory images of the .cst / .hevm files */
 void hevm_load_mem(void *vm, const void *cst, uint64_t cst_len, const void *hevm, uint64_t hevm_len);
@@ -130,8 +131,9 @@ void hevm_last_run_stats(void *vm, int64_t *op_counts /*[11]*/, int64_t *keyswit
  * them.  With the option on, the hops of a plan step that read one source ciphertext share one decomposition; with it off, or under option
  * "plan" = 0, every hop computes its own and the two numbers are equal. */
 void hevm_last_run_hoist_stats(void *vm, int64_t *hops, int64_t *decompositions);
-/* option "hyb_lazy_sum" (grouped-digit mode, off by default): the rotate instructions the last run()'s plan executed as lazy sums -- the
- * accumulators of a group's key switches added in the raised basis, ONE division by P per group.  out = [n_0, op ...,
+/* options "hyb_lazy_sum" (grouped-digit mode) / "ks_lazy_sum" (SEAL-layout keys, with "ks_hoist"; both off by default): the rotate instructions
+ * the last run()'s plan executed as lazy sums -- the accumulators of a group's key switches added in the raised basis, ONE division by P per
+ * group.  The form is the same in both modes.  out = [n_0, op ...,
  * n_1, op ...]: per group its size and its rotations' instruction indices.  Returns the length of that list (written if cap suffices), 0 without
  * groups, -1 before the first run() and under option "plan" = 0 (the loop executes every rotate on its own).  Test infrastructure: oracle/oracle.py OracleVM.set_lazy_groups replays exactly these groups. */
 int64_t hevm_plan_lazy_groups(void *vm, int32_t *out, int64_t cap);
