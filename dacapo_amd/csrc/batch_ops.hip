@@ -4,19 +4,12 @@
 // Evaluator::switch_key_inplace / rescale_to_next / multiply [SEAL-upstream], reached from SEAL_HEVM.cpp:273,283,315-316.
 #include <stdlib.h>
 
+#include "galois.hpp"
 #include "plan.hpp"
 
 namespace dacapo {
 
-typedef u64 u64x2 __attribute__((ext_vector_type(2)));
 constexpr int kBT = 256;
-
-__device__ __forceinline__ u32 galois_src(u32 k, u32 elt, int logN)
-{ // GaloisTool::apply_galois_ntt index map (see poly_kernels.hip)
-    const u32 r = (__brev(k) >> (32 - logN)) * 2u + 1u;
-    const u32 idx = ((elt * r) >> 1) & ((1u << logN) - 1u);
-    return __brev(idx) >> (32 - logN);
-}
 
 // ckks_multiply prologue: dst.c0 = a0 b0, dst.c1 = a0 b1 + a1 b0, target[b] = a1 b1.  grid = (N/512, l, B)
 __global__ __launch_bounds__(kBT) void b_tensor_kernel(const MulItem *__restrict__ items, u64 *__restrict__ target, int ell,
@@ -68,7 +61,7 @@ __global__ __launch_bounds__(kBT) void b_ks_mac_kernel(u64 *__restrict__ acc, co
     for (int j = 0; j < ell; j++) {
         u64x2 x;
         if (j == m && MODE == 0) { // an aligned pair of outputs reads an aligned pair of inputs, possibly swapped
-            const u32 g = galois_src((u32)k, items[b].elt, logN);
+            const u32 g = galois_idx((u32)k, items[b].elt, logN);
             const u64x2 v = *reinterpret_cast<const u64x2 *>(items[b].src.limb(1, j, N) + (g & ~1u));
             x = (g & 1u) ? u64x2{ v.y, v.x } : v;
         } else {

@@ -30,6 +30,42 @@ void *item_slot(dc_context *ctx, const void *host_item, size_t bytes, hipStream_
 }
 BatchWs batch_ws(const Workspace &w) { return BatchWs{ w.ct_tmp, w.ks_digits, w.ks_ext, w.ks_acc, w.ks_tmp }; }
 bool overlaps(const uint64_t *a, const uint64_t *b) { return a == b; }
+
+// What the two hoisted entry points share.  A context with grouped digits is refused (`grouped`: why, in the entry point's words), count and level
+// are checked, build(h) fills the host item table and returns how many decompositions need scratch in the handle; then the handle's buffers --
+// the item table, `pairs` accumulator pairs with their mod-down terms, that scratch -- are grown on demand (growing waits for the device:
+// hipFree) and the table is uploaded.  Returns the device table.
+template <class Build>
+const KsItem *hoist_items(dc_context *ctx, const char *who, const char *grouped, const char *what, int count, int ell, size_t pairs,
+                                 hipStream_t s, Build build)
+{
+    Context &c = *ctx->c;
+    if (c.hybrid()) {
+        fprintf(stderr, "[dacapo_amd] %s: this context switches keys with grouped digits%s; the call is for SEAL-layout keys\n", who, grouped);
+        abort();
+    }
+    if (count < 1 || count > 65535 || ell < 1 || ell > c.max_level()) {
+        fprintf(stderr, "[dacapo_amd] %s: %d %s at level %d (1..65535 %s, level 1..%d)\n", who, count, what, ell, what, c.max_level());
+        abort();
+    }
+    auto grow = [](auto *&p, size_t &cap, size_t need) {
+        if (need <= cap) return;
+        if (p) DC_HIP_CHECK(hipFree(p));
+        p = nullptr;
+        DC_HIP_CHECK(hipMalloc(&p, need));
+        cap = need;
+    };
+    std::vector<KsItem> h;
+    const size_t U = build(h), N = c.N;
+    grow(ctx->hoist_items, ctx->hoist_item_cap, h.size() * sizeof(KsItem));
+    grow(ctx->hoist_acc, ctx->hoist_acc_cap, pairs * 2 * ((size_t)ell + 1) * N * sizeof(u64));
+    grow(ctx->hoist_tmp, ctx->hoist_tmp_cap, pairs * 2 * (size_t)ell * N * sizeof(u64));
+    grow(ctx->hoist_digits, ctx->hoist_digits_cap, U * (size_t)ell * N * sizeof(u64));
+    grow(ctx->hoist_ext, ctx->hoist_ext_cap, U * (size_t)ell * ell * N * sizeof(u64));
+    DC_HIP_CHECK(hipMemcpyAsync(ctx->hoist_items, h.data(), h.size() * sizeof(KsItem), hipMemcpyHostToDevice, s));
+    DC_HIP_CHECK(hipStreamSynchronize(s)); // (the host table goes out of scope)
+    return static_cast<const KsItem *>(ctx->hoist_items);
+}
 } // namespace
 
 extern "C" {
@@ -210,94 +246,53 @@ void dc_ct_rotate_hop(dc_context *ctx, uint64_t *dst, long dst_stride, const uin
     b_rotate_hops(*ctx->c, batch_ws(ctx->c->ws0), d, 1, ell, S(stream));
 }
 // `count` hops of one source on one decomposition (hoist_ks.hip).  The decomposition lives in the context's default workspace (one source);
-// what grows with the hop count -- the item table, the accumulators, the mod-down terms -- is kept in the handle and grown on demand
-// (growing waits for the device: hipFree).
+// what grows with the hop count -- the item table, the accumulators, the mod-down terms -- is kept in the handle.
 void dc_ct_rotate_hoisted(dc_context *ctx, uint64_t *const *dsts, long dst_stride, const uint64_t *src, long src_stride,
                           const uint32_t *galois_elts, const uint64_t *const *galois_keys, int count, int ell, void *stream)
 {
+    const size_t B = (size_t)count;
+    const KsItem *d = hoist_items(ctx, "dc_ct_rotate_hoisted", ", where dc_ct_rotate_hop already takes the digits before the automorphism", "hops",
+                                  count, ell, B, S(stream), [&](std::vector<KsItem> &h) {
+                                      for (size_t b = 0; b < B; b++)
+                                          h.push_back(KsItem{ V(src, src_stride), V(dsts[b], dst_stride), galois_keys[b], galois_elts[b], 0 });
+                                      h.push_back(KsItem{ V(src, src_stride), V(src, src_stride), nullptr, 1u, 0 }); // the source, for the decomposition's loader
+                                      return (size_t)0;
+                                  });
     Context &c = *ctx->c;
-    if (c.hybrid()) {
-        fprintf(stderr, "[dacapo_amd] dc_ct_rotate_hoisted: this context switches keys with grouped digits, where dc_ct_rotate_hop already takes "
-                        "the digits before the automorphism; the call is for SEAL-layout keys\n");
-        abort();
-    }
-    if (count < 1 || count > 65535 || ell < 1 || ell > c.max_level()) {
-        fprintf(stderr, "[dacapo_amd] dc_ct_rotate_hoisted: %d hops at level %d (1..65535 hops, level 1..%d)\n", count, ell, c.max_level());
-        abort();
-    }
-    auto grow = [](auto *&p, size_t &cap, size_t need) {
-        if (need <= cap) return;
-        if (p) DC_HIP_CHECK(hipFree(p));
-        p = nullptr;
-        DC_HIP_CHECK(hipMalloc(&p, need));
-        cap = need;
-    };
-    const size_t B = (size_t)count, N = c.N;
-    grow(ctx->hoist_items, ctx->hoist_item_cap, (B + 1) * sizeof(KsItem));
-    grow(ctx->hoist_acc, ctx->hoist_acc_cap, B * 2 * ((size_t)ell + 1) * N * sizeof(u64));
-    grow(ctx->hoist_tmp, ctx->hoist_tmp_cap, B * 2 * (size_t)ell * N * sizeof(u64));
-    std::vector<KsItem> h(B + 1);
-    for (size_t b = 0; b < B; b++) h[b] = KsItem{ V(src, src_stride), V(dsts[b], dst_stride), galois_keys[b], galois_elts[b], 0 };
-    h[B] = KsItem{ V(src, src_stride), V(src, src_stride), nullptr, 1u, 0 }; // the source, for the decomposition's loader
-    DC_HIP_CHECK(hipMemcpyAsync(ctx->hoist_items, h.data(), h.size() * sizeof(KsItem), hipMemcpyHostToDevice, S(stream)));
-    DC_HIP_CHECK(hipStreamSynchronize(S(stream))); // (the host table goes out of scope)
-    const KsItem *d = static_cast<const KsItem *>(ctx->hoist_items);
     const BatchWs w{ c.ws0.ct_tmp, c.ws0.ks_digits, c.ws0.ks_ext, ctx->hoist_acc, ctx->hoist_tmp };
     hoist_rotate_hops(c, w, d, d + B, count, 1, ell, S(stream));
 }
 // dst = sum_k [plains[k] .] galois_k(srcs[k]) with ONE division by P (hoist_ks.hip hoist_rotate_sum): equal source pointers share a
 // decomposition, which is why the decompositions need scratch of their own here ([distinct sources][l][N] digits and [..][l*l][N] lifted limbs,
-// kept in the handle like the rest and grown on demand).
+// kept in the handle like the rest).
 void dc_ct_rotate_sum_hoisted(dc_context *ctx, uint64_t *dst, long dst_stride, const uint64_t *const *srcs, long src_stride,
                               const uint32_t *galois_elts, const uint64_t *const *galois_keys, const uint64_t *const *plains,
                               const uint64_t *const *plains_sp, int count, int ell, void *stream)
 {
-    Context &c = *ctx->c;
-    if (c.hybrid()) {
-        fprintf(stderr, "[dacapo_amd] dc_ct_rotate_sum_hoisted: this context switches keys with grouped digits (ks_special > 1); the call is for "
-                        "SEAL-layout keys\n");
-        abort();
-    }
-    if (count < 1 || count > 65535 || ell < 1 || ell > c.max_level()) {
-        fprintf(stderr, "[dacapo_amd] dc_ct_rotate_sum_hoisted: %d members at level %d (1..65535 members, level 1..%d)\n", count, ell, c.max_level());
-        abort();
-    }
-    auto grow = [](auto *&p, size_t &cap, size_t need) {
-        if (need <= cap) return;
-        if (p) DC_HIP_CHECK(hipFree(p));
-        p = nullptr;
-        DC_HIP_CHECK(hipMalloc(&p, need));
-        cap = need;
-    };
-    const size_t B = (size_t)count, N = c.N;
-    // members source-major (stable: equal sources keep the caller's order); then the group; then the distinct sources
-    std::vector<size_t> order(B);
-    for (size_t b = 0; b < B; b++) order[b] = b;
-    std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return srcs[x] < srcs[y]; });
-    std::vector<KsItem> h, sources;
-    for (size_t b : order) {
-        const u64 *pl = plains ? plains[b] : nullptr, *psp = plains_sp ? plains_sp[b] : nullptr;
-        if ((pl == nullptr) != (psp == nullptr)) {
-            fprintf(stderr, "[dacapo_amd] dc_ct_rotate_sum_hoisted: member %zu has one of plains / plains_sp only\n", b);
-            abort();
+    const size_t B = (size_t)count;
+    size_t U = 0;
+    const KsItem *d = hoist_items(ctx, "dc_ct_rotate_sum_hoisted", " (ks_special > 1)", "members", count, ell, 1, S(stream), [&](std::vector<KsItem> &h) {
+        // members source-major (stable: equal sources keep the caller's order); then the group; then the distinct sources
+        std::vector<size_t> order(B);
+        for (size_t b = 0; b < B; b++) order[b] = b;
+        std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return srcs[x] < srcs[y]; });
+        std::vector<KsItem> sources;
+        for (size_t b : order) {
+            const u64 *pl = plains ? plains[b] : nullptr, *psp = plains_sp ? plains_sp[b] : nullptr;
+            if ((pl == nullptr) != (psp == nullptr)) {
+                fprintf(stderr, "[dacapo_amd] dc_ct_rotate_sum_hoisted: member %zu has one of plains / plains_sp only\n", b);
+                abort();
+            }
+            const CtView sv = V(srcs[b], src_stride);
+            if (sources.empty() || sources.back().src.p != sv.p) sources.push_back(KsItem{ sv, sv, nullptr, 1u, 0 });
+            h.push_back(KsItem{ sv, V(dst, dst_stride), galois_keys[b], galois_elts[b], (u32)(sources.size() - 1), pl, psp });
         }
-        const CtView sv = V(srcs[b], src_stride);
-        if (sources.empty() || sources.back().src.p != sv.p) sources.push_back(KsItem{ sv, sv, nullptr, 1u, 0 });
-        h.push_back(KsItem{ sv, V(dst, dst_stride), galois_keys[b], galois_elts[b], (u32)(sources.size() - 1), pl, psp });
-    }
-    const size_t U = sources.size();
-    h.push_back(KsItem{ V(dst, dst_stride), V(dst, dst_stride), nullptr, 0u, (u32)B });
-    h.insert(h.end(), sources.begin(), sources.end());
-    grow(ctx->hoist_items, ctx->hoist_item_cap, h.size() * sizeof(KsItem));
-    grow(ctx->hoist_acc, ctx->hoist_acc_cap, 2 * ((size_t)ell + 1) * N * sizeof(u64));
-    grow(ctx->hoist_tmp, ctx->hoist_tmp_cap, 2 * (size_t)ell * N * sizeof(u64));
-    grow(ctx->hoist_digits, ctx->hoist_digits_cap, U * (size_t)ell * N * sizeof(u64));
-    grow(ctx->hoist_ext, ctx->hoist_ext_cap, U * (size_t)ell * ell * N * sizeof(u64));
-    DC_HIP_CHECK(hipMemcpyAsync(ctx->hoist_items, h.data(), h.size() * sizeof(KsItem), hipMemcpyHostToDevice, S(stream)));
-    DC_HIP_CHECK(hipStreamSynchronize(S(stream))); // (the host table goes out of scope)
-    const KsItem *d = static_cast<const KsItem *>(ctx->hoist_items);
+        h.push_back(KsItem{ V(dst, dst_stride), V(dst, dst_stride), nullptr, 0u, (u32)B });
+        h.insert(h.end(), sources.begin(), sources.end());
+        return U = sources.size();
+    });
     const BatchWs w{ nullptr, ctx->hoist_digits, ctx->hoist_ext, ctx->hoist_acc, ctx->hoist_tmp };
-    hoist_rotate_sum(c, w, d, d + B + 1, count, (int)U, d + B, 1, ell, S(stream));
+    hoist_rotate_sum(*ctx->c, w, d, d + B + 1, count, (int)U, d + B, 1, ell, S(stream));
 }
 void dc_ct_rescale(dc_context *ctx, uint64_t *dst, long dst_stride, const uint64_t *src, long src_stride, int ell, void *stream)
 {

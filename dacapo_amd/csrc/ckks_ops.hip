@@ -10,7 +10,6 @@
 
 namespace dacapo {
 
-typedef u64 u64x2 __attribute__((ext_vector_type(2)));
 constexpr int kOpThreads = 256;
 
 // step 2 of switch_key_inplace: digit j (coefficient domain, canonical mod q_j) reduced into every other

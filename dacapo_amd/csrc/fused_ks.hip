@@ -15,34 +15,9 @@
 // 7 launches instead of 13; rescale is L5'-L7' = 3 instead of 7.  (Round 3: throughput-bound launches take MERGE instantiations of L2 / L6
 // / L3-L5 that do not repeat work per target modulus / per accumulator; see the kernels.)  L2/L6 recompute the inverse COLS phase once per
 // target modulus (it is 1/(l+1) of that kernel's work) to keep every workgroup at two phases.
-#include "ntt_tile.hpp"
-#include "plan.hpp"
-#include "tile_dispatch.hpp"
+#include "ks_mac.hpp"
 
 namespace dacapo {
-
-__device__ __forceinline__ u32 galois_idx(u32 k, u32 elt, int logN)
-{
-    const u32 r = (__brev(k) >> (32 - logN)) * 2u + 1u;
-    const u32 idx = ((elt * r) >> 1) & ((1u << logN) - 1u);
-    return __brev(idx) >> (32 - logN);
-}
-
-// E consecutive coefficients k0 .. k0 + E - 1 (k0 a multiple of E >= 2) of galois(p): the index map sends an aligned pair of outputs to an
-// aligned pair of inputs, possibly swapped (brev(k + 1) = brev(k) + N/2, elt odd: the source index moves by N/2 before its own bit
-// reversal, i.e. its lowest bit flips), so a pair is ONE 16-byte load
-template <int E>
-__device__ __forceinline__ void galois_gather(u64 (&x)[E], const u64 *__restrict__ p, u32 k0, u32 elt, int logN)
-{
-    static_assert(E >= 2 && E % 2 == 0, "pairs");
-    typedef u64 u64x2 __attribute__((ext_vector_type(2)));
-#pragma unroll
-    for (int e = 0; e < E; e += 2) {
-        const u32 gi = galois_idx(k0 + (u32)e, elt, logN);
-        const u64x2 v = *reinterpret_cast<const u64x2 *>(p + (gi & ~1u));
-        x[e] = (gi & 1u) ? v.y : v.x, x[e + 1] = (gi & 1u) ? v.x : v.y;
-    }
-}
 
 // ---- operand sources of the first inverse phase ----------------------------------------------------------------------
 struct SrcStrided { // limb z at base + z*stride, modulo prime prime_base + z % period
@@ -358,7 +333,6 @@ __global__ __launch_bounds__(kTileThreads) void f_frows_final_kernel(const u64 *
         auto nost = [](int, u64) {};
         ntt_tile_x<K, LOGE, false, false, true, false, true>(v, M, tw + ((size_t)i << logN), logN, blockIdx.x, [=](int gi) { return in[gi]; }, nost, lds);
         const int g0 = tile_gidx<K, LOGE, false>(num_passes<LOGE>(K) - 1, logN, blockIdx.x, 0);
-        typedef u64 u64x2 __attribute__((ext_vector_type(2)));
 #pragma unroll
         for (int j = 0; j < E; j += 2) {
             const u64x2 a = *reinterpret_cast<const u64x2 *>(x + g0 + j);
@@ -586,15 +560,9 @@ __global__ __launch_bounds__(kTileThreads) void f_ks_frows_mac_kernel(const u64 
 {
     __shared__ __attribute__((aligned(16))) u64 lds[TileGeo<LOGE>::LDS_ELEMS];
     constexpr int E = 1 << LOGE, NP = num_passes<LOGE>(K);
-    // items_fast: grid = (tiles, B, rows) instead of (tiles, rows, B).  The workgroups (tile, row) of consecutive items are then 2^k tiles apart
-    // in launch order -- the same XCD (workgroup w runs on XCD w mod 8), dispatched together -- and items that use the same key (the plan
-    // sorts a rotation step's items by Galois element; a relinearisation step has one key) read each key tile out of that XCD's L2 after
-    // the first of them fetched it.  SEAL's default key set has 28 elements, so a 64-item step of a convolution names each key several times:
-    // with the rows slower than the items, two readers of a key tile were a whole item (~150 MB of traffic at 13 primes) apart.
+    // ks_row's decode (ks_mac.hpp: the items-fast grid order, MERGE and psel are described there), written out: through the function the compiler
+    // settles the comparison of y with l before it has seen this kernel's own tests of m, and every instantiation's code changes
     const int y = items_fast ? blockIdx.z : blockIdx.y, b = items_fast ? blockIdx.y : blockIdx.z, sp = Kp - 1;
-    // psel < 0: both accumulators.  MERGE (grid.y = l + 1, throughput-bound launches): ONE workgroup row does the special prime for both
-    // accumulators -- the l transforms of the lifted digits once instead of twice, then the two inverse ROWS phases one after the other
-    // (its own instantiation: both accumulators live through the epilogue cost 16-20 VGPRs, a wave per SIMD)
     const int m = y < ell ? y : ell, psel = (MERGE && y == ell) ? -1 : y - ell;
     const int pm = m == ell ? sp : m;
     const size_t N = (size_t)1 << logN;
@@ -714,7 +682,7 @@ __global__ __launch_bounds__(kTileThreads) void f_ks_frows_mac_kernel(const u64 
         }
         if ((j & 15) == 15 && j + 1 < ell) { // a 128-bit accumulator holds 16 products of canonical residues (Acc128): fold it into a word
 #pragma unroll
-            for (int e = 0; e < E; e++) {
+            for (int e = 0; e < E; e++) { // (ks_fold, ks_mac.hpp, written out: through the function the generic-width build's code changes)
                 const u64 f0 = a0[e].reduce(M), f1 = a1[e].reduce(M);
                 a0[e].clear(), a1[e].clear();
                 a0[e].lo = f0, a1[e].lo = f1; // the folded sum counts as one more (tiny) term: 16 products + 2^60 < 2^124
@@ -866,39 +834,22 @@ void f_frows_boot_final(const Context &c, const u64 *ptx, const BootItem *items,
                                                   c.d_mods, c.d_tw, c.logN));
 }
 
-static long ks_merge_special_min_wgs()
-{ // option ks_merge_special_min_wgs: launches of at least this many workgroups (more than the chip holds at once: throughput, not one
-  // workgroup's latency, is what counts) let one row of workgroups serve both special-prime accumulators; a huge value = never
-    return (long)option(OPT_KS_MERGE_SPECIAL_MIN_WGS);
-}
-
+// (launch shape: ks_mac.hpp ks_mac_shape)
 void f_ks_frows_mac(const Context &c, int mode, const u64 *ext, const u64 *target, const KsItem *items, const u64 *shared_key, u64 *acc,
                     int B, int ell, hipStream_t s, bool fold_base)
 {
     const u64 *pmod = (fold_base && mode == 0) ? c.d_pmod : nullptr;
-#define DC_FMAC(LEV, MD)                                                                                                                  \
-    {                                                                                                                                     \
-        constexpr int LE = LEV;                                                                                                           \
-        const long wgs = (long)(c.N >> TileGeo<LE>::LOG) * (ell + 2) * B;                                                                \
-        const int merge = wgs >= ks_merge_special_min_wgs() ? 1 : 0;                                                                      \
-        const int items_fast = (B > 1 && B <= 65535 && option(OPT_KS_ITEMS_FAST)) ? 1 : 0;                                               \
-        const dim3 grid((unsigned)(c.N >> TileGeo<LE>::LOG), (unsigned)(items_fast ? B : ell + 2 - merge), (unsigned)(items_fast ? ell + 2 - merge : B)); \
-        if (merge) {                                                                                                                      \
-            DC_K_SWITCH(c.k2, DC_LAUNCH((f_ks_frows_mac_kernel<KK, LE, MD, true>), grid, dim3(kTileThreads), 0, s, ext, target, items,   \
-                                                 shared_key, acc, ell, c.K, c.d_mods, c.d_tw, c.d_itw, c.logN, pmod, items_fast));       \
-        } else {                                                                                                                          \
-            DC_K_SWITCH(c.k2, DC_LAUNCH((f_ks_frows_mac_kernel<KK, LE, MD, false>), grid, dim3(kTileThreads), 0, s, ext, target, items,  \
-                                                 shared_key, acc, ell, c.K, c.d_mods, c.d_tw, c.d_itw, c.logN, pmod, items_fast));       \
-        }                                                                                                                                 \
-    }
-    // (the radix-8 geometry was measured for this kernel too: 8 coefficients x two 128-bit accumulators per thread cost more in
-    // occupancy than the saved LDS exchange returns -- config 3: 520 us against 455 us; profiles/r02_experiments.txt)
-    if (use_tiny_tiles(c.N, (long)(ell + 2) * B)) {
-        if (mode == 0) DC_FMAC(1, 0) else DC_FMAC(1, 1)
-    } else {
-        if (mode == 0) DC_FMAC(2, 0) else DC_FMAC(2, 1)
-    }
-#undef DC_FMAC
+    const KsMacShape sh = ks_mac_shape(c, ell, B);
+    ks_mac_dispatch(c.k2, sh, [&](auto k, auto le, auto merge) {
+        constexpr int KK = decltype(k)::value, LE = decltype(le)::value;
+        constexpr bool MG = decltype(merge)::value;
+        if (mode == 0)
+            DC_LAUNCH((f_ks_frows_mac_kernel<KK, LE, 0, MG>), sh.grid, dim3(kTileThreads), 0, s, ext, target, items, shared_key, acc, ell, c.K,
+                      c.d_mods, c.d_tw, c.d_itw, c.logN, pmod, sh.items_fast);
+        else
+            DC_LAUNCH((f_ks_frows_mac_kernel<KK, LE, 1, MG>), sh.grid, dim3(kTileThreads), 0, s, ext, target, items, shared_key, acc, ell, c.K,
+                      c.d_mods, c.d_tw, c.d_itw, c.logN, pmod, sh.items_fast);
+    });
 }
 
 static long ks_merge_lift_min_wgs()

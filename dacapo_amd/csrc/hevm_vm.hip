@@ -21,7 +21,6 @@
 
 namespace dacapo {
 
-typedef u64 u64x2 __attribute__((ext_vector_type(2)));
 constexpr int kVmThreads = 256;
 
 // ---------------------------------------------------------------------------------------------------------

@@ -21,24 +21,16 @@
 // ONCE per sum.  The decomposition stage is the same; f_ks_gsum takes the place of f_ks_gmac -- a workgroup walks the members of its group and
 // leaves ONE accumulator pair per group -- and the tail runs over 2G polynomials instead of 2B.  The definition is the oracle's
 // orc_rotate_acc_hybrid per member, Oracle.lazy_mul_plain / lazy_add, and one orc_moddown_hybrid per group, limb for limb.
-#include "ntt_tile.hpp"
-#include "plan.hpp"
-#include "tile_dispatch.hpp"
+//
+// Shared with f_ks_frows_mac_kernel (ks_mac.hpp, galois.hpp): the row decode ks_row, the fold ks_fold, the Galois pair indices and gather, and the
+// host's launch-shape rule ks_mac_shape / ks_mac_dispatch.  The digit step and the finish are written out in both kernels below, on purpose:
+// as shared functions they cost registers (ks_mac.hpp, profiles/ks_mac_regs.txt).
+#include "ks_mac.hpp"
 
 namespace dacapo {
 
-typedef u64 u64x2 __attribute__((ext_vector_type(2)));
-
-// GaloisTool::apply_galois_ntt index map (fused_ks.hip galois_idx)
-__device__ __forceinline__ u32 hoist_galois_idx(u32 k, u32 elt, int logN)
-{
-    const u32 r = (__brev(k) >> (32 - logN)) * 2u + 1u;
-    const u32 idx = ((elt * r) >> 1) & ((1u << logN) - 1u);
-    return __brev(idx) >> (32 - logN);
-}
-
-// grid = (tiles, l + 2 - MERGE, B) or, items_fast, (tiles, B, l + 2 - MERGE): the rows and item order of f_ks_frows_mac_kernel.  Workgroup
-// (tile, y, b) owns the tile's coefficients of output modulus slot m (y < l: prime y, both accumulators; above: the special prime) of hop b:
+// grid = (tiles, l + 2 - MERGE, B) or, items_fast, (tiles, B, l + 2 - MERGE): the rows and item order of f_ks_frows_mac_kernel (ks_mac.hpp ks_row).
+// Workgroup (tile, y, b) owns the tile's coefficients of output modulus slot m (y < l: prime y, both accumulators; above: the special prime) of hop b:
 //   acc_c[m] = sum_j L[slot][j][m][pi(.)] key[j][c][m][.]   (+ P c0[m][pi(.)] on acc_0 of a data prime: the base term, as in the fused middle)
 // A thread holds 2^LOGE CONSECUTIVE coefficients (the last-pass layout of a ROWS tile, which the special prime's inverse phase starts from):
 // the map sends an aligned pair of outputs to an aligned pair of inputs, possibly swapped, so every gather is 16-byte loads, and the pair
@@ -51,24 +43,15 @@ __global__ __launch_bounds__(kTileThreads) void f_ks_gmac_kernel(const u64 *__re
 {
     __shared__ __attribute__((aligned(16))) u64 lds[TileGeo<LOGE>::LDS_ELEMS];
     constexpr int E = 1 << LOGE, NP = num_passes<LOGE>(K);
-    static_assert(E >= 2, "pairs");
-    const int y = items_fast ? blockIdx.z : blockIdx.y, b = items_fast ? blockIdx.y : blockIdx.z, sp = Kp - 1;
-    const int m = y < ell ? y : ell, psel = (MERGE && y == ell) ? -1 : y - ell; // psel < 0: both accumulators
-    const int pm = m == ell ? sp : m;
+    const KsRow r = ks_row<MERGE>(blockIdx, ell, Kp, items_fast);
+    const int b = r.b, m = r.m, psel = r.psel, pm = r.pm, sp = Kp - 1;
     const size_t N = (size_t)1 << logN;
     const DModulus M = mods[pm];
     const KsItem it = items[b];
     const int g0 = tile_gidx<K, LOGE, false>(NP - 1, logN, blockIdx.x, 0);
     u32 gi[E / 2];
-#pragma unroll
-    for (int h = 0; h < E / 2; h++) gi[h] = hoist_galois_idx((u32)(g0 + 2 * h), it.elt, logN);
-    auto gather = [&](u64(&x)[E], const u64 *__restrict__ p) {
-#pragma unroll
-        for (int h = 0; h < E / 2; h++) {
-            const u64x2 v = *reinterpret_cast<const u64x2 *>(p + (gi[h] & ~1u));
-            x[2 * h] = (gi[h] & 1u) ? v.y : v.x, x[2 * h + 1] = (gi[h] & 1u) ? v.x : v.y;
-        }
-    };
+    galois_pair_idx<E>(gi, (u32)g0, it.elt, logN);
+    auto gather = [&](u64(&x)[E], const u64 *__restrict__ p) { galois_gather<E>(x, p, gi); };
     Acc128 a0[E], a1[E];
 #pragma unroll
     for (int e = 0; e < E; e++) a0[e].clear(), a1[e].clear();
@@ -99,14 +82,7 @@ __global__ __launch_bounds__(kTileThreads) void f_ks_gmac_kernel(const u64 *__re
                 a1[2 * h].mac(x[2 * h], kv.x), a1[2 * h + 1].mac(x[2 * h + 1], kv.y);
             }
         }
-        if ((j & 15) == 15 && j + 1 < ell) { // a 128-bit accumulator holds 16 products of canonical residues (Acc128): fold it into a word
-#pragma unroll
-            for (int e = 0; e < E; e++) {
-                const u64 f0 = a0[e].reduce(M), f1 = a1[e].reduce(M);
-                a0[e].clear(), a1[e].clear();
-                a0[e].lo = f0, a1[e].lo = f1;
-            }
-        }
+        if ((j & 15) == 15 && j + 1 < ell) ks_fold<E>(a0, a1, M);
     }
     if (m < ell) {
         u64 *ac = acc + (size_t)b * 2 * (ell + 1) * N;
@@ -132,29 +108,14 @@ __global__ __launch_bounds__(kTileThreads) void f_ks_gmac_kernel(const u64 *__re
     }
 }
 
-// geometry and merging as f_ks_frows_mac chooses them (options tiny_tile_wgs, ks_merge_special_min_wgs, ks_items_fast)
+// geometry and merging as f_ks_frows_mac chooses them (ks_mac.hpp ks_mac_shape)
 static void f_ks_gmac(const Context &c, const u64 *L, const KsItem *items, u64 *acc, int B, int ell, hipStream_t s)
 {
-#define DC_GMAC(LEV)                                                                                                                      \
-    {                                                                                                                                     \
-        constexpr int LE = LEV;                                                                                                           \
-        const long wgs = (long)(c.N >> TileGeo<LE>::LOG) * (ell + 2) * B;                                                                \
-        const int merge = wgs >= (long)option(OPT_KS_MERGE_SPECIAL_MIN_WGS) ? 1 : 0;                                                      \
-        const int items_fast = (B > 1 && B <= 65535 && option(OPT_KS_ITEMS_FAST)) ? 1 : 0;                                               \
-        const dim3 grid((unsigned)(c.N >> TileGeo<LE>::LOG), (unsigned)(items_fast ? B : ell + 2 - merge), (unsigned)(items_fast ? ell + 2 - merge : B)); \
-        if (merge) {                                                                                                                      \
-            DC_K_SWITCH(c.k2, DC_LAUNCH((f_ks_gmac_kernel<KK, LE, true>), grid, dim3(kTileThreads), 0, s, L, items, acc, ell, c.K, c.d_mods, \
-                                        c.d_itw, c.logN, c.d_pmod, items_fast));                                                          \
-        } else {                                                                                                                          \
-            DC_K_SWITCH(c.k2, DC_LAUNCH((f_ks_gmac_kernel<KK, LE, false>), grid, dim3(kTileThreads), 0, s, L, items, acc, ell, c.K, c.d_mods, \
-                                        c.d_itw, c.logN, c.d_pmod, items_fast));                                                          \
-        }                                                                                                                                 \
-    }
-    if (use_tiny_tiles(c.N, (long)(ell + 2) * B))
-        DC_GMAC(1)
-    else
-        DC_GMAC(2)
-#undef DC_GMAC
+    const KsMacShape sh = ks_mac_shape(c, ell, B);
+    ks_mac_dispatch(c.k2, sh, [&](auto k, auto le, auto merge) {
+        DC_LAUNCH((f_ks_gmac_kernel<decltype(k)::value, decltype(le)::value, decltype(merge)::value>), sh.grid, dim3(kTileThreads), 0, s, L, items,
+                  acc, ell, c.K, c.d_mods, c.d_itw, c.logN, c.d_pmod, sh.items_fast);
+    });
 }
 
 // The group form of f_ks_gmac_kernel: grid = (tiles, l + 2 - MERGE, G) or, groups_fast, (tiles, G, l + 2 - MERGE).  Workgroup (tile, y, g) owns the
@@ -177,10 +138,8 @@ __global__ __launch_bounds__(kTileThreads) void f_ks_gsum_kernel(const u64 *__re
 {
     __shared__ __attribute__((aligned(16))) u64 lds[TileGeo<LOGE>::LDS_ELEMS];
     constexpr int E = 1 << LOGE, NP = num_passes<LOGE>(K);
-    static_assert(E >= 2, "pairs");
-    const int y = groups_fast ? blockIdx.z : blockIdx.y, g = groups_fast ? blockIdx.y : blockIdx.z, sp = Kp - 1;
-    const int m = y < ell ? y : ell, psel = (MERGE && y == ell) ? -1 : y - ell; // psel < 0: both accumulators
-    const int pm = m == ell ? sp : m;
+    const KsRow r = ks_row<MERGE>(blockIdx, ell, Kp, groups_fast);
+    const int g = r.b, m = r.m, psel = r.psel, pm = r.pm, sp = Kp - 1;
     const size_t N = (size_t)1 << logN;
     const DModulus M = mods[pm];
     const KsItem gr = groups[g];
@@ -188,16 +147,8 @@ __global__ __launch_bounds__(kTileThreads) void f_ks_gsum_kernel(const u64 *__re
     const int cnt = (int)gr.slot;
     const int g0 = tile_gidx<K, LOGE, false>(NP - 1, logN, blockIdx.x, 0);
     const u64 P = m < ell ? pmod[m] : 0;
-    auto fold = [&](Acc128(&x0)[E], Acc128(&x1)[E]) {
-#pragma unroll
-        for (int e = 0; e < E; e++) {
-            const u64 f0 = x0[e].reduce(M), f1 = x1[e].reduce(M);
-            x0[e].clear(), x1[e].clear();
-            x0[e].lo = f0, x1[e].lo = f1;
-        }
-    };
     auto room = [&](Acc128(&x0)[E], Acc128(&x1)[E], int &n) { // one more product per accumulator is about to land
-        if (n == 16) fold(x0, x1), n = 1;
+        if (n == 16) ks_fold<E>(x0, x1, M), n = 1;
         n++;
     };
     Acc128 s0[E], s1[E];
@@ -207,15 +158,8 @@ __global__ __launch_bounds__(kTileThreads) void f_ks_gsum_kernel(const u64 *__re
     for (int k = 0; k < cnt; k++) {
         const KsItem it = mem[k];
         u32 gi[E / 2];
-#pragma unroll
-        for (int h = 0; h < E / 2; h++) gi[h] = hoist_galois_idx((u32)(g0 + 2 * h), it.elt, logN);
-        auto gather = [&](u64(&x)[E], const u64 *__restrict__ p) {
-#pragma unroll
-            for (int h = 0; h < E / 2; h++) {
-                const u64x2 v = *reinterpret_cast<const u64x2 *>(p + (gi[h] & ~1u));
-                x[2 * h] = (gi[h] & 1u) ? v.y : v.x, x[2 * h + 1] = (gi[h] & 1u) ? v.x : v.y;
-            }
-        };
+        galois_pair_idx<E>(gi, (u32)g0, it.elt, logN);
+        auto gather = [&](u64(&x)[E], const u64 *__restrict__ p) { galois_gather<E>(x, p, gi); };
         const u64 *Ls = L + (size_t)it.slot * ell * ell * N;
         auto products = [&](Acc128(&x0)[E], Acc128(&x1)[E], int &n) { // the member's base term and inner products into (x0, x1)
             if (m < ell) {
@@ -292,26 +236,11 @@ __global__ __launch_bounds__(kTileThreads) void f_ks_gsum_kernel(const u64 *__re
 // geometry and merging chosen as f_ks_gmac chooses them, with groups in the place of hops
 static void f_ks_gsum(const Context &c, const u64 *L, const KsItem *items, const KsItem *groups, u64 *acc, int G, int ell, hipStream_t s)
 {
-#define DC_GSUM(LEV)                                                                                                                      \
-    {                                                                                                                                     \
-        constexpr int LE = LEV;                                                                                                           \
-        const long wgs = (long)(c.N >> TileGeo<LE>::LOG) * (ell + 2) * G;                                                                \
-        const int merge = wgs >= (long)option(OPT_KS_MERGE_SPECIAL_MIN_WGS) ? 1 : 0;                                                      \
-        const int groups_fast = (G > 1 && G <= 65535 && option(OPT_KS_ITEMS_FAST)) ? 1 : 0;                                              \
-        const dim3 grid((unsigned)(c.N >> TileGeo<LE>::LOG), (unsigned)(groups_fast ? G : ell + 2 - merge), (unsigned)(groups_fast ? ell + 2 - merge : G)); \
-        if (merge) {                                                                                                                      \
-            DC_K_SWITCH(c.k2, DC_LAUNCH((f_ks_gsum_kernel<KK, LE, true>), grid, dim3(kTileThreads), 0, s, L, items, groups, acc, ell, c.K, \
-                                        c.d_mods, c.d_itw, c.logN, c.d_pmod, groups_fast));                                               \
-        } else {                                                                                                                          \
-            DC_K_SWITCH(c.k2, DC_LAUNCH((f_ks_gsum_kernel<KK, LE, false>), grid, dim3(kTileThreads), 0, s, L, items, groups, acc, ell, c.K, \
-                                        c.d_mods, c.d_itw, c.logN, c.d_pmod, groups_fast));                                               \
-        }                                                                                                                                 \
-    }
-    if (use_tiny_tiles(c.N, (long)(ell + 2) * G))
-        DC_GSUM(1)
-    else
-        DC_GSUM(2)
-#undef DC_GSUM
+    const KsMacShape sh = ks_mac_shape(c, ell, G);
+    ks_mac_dispatch(c.k2, sh, [&](auto k, auto le, auto merge) {
+        DC_LAUNCH((f_ks_gsum_kernel<decltype(k)::value, decltype(le)::value, decltype(merge)::value>), sh.grid, dim3(kTileThreads), 0, s, L, items,
+                  groups, acc, ell, c.K, c.d_mods, c.d_itw, c.logN, c.d_pmod, sh.items_fast);
+    });
 }
 
 // B hops over U decompositions.  d_items[b].slot names the hop's source among d_sources[0 .. U) (items with the identity element whose

@@ -25,13 +25,6 @@
 
 namespace dacapo {
 
-__device__ __forceinline__ u32 hf_galois_idx(u32 k, u32 elt, int logN)
-{ // GaloisTool::apply_galois_ntt index map (poly_kernels.hip)
-    const u32 r = (__brev(k) >> (32 - logN)) * 2u + 1u;
-    const u32 idx = ((elt * r) >> 1) & ((1u << logN) - 1u);
-    return __brev(idx) >> (32 - logN);
-}
-
 // sum of up to 8 products y w with y, w < 2^60, kept as three 64-bit columns of 30-bit limb products: y = y0 + y1 2^30, w = w0 + w1 2^30,
 // every product < 2^60, so c0 < 8 2^60, c1 < 16 2^60 <= 2^64 - 16 2^31, c2 < 8 2^60 never overflow and a term is 4 v_mad_u64_u32 with no
 // carry handling (a 128-bit accumulator: 4 mads + 6 adds with carries).  w is wave-uniform in every use (a conversion constant): scalar operands.
@@ -276,7 +269,6 @@ __global__ __launch_bounds__(kTileThreads) void hybf_frows_final_kernel(const u6
     auto nost = [](int, u64) {};
     ntt_tile_x<K, LOGE, false, false, true, false, true>(x, M, tw + ((size_t)i << logN), logN, blockIdx.x, [=](int g) { return in[g]; }, nost, lds);
     const int g0 = tile_gidx<K, LOGE, false>(NP - 1, logN, blockIdx.x, 0); // register j holds coefficient g0 + j
-    typedef u64 u64x2 __attribute__((ext_vector_type(2)));
 #pragma unroll
     for (int j = 0; j < EC; j += 2) {
         const u64x2 a = *reinterpret_cast<const u64x2 *>(ac + g0 + j);
@@ -381,7 +373,6 @@ __global__ __launch_bounds__(256) void hybf_group_sum_kernel(const u64 *__restri
                                                              u64 *__restrict__ gp, const KsItem *__restrict__ items, const KsItem *__restrict__ groups,
                                                              int ell, int ksp, int L, size_t N, const DModulus *__restrict__ mods)
 {
-    typedef u64 u64x2 __attribute__((ext_vector_type(2)));
     const int mi = blockIdx.y, g = blockIdx.z >> 1, c = blockIdx.z & 1;
     const u32 first = groups[g].elt, count = groups[g].slot;
     const bool special = mi >= ell;

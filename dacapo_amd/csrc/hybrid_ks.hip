@@ -19,20 +19,13 @@
 //   NTT       t [B][2][l]
 //   final     dst.c += (acc_c - t_c) P^-1
 // HBM-bound element-wise kernels around the transforms; 16-byte accesses, constants through scalar loads.
+#include "galois.hpp"
 #include "plan.hpp"
 
 namespace dacapo {
 
-typedef u64 u64x2 __attribute__((ext_vector_type(2)));
 constexpr int kHT = 256;
 constexpr int kHybMaxAlpha = 16;
-
-__device__ __forceinline__ u32 hyb_galois_src(u32 k, u32 elt, int logN)
-{ // GaloisTool::apply_galois_ntt index map (poly_kernels.hip)
-    const u32 r = (__brev(k) >> (32 - logN)) * 2u + 1u;
-    const u32 idx = ((elt * r) >> 1) & ((1u << logN) - 1u);
-    return __brev(idx) >> (32 - logN);
-}
 
 struct HybSingle { // one key switch by value (the one-instruction-at-a-time loop, the kernel-level C ABI): out = base + KS(target)
     CtView out;
@@ -48,7 +41,7 @@ __global__ __launch_bounds__(kHT) void hyb_prepare_rot_kernel(const KsItem *__re
     const int i = blockIdx.y, b = blockIdx.z;
     const KsItem it = items ? items[b] : single;
     const size_t k = ((size_t)blockIdx.x * kHT + threadIdx.x) * 2;
-    const u32 g = hyb_galois_src((u32)k, it.elt, logN); // an aligned pair of outputs reads an aligned pair of inputs, possibly swapped
+    const u32 g = galois_idx((u32)k, it.elt, logN); // an aligned pair of outputs reads an aligned pair of inputs, possibly swapped
     const u64x2 v0 = *reinterpret_cast<const u64x2 *>(it.src.limb(0, i, N) + (g & ~1u));
     *reinterpret_cast<u64x2 *>(it.dst.limb(0, i, N) + k) = (g & 1u) ? u64x2{ v0.y, v0.x } : v0;
     const size_t slot = use_slots ? it.slot : (size_t)b;
@@ -149,7 +142,7 @@ __global__ __launch_bounds__(kHT) void hyb_mac_kernel(u64 *__restrict__ accq, u6
     const size_t k = ((size_t)blockIdx.x * kHT + threadIdx.x) * 2;
     const size_t slot = MODE == 0 ? (use_slots ? it.slot : (size_t)b) : (size_t)b;
     u32 gsrc = (u32)k;
-    if (MODE == 0) gsrc = hyb_galois_src((u32)k, it.elt, logN);
+    if (MODE == 0) gsrc = galois_idx((u32)k, it.elt, logN);
     const int G = (ell + alpha - 1) / alpha;
     Acc128 a0[2], a1[2];
 #pragma unroll
@@ -219,7 +212,7 @@ __global__ __launch_bounds__(kHT) void hyb_mac_group_kernel(u64 *__restrict__ ac
     for (u32 t = 0; t < count; t++) {
         const KsItem it = items[first + t];
         const size_t slot = use_slots ? it.slot : (size_t)(first + t);
-        const u32 gsrc = hyb_galois_src((u32)k, it.elt, logN);
+        const u32 gsrc = galois_idx((u32)k, it.elt, logN);
         Acc128 a0[2], a1[2];
 #pragma unroll
         for (int e = 0; e < 2; e++) a0[e].clear(), a1[e].clear();

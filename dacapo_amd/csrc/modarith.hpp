@@ -17,6 +17,7 @@
 namespace dacapo {
 
 typedef uint64_t u64;
+typedef u64 u64x2 __attribute__((ext_vector_type(2))); // one 16-byte access
 typedef uint32_t u32;
 
 constexpr int kQBits = 60;   // the reference's chain; the widest supported prime

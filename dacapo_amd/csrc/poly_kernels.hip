@@ -1,11 +1,11 @@
 // Limb-wise kernels of the HEVM path: the single-pass opcodes (negate/addcc/addcp/mulcp, SEAL_HEVM.cpp:275-323),
 // the ckks tensor product (:315), the NTT-domain Galois permutation (:273) and the glue passes of key switching
 // and rescaling.  All are streaming kernels: 16 B per lane, grid = (N/512, limbs, polys).
+#include "galois.hpp"
 #include "kernels.hpp"
 
 namespace dacapo {
 
-typedef u64 u64x2 __attribute__((ext_vector_type(2)));
 constexpr int kEwThreads = 256;
 
 template <int OP>
@@ -102,22 +102,13 @@ void launch_tensor(const Context &c, CtView dst, u64 *c2out, CtView a, CtView b,
     DC_LAUNCH(tensor_kernel, grid, dim3(kEwThreads), 0, s, dst, c2out, a, b, c.N, c.d_mods);
 }
 
-// GaloisTool::apply_galois_ntt: out[k] = in[bitrev(((elt * (2*bitrev(k)+1)) >> 1) mod N)].  An aligned block of
-// 2^b consecutive k reads an aligned block of 2^b consecutive inputs (elt is odd), so the gather stays
-// coalesced at 64-lane granularity; no permutation table is needed (v_bfrev_b32 does the bit reversals).
-__device__ __forceinline__ u32 galois_src_index(u32 k, u32 elt, int logN)
-{
-    const u32 r = (__brev(k) >> (32 - logN)) * 2u + 1u;
-    const u32 idx = ((elt * r) >> 1) & ((1u << logN) - 1u);
-    return __brev(idx) >> (32 - logN);
-}
-
+// GaloisTool::apply_galois_ntt as a kernel of its own (the index map: galois.hpp)
 __global__ __launch_bounds__(kEwThreads) void galois_kernel(CtView dst, CtView src, u32 elt, int logN)
 {
     const size_t N = (size_t)1 << logN;
     const int i = blockIdx.y, p = blockIdx.z;
     const u32 k = blockIdx.x * kEwThreads + threadIdx.x;
-    dst.limb(p, i, N)[k] = src.limb(p, i, N)[galois_src_index(k, elt, logN)];
+    dst.limb(p, i, N)[k] = src.limb(p, i, N)[galois_idx(k, elt, logN)];
 }
 
 void launch_galois(const Context &c, CtView dst, CtView src, u32 galois_elt, int polys, int ell, hipStream_t s)
