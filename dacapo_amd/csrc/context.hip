@@ -85,6 +85,13 @@ Context::Context(int logN_, int K_, int bits, const u64 *primes_or_null, int ksp
         fprintf(stderr, "[dacapo_amd] ring degree 2^%d unsupported (12..17)\n", logN);
         abort();
     }
+    // The samplers address the uniform half of a key by object (key_id * 64 + digit) * 64 + limb (chacha.hpp, hevm_vm.hip): beyond 64 limbs,
+    // or 64 digits per key (SEAL layout: K - 1 digits; grouped digits: at most 16), two draws would share ChaCha20 blocks.
+    if (K > 64) {
+        fprintf(stderr, "[dacapo_amd] a chain of %d primes is unsupported: at most 64 limbs and 64 digits per key (the key generator's randomness "
+                        "is addressed with 6 bits each for the limb and the digit)\n", K);
+        abort();
+    }
     k1 = logN / 2;
     k2 = logN - k1;
     if (primes_or_null)
