@@ -170,6 +170,30 @@ void b_mul_relin(Context &c, const BatchWs &w, const MulItem *d_items, const u64
     b_ks_tail<1>(c, w, digits, nullptr, d_items, relin_key, B, ell, s, h);
 }
 
+bool mul_relin_rescale_fused(const Context &c, int B, int ell)
+{
+    const long tiles = (long)(c.N >> 10) * B * ell * ell; // (b_ks_tail's split: the folded form exists for its latency-shaped sequence)
+    return !c.hybrid() && ell >= 2 && fuse_mac() && tiles < fuse_mac_threshold() && tiles < big_threshold();
+}
+
+void b_mul_relin_rescale(Context &c, const BatchWs &w, const MulRsItem *d_items, const u64 *relin_key, int B, int ell, hipStream_t s, const Handoff &h)
+{
+    if (!mul_relin_rescale_fused(c, B, ell)) {
+        fprintf(stderr, "[dacapo_amd] b_mul_relin_rescale: no folded form for %d items at level %d under this context / these launch options "
+                        "(run b_mul_relin and b_rescale)\n", B, ell);
+        abort();
+    }
+    const u64 *digits = h.in; // a fused producer already ran the inverse ROWS phase of a1*b1
+    if (!digits) {
+        f_irows_tensor_c2_rs(c, d_items, ell, w.digits, B, s);
+        digits = w.digits;
+    }
+    f_ks_icols_lift_fcols(c, digits, w.ext, B, ell, s);
+    f_ks_frows_mac_rs(c, w.ext, d_items, relin_key, w.acc, B, ell, s);
+    f_dr2_icols_lift_fcols(c, w.acc, d_items, w.tmp, B, ell, s);
+    f_frows_fold_final(c, w.tmp, d_items, w.acc, B, ell, s, h);
+}
+
 void b_rescale(Context &c, const BatchWs &w, const RsItem *d_items, int B, int ell, hipStream_t s, const SumSrc *d_srcs, const Handoff &h)
 {
     const int l = ell - 1;
@@ -180,6 +204,17 @@ void b_rescale(Context &c, const BatchWs &w, const RsItem *d_items, int B, int e
         f_irows_rs_last(c, d_items, d_srcs, l, w.digits, B, s);
     f_dr_icols_lift_fcols(c, last, (long)c.N, w.tmp, 2 * B, l, l, s);
     f_frows_final(c, 2, w.tmp, d_items, nullptr, 2 * B, l, l, s, RsItem{}, nullptr, d_srcs, h);
+}
+
+__global__ __launch_bounds__(kBT) void b_fill_const_kernel(u64 *__restrict__ out, const u64 *__restrict__ residues, size_t N)
+{
+    const size_t k = ((size_t)blockIdx.x * kBT + threadIdx.x) * 2;
+    const u64 r = residues[blockIdx.y];
+    *reinterpret_cast<u64x2 *>(out + (size_t)blockIdx.y * N + k) = u64x2{ r, r };
+}
+void fill_const_plain(Context &c, u64 *out, const u64 *d_residues, int ell, hipStream_t s)
+{
+    DC_LAUNCH(b_fill_const_kernel, dim3((unsigned)(c.N / (2 * kBT)), (unsigned)ell), dim3(kBT), 0, s, out, d_residues, c.N);
 }
 
 void rescale_fused(Context &c, const Workspace &w, CtView dst, CtView src, int ell, const u64 *plain, hipStream_t s)

@@ -20,7 +20,8 @@ static inline CtView V(const uint64_t *p, long stride) { return CtView{ const_ca
 namespace {
 constexpr int kItemSlots = 64;
 constexpr size_t kItemBytes = 128;
-static_assert(sizeof(KsItem) <= kItemBytes && sizeof(MulItem) <= kItemBytes && sizeof(RsItem) <= kItemBytes, "item slot too small");
+static_assert(sizeof(KsItem) <= kItemBytes && sizeof(MulItem) <= kItemBytes && sizeof(RsItem) <= kItemBytes && sizeof(MulRsItem) <= kItemBytes, "item slot too small");
+constexpr int kConstSlotWords = 64; // residues of one mul_const table (levels up to 64)
 void *item_slot(dc_context *ctx, const void *host_item, size_t bytes, hipStream_t s)
 {
     if (!ctx->item_ring) DC_HIP_CHECK(hipMalloc(&ctx->item_ring, kItemSlots * kItemBytes));
@@ -116,7 +117,8 @@ void dc_context_destroy(dc_context *ctx)
 {
     if (ctx && ctx->item_ring) (void)hipFree(ctx->item_ring);
     if (ctx)
-        for (void *p : { ctx->hoist_items, (void *)ctx->hoist_acc, (void *)ctx->hoist_tmp, (void *)ctx->hoist_digits, (void *)ctx->hoist_ext })
+        for (void *p : { ctx->hoist_items, (void *)ctx->hoist_acc, (void *)ctx->hoist_tmp, (void *)ctx->hoist_digits, (void *)ctx->hoist_ext, (void *)ctx->fold_consts,
+                         (void *)ctx->fold_tmp })
             if (p) (void)hipFree(p);
     if (ctx && ctx->owned) delete ctx->c;
     delete ctx;
@@ -233,6 +235,61 @@ void dc_ct_mul_relin(dc_context *ctx, uint64_t *dst, long dst_stride, const uint
     const MulItem it{ V(a, a_stride), V(b, b_stride), V(dst, dst_stride) };
     const MulItem *d = static_cast<const MulItem *>(item_slot(ctx, &it, sizeof(it), S(stream)));
     b_mul_relin(*ctx->c, batch_ws(ctx->c->ws0), d, relin_key, 1, ell, S(stream));
+}
+void dc_ct_mul_relin_rescale(dc_context *ctx, uint64_t *dst, long dst_stride, const uint64_t *a, long a_stride, const uint64_t *b,
+                             long b_stride, const uint64_t *relin_key, const uint64_t *add_plain, const uint64_t *mul_const, int ell,
+                             void *stream)
+{
+    Context &c = *ctx->c;
+    hipStream_t s = S(stream);
+    if (c.hybrid()) {
+        fprintf(stderr, "[dacapo_amd] dc_ct_mul_relin_rescale: this context switches keys with grouped digits, whose mod-down is an approximate base "
+                        "conversion; the call is for SEAL-layout keys (use dc_ct_mul_relin and dc_ct_rescale)\n");
+        abort();
+    }
+    if (ell < 2 || ell > c.max_level() || ell > kConstSlotWords) {
+        fprintf(stderr, "[dacapo_amd] dc_ct_mul_relin_rescale: level %d (2..%d)\n", ell, std::min(c.max_level(), kConstSlotWords));
+        abort();
+    }
+    const size_t N = c.N;
+    const u64 *d_consts = nullptr;
+    if (mul_const) { // the residues travel like the item: a ring of device slots written in stream order
+        if (!ctx->fold_consts) DC_HIP_CHECK(hipMalloc(&ctx->fold_consts, (size_t)kItemSlots * kConstSlotWords * sizeof(u64)));
+        u64 *slot = ctx->fold_consts + (size_t)(ctx->item_next % kItemSlots) * kConstSlotWords;
+        DC_HIP_CHECK(hipMemcpyAsync(slot, mul_const, (size_t)ell * sizeof(u64), hipMemcpyHostToDevice, s));
+        d_consts = slot;
+    }
+    const bool fused = mul_relin_rescale_fused(c, 1, ell), alias = overlaps(dst, a) || overlaps(dst, b);
+    if (!fused || alias) {
+        const size_t need = (size_t)3 * ell * N * sizeof(u64);
+        if (need > ctx->fold_tmp_cap) { // (growing waits for the device: hipFree)
+            if (ctx->fold_tmp) DC_HIP_CHECK(hipFree(ctx->fold_tmp));
+            ctx->fold_tmp = nullptr;
+            DC_HIP_CHECK(hipMalloc(&ctx->fold_tmp, need));
+            ctx->fold_tmp_cap = need;
+        }
+    }
+    if (fused) { // the last kernel's epilogue reads a and b where other workgroups write dst: an aliased destination is written through scratch
+        const CtView out = alias ? CtView{ ctx->fold_tmp, (long)(ell - 1) * (long)N } : V(dst, dst_stride);
+        MulRsItem it;
+        it.a = V(a, a_stride), it.b = V(b, b_stride), it.dst = out;
+        it.add = add_plain, it.mul = d_consts, it.mul_stride = 1;
+        const MulRsItem *d = static_cast<const MulRsItem *>(item_slot(ctx, &it, sizeof(it), s));
+        b_mul_relin_rescale(c, batch_ws(c.ws0), d, relin_key, 1, ell, s);
+        if (alias) launch_ew(c, EwOp::Copy, V(dst, dst_stride), out, out, 2, 2, ell - 1, s);
+        return;
+    }
+    // the default sequence (its large-batch or un-fused forms): product at level ell in scratch, then the rescale with its operand expression
+    const CtView prod{ ctx->fold_tmp, (long)ell * (long)N };
+    u64 *mul_plain = nullptr;
+    if (d_consts) {
+        mul_plain = ctx->fold_tmp + (size_t)2 * ell * N;
+        fill_const_plain(c, mul_plain, d_consts, ell, s);
+    }
+    const MulItem mi{ V(a, a_stride), V(b, b_stride), prod };
+    b_mul_relin(c, batch_ws(c.ws0), static_cast<const MulItem *>(item_slot(ctx, &mi, sizeof(mi), s)), relin_key, 1, ell, s);
+    const RsItem ri{ prod, V(dst, dst_stride), 0, 0, add_plain, mul_plain };
+    b_rescale(c, batch_ws(c.ws0), static_cast<const RsItem *>(item_slot(ctx, &ri, sizeof(ri), s)), 1, ell, s);
 }
 void dc_ct_rotate_hop(dc_context *ctx, uint64_t *dst, long dst_stride, const uint64_t *src, long src_stride,
                       uint32_t galois_elt, const uint64_t *galois_key, int ell, void *stream)

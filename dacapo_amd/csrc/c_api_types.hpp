@@ -14,4 +14,7 @@ struct dc_context {
     // dc_ct_rotate_sum_hoisted uses the same three, plus the decompositions of its distinct sources: digits [U][l][N], lifted limbs [U][l*l][N]
     dacapo::u64 *hoist_digits = nullptr, *hoist_ext = nullptr;
     size_t hoist_digits_cap = 0, hoist_ext_cap = 0;
+    // dc_ct_mul_relin_rescale: a ring of mul_const residue tables, and [3][l][N] for a destination that aliases an operand / the default sequence
+    dacapo::u64 *fold_consts = nullptr, *fold_tmp = nullptr;
+    size_t fold_tmp_cap = 0;
 };

@@ -164,6 +164,19 @@ struct SrcTensorC2 { // limb z = b*ell + i of a1*b1, the c2 of item b's tensor p
         return mulmod(it.a.limb(1, i, N)[g], it.b.limb(1, i, N)[g], mods[i]);
     }
 };
+struct SrcTensorC2Rs { // the same from a MulRsItem table (a multiply with its rescale folded in)
+    const MulRsItem *items;
+    const DModulus *mods;
+    int ell;
+    __device__ int prime(int z) const { return z % ell; }
+    __device__ u64 load(int z, int g, int logN) const
+    {
+        const size_t N = (size_t)1 << logN;
+        const int i = z % ell;
+        const MulRsItem &it = items[z / ell];
+        return mulmod(it.a.limb(1, i, N)[g], it.b.limb(1, i, N)[g], mods[i]);
+    }
+};
 // L1 / L5 / R1: inverse ROWS phase, out[z] (lazy values) = phase(src limb z)
 template <int K, int LOGE, class Src>
 __global__ __launch_bounds__(kTileThreads) void f_irows_kernel(Src src, u64 *__restrict__ out, long out_stride,
@@ -244,6 +257,76 @@ __global__ __launch_bounds__(kTileThreads) void f_dr_icols_lift_fcols_kernel(con
         for (int r = 0; r < (1 << LOGE); r++) { // ... reduced into q_i, - floor(q_l / 2) mod q_i
             const u64 v = recanon(x[r], Mi) + neg_half;
             y[r] = v >= qi ? v - qi : v;
+        }
+        __syncthreads();
+        ntt_tile_fcols<K, LOGE, false, true, false>(
+            y, Mi, tw + ((size_t)i << logN), tw2 ? tw2 + ((size_t)i << (K + 1)) : nullptr, logN, blockIdx.x, nold, [=](int g, u64 v) { out[g] = v; }, lds);
+    }
+}
+
+// L6 + R2 of a multiply whose rescale is folded in (option ks_fold_rescale): z = bp*cnt + i, cnt = l - 1 kept limbs.  Both dropped limbs of
+// accumulator bp -- the special prime's (slot l of acc) and row l - 1's, which carries P (d + A) (f_ks_frows_mac_kernel, FOLD) -- finish their
+// inverse transforms here, and per coefficient
+//   rho = [X_P + floor(P/2)]_P                     t_i = (rho mod q_i) - (floor(P/2) mod q_i)
+//   c   = s_L P^-1 (row_L - t_L)  mod q_L          u   = [c + floor(q_L/2)]_{q_L},  u_i = (u mod q_i) - (floor(q_L/2) mod q_i)
+//   v_i = (s_i P^-1 t_i + u_i) q_L^-1              (L = l - 1; s the constant polynomial folded into the rescale, 1 when absent)
+// is ONE lifted polynomial per kept limb, whose first NTT phase follows: SEAL's two roundings, limb for limb, from l - 1 forward
+// transforms instead of 2l - 1.  Every step is exact arithmetic mod q_i.  MERGE as in f_dr_icols_lift_fcols_kernel.
+template <int K, int LOGE, bool MERGE>
+__global__ __launch_bounds__(kTileThreads) void f_dr2_icols_lift_fcols_kernel(const u64 *__restrict__ acc, const MulRsItem *__restrict__ items,
+                                                                               u64 *__restrict__ tmp, int ell, int Kp,
+                                                                               const DModulus *__restrict__ mods,
+                                                                               const u64 *__restrict__ half_mod,
+                                                                               const u64 *__restrict__ inv_last, const u64 *__restrict__ tw,
+                                                                               const u64 *__restrict__ itw, int logN, const u64 *__restrict__ tw2)
+{
+    __shared__ __attribute__((aligned(16))) u64 lds[TileGeo<LOGE>::LDS_ELEMS];
+    constexpr int E = 1 << LOGE;
+    const int cnt = ell - 1, L = ell - 1, sp = Kp - 1;
+    const int z = blockIdx.y, bp = MERGE ? z : z / cnt;
+    const size_t N = (size_t)1 << logN;
+    const u64 *in_p = acc + ((size_t)bp * (ell + 1) + ell) * N, *in_l = acc + ((size_t)bp * (ell + 1) + L) * N;
+    const u64 *mul = items[bp >> 1].mul;
+    const long mul_stride = items[bp >> 1].mul_stride;
+    auto nost = [](int, u64) {};
+    u64 rho[E], u[E];
+    ntt_tile_x<K, LOGE, true, true, true, false, true>(
+        rho, mods[sp], itw + ((size_t)sp << logN), logN, blockIdx.x, [=](int g) { return in_p[g]; }, nost, lds);
+    __syncthreads(); // the tile's last LDS image has been read by everyone
+    const DModulus ML = mods[L];
+    ntt_tile_x<K, LOGE, true, true, true, false, true>(
+        u, ML, itw + ((size_t)L << logN), logN, blockIdx.x, [=](int g) { return in_l[g]; }, nost, lds);
+    {
+        const u64 P = mods[sp].q, half_p = P >> 1, qL = ML.q, half_l = qL >> 1;
+        const u64 neg_half = qL - half_mod[(size_t)sp * Kp + L];
+        u64 k = inv_last[(size_t)sp * Kp + L]; // s_L P^-1 mod q_L
+        if (mul) k = mulmod(mul[(long)L * mul_stride], k, ML);
+#pragma unroll
+        for (int r = 0; r < E; r++) {
+            const u64 y = rho[r] + half_p;
+            rho[r] = y >= P ? y - P : y;
+            const u64 t = recanon(rho[r], ML) + neg_half;
+            const u64 c = mulmod(submod(u[r], t >= qL ? t - qL : t, qL), k, ML) + half_l;
+            u[r] = c >= qL ? c - qL : c;
+        }
+    }
+    auto nold = [](int) -> u64 { return 0; };
+    for (int i = MERGE ? 0 : z % cnt; i < (MERGE ? cnt : z % cnt + 1); i++) {
+        u64 *out = tmp + ((size_t)bp * cnt + i) * N;
+        const DModulus Mi = mods[i];
+        const u64 qi = Mi.q, neg_half_p = qi - half_mod[(size_t)sp * Kp + i], neg_half_l = qi - half_mod[(size_t)L * Kp + i];
+        const u64 k2 = inv_last[(size_t)L * Kp + i]; // q_L^-1 and s_i P^-1 q_L^-1 mod q_i
+        u64 k3 = mulmod(inv_last[(size_t)sp * Kp + i], k2, Mi);
+        if (mul) k3 = mulmod(mul[(long)i * mul_stride], k3, Mi);
+        u64 y[E];
+#pragma unroll
+        for (int r = 0; r < E; r++) {
+            const u64 t = recanon(rho[r], Mi) + neg_half_p, w = recanon(u[r], Mi) + neg_half_l;
+            Acc128 a;
+            a.clear();
+            a.mac(t >= qi ? t - qi : t, k3);
+            a.mac(w >= qi ? w - qi : w, k2);
+            y[r] = a.reduce(Mi);
         }
         __syncthreads();
         ntt_tile_fcols<K, LOGE, false, true, false>(
@@ -544,13 +627,117 @@ __global__ __launch_bounds__(kTileThreads) void f_frows_final_cont_kernel(const 
     }
 }
 
+// L7 + R3 of a multiply whose rescale is folded in: output polynomial p, kept limb i of item b at this tile's coefficients g[],
+//   r_i = s_i q_L^-1 (X_i P^-1 + d_i + A_i) - NTT_i(v_i)
+// (X the key-switch inner product, d the tensor term computed here as mode 4 of f_frows_final_kernel does, A the plaintext added to c0, v what
+// f_dr2_icols_lift_fcols_kernel left), stored to the item's destination at level l - 1 and left in v[] (canonical).
+template <int K, int LOGE>
+__device__ __forceinline__ void fold_final_value(u64 (&v)[1 << LOGE], const int (&g)[1 << LOGE], const u64 *__restrict__ in, const MulRsItem &it,
+                                                 const u64 *__restrict__ acc, int b, int p, int i, int ell, int Kp, const DModulus &M,
+                                                 const u64 *__restrict__ inv_last, const u64 *__restrict__ tw, int logN, u64 *__restrict__ lds)
+{
+    constexpr int E = 1 << LOGE;
+    const size_t N = (size_t)1 << logN;
+    auto nost = [](int, u64) {};
+    u64 x[E];
+    ntt_tile_x<K, LOGE, false, false, true, false, true>(x, M, tw + ((size_t)i << logN), logN, blockIdx.x, [=](int gi) { return in[gi]; }, nost, lds);
+    const u64 pinv = inv_last[(size_t)(Kp - 1) * Kp + i];
+    u64 k1 = inv_last[(size_t)(ell - 1) * Kp + i]; // s_i q_L^-1 mod q_i
+    if (it.mul) k1 = mulmod(it.mul[(long)i * it.mul_stride], k1, M);
+    const u64 *ac = acc + (((size_t)(b * 2 + p)) * (ell + 1) + i) * N;
+    const u64 *a0 = it.a.limb(0, i, N), *a1 = it.a.limb(1, i, N), *b0 = it.b.limb(0, i, N), *b1 = it.b.limb(1, i, N);
+    const u64 *pl = (it.add && p == 0) ? it.add + (size_t)i * N : nullptr;
+    u64 *o = it.dst.limb(p, i, N);
+    u64 base[E];
+    if (p == 0) {
+#pragma unroll
+        for (int j = 0; j < E; j++) base[j] = mulmod(a0[g[j]], b0[g[j]], M);
+        if (pl) {
+#pragma unroll
+            for (int j = 0; j < E; j++) base[j] = addmod(base[j], pl[g[j]], M.q);
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < E; j++) {
+            Acc128 t;
+            t.clear();
+            t.mac(a0[g[j]], b1[g[j]]);
+            t.mac(a1[g[j]], b0[g[j]]);
+            base[j] = t.reduce(M);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < E; j++) {
+        v[j] = submod(mulmod(addmod(mulmod(ac[g[j]], pinv, M), base[j], M.q), k1, M), x[j], M.q);
+        o[g[j]] = v[j];
+    }
+}
+
+// grid = (tiles, 2B * cnt), z = (b*2 + p)*cnt + i with cnt = l - 1; CONT_MUL / CONT_BOOT (grid (tiles, B * cnt), z = b*cnt + i) carry on into the
+// consumer's first phase exactly as f_frows_final_cont_kernel's rescale forms do: the merged step keeps the rescale's outgoing hand-off.
+template <int K, int LOGE, int CONT>
+__global__ __launch_bounds__(kTileThreads) void f_frows_fold_final_kernel(const u64 *__restrict__ tmp, const MulRsItem *__restrict__ items,
+                                                                           const u64 *__restrict__ acc, int ell, int Kp,
+                                                                           const DModulus *__restrict__ mods, const u64 *__restrict__ inv_last,
+                                                                           const u64 *__restrict__ tw, const u64 *__restrict__ itw, int logN,
+                                                                           Handoff h)
+{
+    __shared__ __attribute__((aligned(16))) u64 lds[TileGeo<LOGE>::LDS_ELEMS];
+    constexpr int E = 1 << LOGE, NP = num_passes<LOGE>(K);
+    const size_t N = (size_t)1 << logN;
+    const int cnt = ell - 1;
+    int g[E];
+#pragma unroll
+    for (int j = 0; j < E; j++) g[j] = tile_gidx<K, LOGE, false>(NP - 1, logN, blockIdx.x, j);
+    auto nold = [](int) -> u64 { return 0; };
+    if (CONT == CONT_BOOT) {
+        const int z = blockIdx.y, i = z % cnt, b = z / cnt;
+        const DModulus M = mods[i];
+        const MulRsItem it = items[b];
+        u64 v0[E], v1[E];
+        fold_final_value<K, LOGE>(v0, g, tmp + ((size_t)(b * 2 + 0) * cnt + i) * N, it, acc, b, 0, i, ell, Kp, M, inv_last, tw, logN, lds);
+        __syncthreads(); // the tile's last LDS image has been read by everyone
+        fold_final_value<K, LOGE>(v1, g, tmp + ((size_t)(b * 2 + 1) * cnt + i) * N, it, acc, b, 1, i, ell, Kp, M, inv_last, tw, logN, lds);
+        const u64 *sk = h.sk + (size_t)i * N;
+#pragma unroll
+        for (int j = 0; j < E; j++) v0[j] = addmod(v0[j], mulmod(v1[j], sk[g[j]], M), M.q);
+        __syncthreads();
+        u64 *o = h.out + (size_t)z * N;
+        ntt_tile_x<K, LOGE, false, true, false, true, false>(v0, M, itw + ((size_t)i << logN), logN, blockIdx.x, nold, [=](int gi, u64 v) { o[gi] = v; }, lds);
+    } else {
+        const int z = blockIdx.y, i = z % cnt, bp = z / cnt, b = bp >> 1, p = bp & 1;
+        const DModulus M = mods[i];
+        u64 v[E];
+        fold_final_value<K, LOGE>(v, g, tmp + (size_t)z * N, items[b], acc, b, p, i, ell, Kp, M, inv_last, tw, logN, lds);
+        if (CONT == CONT_MUL) {
+            if (p != 1) return;
+            const CtView other = h.other[b];
+            if (other.p) {
+                const u64 *o1 = other.limb(1, i, N);
+#pragma unroll
+                for (int j = 0; j < E; j++) v[j] = mulmod(v[j], o1[g[j]], M);
+            } else {
+#pragma unroll
+                for (int j = 0; j < E; j++) v[j] = mulmod(v[j], v[j], M);
+            }
+            __syncthreads();
+            u64 *o = h.out + ((size_t)b * cnt + i) * N;
+            ntt_tile_x<K, LOGE, false, true, false, true, false>(v, M, itw + ((size_t)i << logN), logN, blockIdx.x, nold, [=](int gi, u64 y) { o[gi] = y; }, lds);
+        }
+    }
+}
+
 // L3 + L4 + L5 in one launch (latency path): grid = (tiles, l + 2, B).  Workgroup (tile, y, b) owns one ROWS-phase tile of
 // output modulus slot m (y < l: prime y, both accumulators; y = l, l + 1: the special prime, accumulator y - l).  For every
 // digit j it finishes the NTT of the lifted digit (forward ROWS phase, result kept in registers) -- or, for j == m, reads the
 // operand itself, which is already in NTT form -- and multiplies by the key limb at the same coefficients.  The special-prime
 // accumulators continue in registers into the inverse ROWS phase that the mod-down starts with.
 // MODE 0: rotation (operand = c1 of the item through its Galois permutation, key per item); MODE 1: relinearisation.
-template <int K, int LOGE, int MODE, bool MERGE>
+// FOLD (MODE 1, option ks_fold_rescale; items is a MulRsItem table, pmod = P mod q_i): the multiply's rescale is folded into the key switch.
+// Row l - 1 -- the limb that rescale drops -- starts its accumulators at P (d + A) (d the tensor term, A the plaintext added to c0) and leaves,
+// like the special prime's, as the first inverse ROWS phase of both accumulators, in its own slot of acc: f_dr2_icols_lift_fcols_kernel
+// divides by P and by q_{l-1} in one pass from the two.
+template <int K, int LOGE, int MODE, bool MERGE, bool FOLD = false>
 __global__ __launch_bounds__(kTileThreads) void f_ks_frows_mac_kernel(const u64 *__restrict__ ext, const u64 *__restrict__ target,
                                                                        const KsItem *__restrict__ items,
                                                                        const u64 *__restrict__ shared_key, u64 *__restrict__ acc, int ell,
@@ -586,6 +773,23 @@ __global__ __launch_bounds__(kTileThreads) void f_ks_frows_mac_kernel(const u64 
         galois_gather<E>(cv, c0, (u32)g[0], it.elt, logN);
 #pragma unroll
         for (int e = 0; e < E; e++) a0[e].lo = mulmod(cv[e], P, M);
+    }
+    if (FOLD && m == ell - 1) { // (start values for the reason given above: nothing else is live yet)
+        const MulRsItem &it = reinterpret_cast<const MulRsItem *>(items)[b];
+        const u64 *pa0 = it.a.limb(0, m, N), *pa1 = it.a.limb(1, m, N), *pb0 = it.b.limb(0, m, N), *pb1 = it.b.limb(1, m, N);
+        const u64 *pl = it.add ? it.add + (size_t)m * N : nullptr;
+        const u64 P = pmod[m];
+#pragma unroll
+        for (int e = 0; e < E; e++) {
+            const u64 va0 = pa0[g[e]], va1 = pa1[g[e]], vb0 = pb0[g[e]], vb1 = pb1[g[e]];
+            u64 d0 = mulmod(va0, vb0, M);
+            if (pl) d0 = addmod(d0, pl[g[e]], M.q);
+            Acc128 t;
+            t.clear();
+            t.mac(va0, vb1);
+            t.mac(va1, vb0);
+            a0[e].lo = mulmod(d0, P, M), a1[e].lo = mulmod(t.reduce(M), P, M);
+        }
     }
     auto nost = [](int, u64) {};
     auto nold = [](int) -> u64 { return 0; };
@@ -641,7 +845,7 @@ __global__ __launch_bounds__(kTileThreads) void f_ks_frows_mac_kernel(const u64 
             for (int e = 0; e < E; e++) x[e] = xn[e];
             if (j + 1 < ell) fetch_x(j + 1, xn);
             if (own_on_the_fly(j)) { // c2 = a1*b1 on the fly (items points at the MulItem table)
-                const MulItem &it = reinterpret_cast<const MulItem *>(items)[b];
+                const MulItem &it = FOLD ? static_cast<const MulItem &>(reinterpret_cast<const MulRsItem *>(items)[b]) : reinterpret_cast<const MulItem *>(items)[b];
                 const u64 *a1 = it.a.limb(1, j, N), *b1 = it.b.limb(1, j, N);
 #pragma unroll
                 for (int e = 0; e < E; e++) x[e] = mulmod(a1[g[e]], b1[g[e]], M);
@@ -660,7 +864,7 @@ __global__ __launch_bounds__(kTileThreads) void f_ks_frows_mac_kernel(const u64 
 #pragma unroll
                 for (int e = 0; e < E; e++) x[e] = tg[g[e]];
             } else { // c2 = a1*b1 on the fly (items points at the MulItem table)
-                const MulItem &it = reinterpret_cast<const MulItem *>(items)[b];
+                const MulItem &it = FOLD ? static_cast<const MulItem &>(reinterpret_cast<const MulRsItem *>(items)[b]) : reinterpret_cast<const MulItem *>(items)[b];
                 const u64 *a1 = it.a.limb(1, j, N), *b1 = it.b.limb(1, j, N);
 #pragma unroll
                 for (int e = 0; e < E; e++) x[e] = mulmod(a1[g[e]], b1[g[e]], M);
@@ -689,7 +893,18 @@ __global__ __launch_bounds__(kTileThreads) void f_ks_frows_mac_kernel(const u64 
             }
         }
     }
-    if (m < ell) {
+    if (FOLD && m == ell - 1) {
+        for (int p = 0; p < 2; p++) {
+            u64 r[E];
+#pragma unroll
+            for (int e = 0; e < E; e++) r[e] = p == 0 ? a0[e].reduce(M) : a1[e].reduce(M);
+            u64 *o = acc + (((size_t)b * 2 + p) * (ell + 1) + m) * N;
+            if (lds_used) __syncthreads();
+            ntt_tile_x<K, LOGE, false, true, false, true, false>(r, M, itw + ((size_t)pm << logN), logN, blockIdx.x, nold,
+                                                                 [=](int gi, u64 v) { o[gi] = v; }, lds);
+            lds_used = true;
+        }
+    } else if (m < ell) {
         u64 *ac = acc + (size_t)b * 2 * (ell + 1) * N;
         u64 *o0 = ac + ((size_t)0 * (ell + 1) + m) * N, *o1 = ac + ((size_t)1 * (ell + 1) + m) * N;
 #pragma unroll
@@ -811,6 +1026,10 @@ void f_irows_tensor_c2(const Context &c, const MulItem *items, int ell, u64 *out
 {
     launch_irows(c, SrcTensorC2{ items, c.d_mods, ell }, out, (long)c.N, B * ell, s);
 }
+void f_irows_tensor_c2_rs(const Context &c, const MulRsItem *items, int ell, u64 *out, int B, hipStream_t s)
+{
+    launch_irows(c, SrcTensorC2Rs{ items, c.d_mods, ell }, out, (long)c.N, B * ell, s);
+}
 void f_irows_decrypt_items(const Context &c, const BootItem *items, const SumSrc *srcs, const u64 *sk, int ell, u64 *out, int B,
                            hipStream_t s)
 {
@@ -849,6 +1068,17 @@ void f_ks_frows_mac(const Context &c, int mode, const u64 *ext, const u64 *targe
         else
             DC_LAUNCH((f_ks_frows_mac_kernel<KK, LE, 1, MG>), sh.grid, dim3(kTileThreads), 0, s, ext, target, items, shared_key, acc, ell, c.K,
                       c.d_mods, c.d_tw, c.d_itw, c.logN, pmod, sh.items_fast);
+    });
+}
+
+void f_ks_frows_mac_rs(const Context &c, const u64 *ext, const MulRsItem *items, const u64 *relin_key, u64 *acc, int B, int ell, hipStream_t s)
+{
+    const KsMacShape sh = ks_mac_shape(c, ell, B);
+    ks_mac_dispatch(c.k2, sh, [&](auto k, auto le, auto merge) {
+        constexpr int KK = decltype(k)::value, LE = decltype(le)::value;
+        constexpr bool MG = decltype(merge)::value;
+        DC_LAUNCH((f_ks_frows_mac_kernel<KK, LE, 1, MG, true>), sh.grid, dim3(kTileThreads), 0, s, ext, nullptr, reinterpret_cast<const KsItem *>(items),
+                  relin_key, acc, ell, c.K, c.d_mods, c.d_tw, c.d_itw, c.logN, c.d_pmod, sh.items_fast);
     });
 }
 
@@ -891,7 +1121,28 @@ void f_dr_icols_lift_fcols(const Context &c, const u64 *last, long last_stride, 
     DC_MERGED_LAUNCH(polys * cnt, polys, cnt, f_dr_icols_lift_fcols_kernel, last, last_stride, tmp, cnt, l, c.K, c.d_mods, c.d_half_mod, c.d_tw,
                      c.d_itw, c.logN, c.twc2())
 }
+
+void f_dr2_icols_lift_fcols(const Context &c, const u64 *acc, const MulRsItem *items, u64 *tmp, int B, int ell, hipStream_t s)
+{
+    DC_MERGED_LAUNCH(2 * B * (ell - 1), 2 * B, ell - 1, f_dr2_icols_lift_fcols_kernel, acc, items, tmp, ell, c.K, c.d_mods, c.d_half_mod, c.d_inv_last,
+                     c.d_tw, c.d_itw, c.logN, c.twc2())
+}
 #undef DC_MERGED_LAUNCH
+
+void f_frows_fold_final(const Context &c, const u64 *tmp, const MulRsItem *items, const u64 *acc, int B, int ell, hipStream_t s, const Handoff &h)
+{
+    const int cnt = ell - 1, groups = h.cont == CONT_BOOT ? B : 2 * B;
+#define DC_FOLD(CT)                                                                                                                    \
+    DC_GEO_SWITCH(c.k2, groups * cnt, DC_LAUNCH((f_frows_fold_final_kernel<KK, LE, CT>), grid, dim3(kTileThreads), 0, s, tmp, items, acc, ell, c.K, \
+                                                         c.d_mods, c.d_inv_last, c.d_tw, c.d_itw, c.logN, h))
+    switch (h.cont) {
+    case CONT_NONE: DC_FOLD(CONT_NONE); break;
+    case CONT_MUL: DC_FOLD(CONT_MUL); break;
+    case CONT_BOOT: DC_FOLD(CONT_BOOT); break;
+    default: fprintf(stderr, "[dacapo_amd] f_frows_fold_final: no continuation kernel for consumer kind %d\n", h.cont); abort();
+    }
+#undef DC_FOLD
+}
 
 void f_ks_lift_fcols(const Context &c, const u64 *digits, u64 *ext, int B, int ell, hipStream_t s)
 {

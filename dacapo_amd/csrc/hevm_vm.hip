@@ -469,6 +469,12 @@ void HEVM::init_context(int logN, int K, const u64 *primes, int dir_ksp, int dir
                         "(ks_hoist = 0 here)\n", ks_lazy);
         abort();
     }
+    ks_fold_rescale = option(OPT_KS_FOLD_RESCALE) != 0;
+    if (ks_fold_rescale && (ksp > 1 || alpha > 1)) {
+        fprintf(stderr, "[dacapo_amd] option ks_fold_rescale = 1 is for SEAL-layout keys (ks_special = 1); with ks_special = %d, ks_alpha = %d the mod-down "
+                        "is an approximate base conversion, and dividing by P q in one exact pass does not reproduce it\n", ksp, alpha);
+        abort();
+    }
     // prime_bits = b (45..60; the generic-width build only): the chain CoeffModulus::Create(N, {b, b, ...}) instead of the reference's
     // 60-bit one (SEAL_HEVM.cpp:48-53) -- e.g. 51 for rescale primes of the HEaaN configuration's width
     const int bits = (int)option(OPT_PRIME_BITS);
@@ -1887,7 +1893,7 @@ void HEVM::execute()
 {
     memset(op_counts, 0, sizeof(op_counts));
     n_keyswitch = n_ntt = 0;
-    n_hops = n_decomp = 0;
+    n_hops = n_decomp = 0, n_fold = 0;
     t_bootstrap = 0.0;
     int i = (int)((header.hevm_header_size + config.config_body_length) / 8), j = 0;
     for (const WireOp &op : ops) {
@@ -2274,6 +2280,13 @@ void hevm_last_run_hoist_stats(void *vm, int64_t *hops, int64_t *decompositions)
     auto h = V(vm);
     if (hops) *hops = h->n_hops;
     if (decompositions) *decompositions = h->n_decomp;
+}
+
+// option ks_fold_rescale: items (multiply-rescale pairs x streams) that the plan of the last run() executed as one merged step; 0 with the
+// option off, in the loop (plan = 0), and for pairs that keep the default sequence
+void hevm_last_run_fold_rescale_stats(void *vm, int64_t *pairs)
+{
+    if (pairs) *pairs = V(vm)->n_fold;
 }
 
 // options hyb_lazy_sum / ks_lazy_sum: which rotate instructions of the loaded program the plan of the last run() executed as lazy sums (one

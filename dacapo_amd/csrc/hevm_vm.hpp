@@ -189,6 +189,8 @@ class HEVM {
         int wave = 0, lane = 0;             // steps of one wave are independent: lane 1 runs on the auxiliary stream
         Handoff h;                          // link to a fused producer (h.in) / consumer (h.cont, h.out) step, plan.hpp
         int fused_consumer = -1;            // index of the step whose first phase this step's last kernel computes
+        bool fold_rs = false;               // P_MULCC, option ks_fold_rescale: every item also does the rescale that alone reads it (first: in d_mulrs);
+                                            // those rescales are in no step of their own, and the step defines THEIR results
         int gfirst = 0, gcount = 0;         // P_SUM: the step's items as groups that share sources (plan.hpp SumGroup), when it runs that way; P_ROTSUM: its groups (in d_ks; option ks_lazy_sum: the distinct sources' items follow them)
         int unique = 0;                     // P_ROT, grouped-digit mode: distinct source ciphertexts among the items (shared decompositions)
                                             // ... and option ks_hoist (target == -2): the same count; d_ks[gfirst .. gfirst + unique) are the sources' items
@@ -204,6 +206,7 @@ class HEVM {
         std::vector<int> final_val; // architectural register -> value at program end
         KsItem *d_ks = nullptr;
         MulItem *d_mul = nullptr;
+        MulRsItem *d_mulrs = nullptr;        // items of the multiply steps whose rescale is folded in (Step::fold_rs)
         RsItem *d_rs = nullptr;
         EwItem *d_ew = nullptr;
         SumItem *d_sum = nullptr;
@@ -234,6 +237,7 @@ class HEVM {
         std::vector<u64 *> pool; // every pool buffer ever allocated (reused across plans)
         int64_t n_keyswitch = 0, n_ntt = 0;
         int64_t n_hops = 0, n_decomp = 0; // rotation hops and the decompositions computed for them (hevm_last_run_hoist_stats)
+        int64_t n_fold = 0;               // items of multiply steps that run with their rescale folded in (hevm_last_run_fold_rescale_stats)
         size_t launches = 0, max_live = 0;
         hipGraph_t graph = nullptr;
         hipGraphExec_t graph_exec = nullptr;
@@ -273,6 +277,9 @@ class HEVM {
     // option ks_lazy_sum (with ks_hoist): 1 sums of bare rotations share one division by P, 2 rotations times a plaintext join them too
     // (plan_exec.hip section 2b; hoist_ks.hip hoist_rotate_sum)
     int ks_lazy = 0;
+    // option ks_fold_rescale = 1 (SEAL-layout keys): a multiply and the rescale that alone reads it run as one step
+    // (plan_exec.hip section 4; plan.hpp b_mul_relin_rescale).  Every limb equals the default path's.
+    bool ks_fold_rescale = false;
     KsItem *d_hoist_items = nullptr; // the loop's (plan = 0) two-entry item table: the hop and its source
     void rotate_hop_vm(CtView dst, CtView src, u32 elt, const u64 *key, int ell);
     bool chain_fusion = true; // option chain_fusion = 0: every step runs all of its own launches
@@ -292,6 +299,7 @@ class HEVM {
     int64_t op_counts[11] = { 0 };
     int64_t n_keyswitch = 0, n_ntt = 0;
     int64_t n_hops = 0, n_decomp = 0; // hevm_last_run_hoist_stats
+    int64_t n_fold = 0;               // hevm_last_run_fold_rescale_stats
     double t_bootstrap = 0.0; // host wall time spent inside opcode 10
 
     VmAllocs allocs;   // device memory held by this VM (hevm_destroy)

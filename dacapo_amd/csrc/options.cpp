@@ -39,6 +39,7 @@ static const OptDef kDefs[OPT_COUNT] = {
     { "hyb_double_hoist", 0 },
     { "ks_hoist", 0 },
     { "ks_lazy_sum", 0 },
+    { "ks_fold_rescale", 0 },
     { "seal_compr", 0 },
     { "trace", 0 },
     { "step_profile", 0 },

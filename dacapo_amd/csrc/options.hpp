@@ -40,6 +40,7 @@ enum Opt : int {
     OPT_HYB_DOUBLE_HOIST,  // with hyb_lazy_sum: a rotation multiplied by a plaintext before it joins the sum is a member too -- the product is taken in the raised basis (the plaintext's special-prime limbs are encoded at preprocess) and the group still has ONE mod-down (changes the rounding like hyb_lazy_sum: off)
     OPT_KS_HOIST,          // SEAL-layout keys: rotation hops take the digits before the automorphism, and the hops of a plan step that read one source ciphertext share one decomposition (changes the rounding: off; with ks_special > 1 it aborts -- that mode already hoists)
     OPT_KS_LAZY_SUM,       // SEAL-layout keys, with ks_hoist: rotations (the last hop of a rotate instruction) whose single-use results are bare terms of one sum share ONE mod-down (hoist_ks.hip f_ks_gsum_kernel); 2: a rotation times a plaintext before it joins the sum is a member too, the product taken in the raised basis (changes the rounding: off; hevm_plan_lazy_groups names the groups; without ks_hoist, or with ks_special > 1, it aborts)
+    OPT_KS_FOLD_RESCALE,   // SEAL-layout keys: a ct x ct multiply whose value only a rescale reads runs with that rescale as ONE five-launch sequence -- one exact pass divides by P q_{l-1} (fused_ks.hip f_dr2_icols_lift_fcols_kernel); every limb equals the default path's (off until measured; hevm_last_run_fold_rescale_stats counts the pairs; with ks_special > 1 it aborts)
     OPT_SEAL_COMPR,        // compression of written .seal files: 0 none, 1 zlib, 2 zstd
     OPT_TRACE,             // plan statistics on stderr (2: per wave)
     OPT_STEP_PROFILE,      // per-step timing of an un-graphed plan on stderr

@@ -29,6 +29,14 @@ struct KsItem {   // one key-switch hop of a rotation: dst = apply_galois(src)
 struct MulItem {  // dst = relinearize(a * b)
     CtView a, b, dst;
 };
+// dst (level l - 1) = rescale_to_next(((relinearize(a * b) + add on c0) * mul)) with the rescale folded into the key switch (option
+// ks_fold_rescale; fused_ks.hip f_dr2_icols_lift_fcols_kernel).  mul is a CONSTANT polynomial: limb i's value is mul[i * mul_stride]
+// (a plaintext [level][N] whose every value of a limb equals its first: stride N; a table of residues: stride 1), or null
+struct MulRsItem : MulItem {
+    const u64 *add = nullptr; // plaintext [level][N] added to c0, or null
+    const u64 *mul = nullptr;
+    long mul_stride = 0;
+};
 struct RsItem {   // dst = rescale_to_next(expr), expr = ((src | sum of `count` terms srcs[first ...]) + add on c0) * mul
     CtView src, dst;
     int first = 0, count = 0;          // count == 0: expr starts from src
@@ -103,6 +111,12 @@ struct BatchWs {
 void b_rotate_hops(Context &c, const BatchWs &w, const KsItem *d_items, int B, int ell, hipStream_t s, const Handoff &h = Handoff{}, int unique = 0);
 void b_mul_relin(Context &c, const BatchWs &w, const MulItem *d_items, const u64 *relin_key, int B, int ell, hipStream_t s,
                  const Handoff &h = Handoff{});
+// a multiply and the rescale that alone reads it as ONE five-launch sequence (SEAL-layout keys, the latency-shaped launch forms only:
+// mul_relin_rescale_fused says whether a batch of B at level ell has it; otherwise run b_mul_relin and b_rescale -- the limbs are the same).
+// h.in as for b_mul_relin; h.cont CONT_MUL / CONT_BOOT as for b_rescale.
+bool mul_relin_rescale_fused(const Context &c, int B, int ell);
+void b_mul_relin_rescale(Context &c, const BatchWs &w, const MulRsItem *d_items, const u64 *relin_key, int B, int ell, hipStream_t s,
+                         const Handoff &h = Handoff{});
 void b_rescale(Context &c, const BatchWs &w, const RsItem *d_items, int B, int ell, hipStream_t s, const SumSrc *d_srcs = nullptr,
                const Handoff &h = Handoff{});
 // hoisted rotations on SEAL-layout keys (hoist_ks.hip; option ks_hoist, dc_ct_rotate_hoisted): B hops over U <= B decompositions, digits taken
@@ -152,6 +166,13 @@ void f_irows_tensor_c2(const Context &c, const MulItem *items, int ell, u64 *out
 // batched opcode 10: inverse ROWS phase of c0 + c1*s of every item -> out[B][ell][N] ...
 void f_irows_decrypt_items(const Context &c, const BootItem *items, const SumSrc *srcs, const u64 *sk, int ell, u64 *out, int B,
                            hipStream_t s);
+// the phases of b_mul_relin_rescale that differ from b_mul_relin's: first inverse phase of a1*b1 from a MulRsItem table; the fused middle
+// whose row l - 1 leaves as an inverse ROWS phase with P (d + A) added; both divisions in one COLS launch; the last ROWS phase
+void f_irows_tensor_c2_rs(const Context &c, const MulRsItem *items, int ell, u64 *out, int B, hipStream_t s);
+void f_ks_frows_mac_rs(const Context &c, const u64 *ext, const MulRsItem *items, const u64 *relin_key, u64 *acc, int B, int ell, hipStream_t s);
+void f_dr2_icols_lift_fcols(const Context &c, const u64 *acc, const MulRsItem *items, u64 *tmp, int B, int ell, hipStream_t s);
+void f_frows_fold_final(const Context &c, const u64 *tmp, const MulRsItem *items, const u64 *acc, int B, int ell, hipStream_t s,
+                        const Handoff &h = Handoff{});
 // re-encode + reduce + first forward phase in one launch (ell == 1: every target limb recomputes the trivial composition):
 // pt [B][ell][N] coefficient domain -> ptx [B][t][N] after the COLS phase
 void f_boot_reencode_fcols(const Context &c, const u64 *pt, u64 *ptx, const BootItem *items, int B, int ell, int t, CrtDev crt,
@@ -173,6 +194,8 @@ void f_dr_lift_fcols(const Context &c, const u64 *last, long last_stride, u64 *t
 void f_frows_final(const Context &c, int mode, const u64 *tmp, const void *items, const u64 *acc, int polys, int cnt, int l,
                    hipStream_t s, RsItem single = RsItem{}, const u64 *plain = nullptr, const SumSrc *srcs = nullptr,
                    const Handoff &h = Handoff{}, bool base_folded = false);
+// out[i][k] = residues[i] for i < ell: a constant polynomial's limbs in NTT form (batch_ops.hip)
+void fill_const_plain(Context &c, u64 *out, const u64 *d_residues, int ell, hipStream_t s);
 // a single rescale_to_next of `src` (level ell) into dst, optionally adding a level-(ell-1) plaintext to c0: 3 launches
 void rescale_fused(Context &c, const Workspace &w, CtView dst, CtView src, int ell, const u64 *plain, hipStream_t s);
 

@@ -39,6 +39,7 @@ void HEVM::build_plan()
     P.d_enc_items = nullptr, P.enc_arena = nullptr, P.enc_scratch = nullptr, P.d_enc_overflow = nullptr;
     P.enc_groups.clear(), P.enc_arena_bytes = P.enc_scratch_bytes = 0;
     if (P.d_cont_other) (void)vm_free(P.d_cont_other), P.d_cont_other = nullptr;
+    if (P.d_mulrs) (void)vm_free(P.d_mulrs), P.d_mulrs = nullptr;
     for (void *p : { (void *)P.d_ks, (void *)P.d_mul, (void *)P.d_rs, (void *)P.d_ew, (void *)P.d_sum, (void *)P.d_sum_srcs, (void *)P.d_sumg, (void *)P.d_sumg_srcs, (void *)P.d_boot,
                      (void *)P.d_boot_rs, (void *)P.zenc, (void *)P.boot_ue, (void *)P.boot_tmp, (void *)P.boot_pt[0], (void *)P.boot_ptx[0],
                      (void *)P.boot_pt[1], (void *)P.boot_ptx[1] })
@@ -51,7 +52,7 @@ void HEVM::build_plan()
     P.graph_exec = nullptr, P.graph = nullptr;
     P.vals.clear(), P.pops.clear(), P.steps.clear();
     P.n_keyswitch = P.n_ntt = 0;
-    P.n_hops = P.n_decomp = 0;
+    P.n_hops = P.n_decomp = 0, P.n_fold = 0;
     const size_t nreg = ciphers.size();
     const int S = streams; // independent ciphertext streams executed side by side (items of every step are replicated)
     std::vector<int> cur(nreg, -1);
@@ -480,6 +481,7 @@ void HEVM::build_plan()
         if (!O[i].dead) by_wave[(size_t)O[i].wave].push_back((int)i);
     std::vector<KsItem> h_ks;
     std::vector<MulItem> h_mul;
+    std::vector<MulRsItem> h_mulrs;
     std::vector<RsItem> h_rs;
     std::vector<EwItem> h_ew;
     std::vector<SumItem> h_sum;
@@ -488,10 +490,47 @@ void HEVM::build_plan()
     double sum_stat[5] = { 0, 0, 0, 0, 0 }; // option trace: sharing of sources between the items of an n-ary sum step
     std::vector<SumSrc> h_srcs;
     std::vector<std::vector<int>> step_pops;
+    // Option ks_fold_rescale: a ct x ct multiply and the rescale that alone reads it run as ONE step (plan.hpp b_mul_relin_rescale: one exact
+    // pass divides by P q_{l-1}; every limb equals the two steps').  A pair qualifies when the product has no reader but that rescale and is not
+    // a program result (its buffer is then never written), the rescale has no folded sum, and a folded multiplier is a constant polynomial --
+    // decided from the plaintext's limbs, every value of a limb equal to its first, read back once here.  Qualifying multiplies get a bucket of
+    // their own (target_level = -3), so a pair that does not qualify never holds back the other items of its wave; a chunk whose batch has no
+    // folded launch form (mul_relin_rescale_fused) stays two steps.  The merged step stands where the multiply stood, defines the RESCALE's
+    // result, and takes part in the links of section 4b as the rescale would (CONT_MUL / CONT_BOOT out, a producer's hand-off in).
+    std::map<int, int> fold_rs_of;                // qualifying multiply pop -> its rescale pop
+    std::vector<char> absorbed(O.size(), 0);      // rescale pops that a merged step executes: in no step of their own
+    std::map<size_t, std::vector<int>> fold_pops; // merged step -> the rescale pops it absorbed, item for item
+    if (ks_fold_rescale && !online_encode && !c.hybrid()) {
+        std::map<int, bool> constant; // plaintext register -> is it a constant polynomial
+        auto is_constant = [&](int reg) {
+            auto it = constant.find(reg);
+            if (it != constant.end()) return it->second;
+            const Plain &pl = plains.at((size_t)reg);
+            bool same = pl.d != nullptr;
+            if (same) {
+                std::vector<u64> h((size_t)pl.level * N);
+                DC_HIP_CHECK(hipMemcpy(h.data(), pl.d, h.size() * sizeof(u64), hipMemcpyDeviceToHost));
+                for (size_t i = 0; i < (size_t)pl.level && same; i++)
+                    for (size_t k = 1; k < N && same; k++) same = h[i * N + k] == h[i * N];
+            }
+            return constant[reg] = same;
+        };
+        for (size_t ri = 0; ri < O.size(); ri++) {
+            const Pop &rp = O[ri];
+            if (rp.dead || rp.kind != P_RESCALE || rp.rs_sum || rp.srcs.size() != 1) continue;
+            const Val &mv = V[(size_t)rp.srcs[0]];
+            if (mv.root != rp.srcs[0] || mv.def_pop < 0 || mv.uses != 1 || mv.pinned) continue;
+            Pop &mp = O[(size_t)mv.def_pop];
+            if (mp.dead || mp.kind != P_MULCC || mp.dst != rp.srcs[0] || mp.level != rp.level || mp.level < 2) continue;
+            if (rp.rs_mul >= 0 && !is_constant(rp.rs_mul)) continue;
+            fold_rs_of[mv.def_pop] = (int)ri, mp.target_level = -3;
+        }
+    }
     for (int w = 1; w <= max_wave; w++) {
         std::map<std::tuple<int, int, int>, std::vector<int>> buckets; // (kind, level, target level of opcode 10) -> pops
         for (int pi : by_wave[(size_t)w])
-            buckets[std::make_tuple((int)O[(size_t)pi].kind, O[(size_t)pi].level, O[(size_t)pi].target_level)].push_back(pi);
+            if (!absorbed[(size_t)pi])
+                buckets[std::make_tuple((int)O[(size_t)pi].kind, O[(size_t)pi].level, O[(size_t)pi].target_level)].push_back(pi);
         for (auto &kv : buckets) {
             const PopKind kind = (PopKind)std::get<0>(kv.first);
             // A rotation step's items in key order (option ks_items_fast): SEAL's default key set has 28 Galois elements, so the 64 hops of a
@@ -531,6 +570,17 @@ void HEVM::build_plan()
                 st.count = (int)std::min(chunk, kv.second.size() - off);
                 std::vector<int> members(kv.second.begin() + (long)off, kv.second.begin() + (long)off + st.count);
                 for (int pi : members) O[(size_t)pi].step = (int)P.steps.size();
+                if (kind == P_MULCC && st.target == -3) { // option ks_fold_rescale: the chunk and its rescales as one step, where a folded form exists
+                    st.target = 0;
+                    if (mul_relin_rescale_fused(c, st.count * S, st.level)) {
+                        st.fold_rs = true;
+                        std::vector<int> &rs = fold_pops[P.steps.size()];
+                        for (int pi : members) {
+                            const int ri = fold_rs_of.at(pi);
+                            rs.push_back(ri), absorbed[(size_t)ri] = 1, O[(size_t)ri].step = (int)P.steps.size();
+                        }
+                    }
+                }
                 P.steps.push_back(st);
                 step_pops.push_back(members);
             }
@@ -568,9 +618,10 @@ void HEVM::build_plan()
                     const int st = def_step_of(p.srcs[w]);
                     if (st < 0 || (ai >= 0 && st != ai)) continue;
                     const Step &A = P.steps[(size_t)st];
-                    const bool kinds = (B.kind == P_RESCALE && A.kind == P_MULCC && A.level == B.level) ||
-                                       (B.kind == P_BOOT && ((A.kind == P_RESCALE && A.level - 1 == B.level) || (A.kind == P_ROT && A.target >= 0 && A.level == B.level))) ||
-                                       (B.kind == P_MULCC && A.kind == P_RESCALE && A.level - 1 == B.level);
+                    const bool a_rescales = A.kind == P_RESCALE || (A.kind == P_MULCC && A.fold_rs); // (a merged step ends as a rescale does)
+                    const bool kinds = (B.kind == P_RESCALE && A.kind == P_MULCC && !A.fold_rs && A.level == B.level) ||
+                                       (B.kind == P_BOOT && ((a_rescales && A.level - 1 == B.level) || (A.kind == P_ROT && A.target >= 0 && A.level == B.level))) ||
+                                       (B.kind == P_MULCC && a_rescales && A.level - 1 == B.level);
                     if (!kinds || A.fused_consumer >= 0 || A.wave >= B.wave) continue;
                     if (B.kind == P_MULCC) { // the other operand: the same value, or complete before A starts
                         const int other = p.srcs[1 - w];
@@ -581,13 +632,14 @@ void HEVM::build_plan()
                 if (found < 0) ok = false;
                 ai = found;
             }
-            if (!ok || ai < 0 || step_pops[(size_t)ai].size() != bp.size()) continue;
+            // (the pops whose results A's last kernel holds: a merged step's are the rescales it absorbed)
+            const std::vector<int> &apops = (ai >= 0 && P.steps[(size_t)ai].fold_rs) ? fold_pops.at((size_t)ai) : step_pops[(size_t)std::max(ai, 0)];
+            if (!ok || ai < 0 || apops.size() != bp.size()) continue;
             // item for item: reorder B's pops to follow A's; every A result must be consumed by exactly one pop of B here
             std::vector<int> order(bp.size(), -1);
             std::vector<int> which2(bp.size(), 0);
             for (size_t k = 0; k < bp.size() && ok; k++) {
                 const int src = O[(size_t)bp[k]].srcs[(size_t)which[k]];
-                const std::vector<int> &apops = step_pops[(size_t)ai];
                 size_t pos = 0;
                 while (pos < apops.size() && O[(size_t)apops[pos]].dst != src) pos++;
                 if (pos == apops.size() || order[pos] >= 0)
@@ -597,6 +649,10 @@ void HEVM::build_plan()
             }
             if (!ok) continue;
             bp = order;
+            if (B.fold_rs) { // (a merged step's absorbed rescales follow its multiplies)
+                std::vector<int> &rs = fold_pops.at(bi);
+                for (size_t k = 0; k < bp.size(); k++) rs[k] = fold_rs_of.at(bp[k]);
+            }
             Step &A = P.steps[(size_t)ai];
             A.fused_consumer = (int)bi;
             A.h.cont = B.kind == P_RESCALE ? CONT_RS : B.kind == P_BOOT ? CONT_BOOT : CONT_MUL;
@@ -829,6 +885,21 @@ void HEVM::build_plan()
             break;
         }
         case P_MULCC:
+            if (st.fold_rs) { // dst, + plaintext and * constant are the absorbed rescale's
+                st.first = (int)h_mulrs.size();
+                const std::vector<int> &rs = fold_pops.at(s);
+                for (size_t k = 0; k < rs.size(); k++)
+                    for (int q = 0; q < S; q++) {
+                        const Pop &mp = O[(size_t)step_pops[s][k]], &rp = O[(size_t)rs[k]];
+                        MulRsItem it;
+                        it.a = view(mp.srcs[0], q), it.b = view(mp.srcs[1], q), it.dst = view(rp.dst, q);
+                        if (rp.rs_add >= 0) it.add = plains.at((size_t)rp.rs_add).d;
+                        if (rp.rs_mul >= 0) it.mul = plains.at((size_t)rp.rs_mul).d, it.mul_stride = (long)N;
+                        h_mulrs.push_back(it);
+                    }
+                P.n_fold += (int64_t)B;
+                break;
+            }
             st.first = (int)h_mul.size();
             for (int pi : step_pops[s])
                 for (int q = 0; q < S; q++)
@@ -996,6 +1067,8 @@ void HEVM::build_plan()
             for (int v : p.srcs) st.reads.push_back(V[(size_t)V[(size_t)v].root].buf);
             st.writes.push_back(V[(size_t)V[(size_t)p.dst].root].buf);
         }
+        if (st.fold_rs)
+            for (int pi : fold_pops.at(s)) st.writes.push_back(V[(size_t)V[(size_t)O[(size_t)pi].dst].root].buf);
         if (st.fused_consumer >= 0 && st.h.cont == CONT_MUL) // the producer's last kernel multiplies by the consumer's OTHER operand
             for (int pi : step_pops[(size_t)st.fused_consumer])
                 for (int v : O[(size_t)pi].srcs) st.reads.push_back(V[(size_t)V[(size_t)v].root].buf);
@@ -1064,6 +1137,7 @@ void HEVM::build_plan()
         }
         P.d_boot = upload(h_boot), P.d_boot_rs = upload(h_brs);
     }
+    P.d_mulrs = upload(h_mulrs);
     P.d_ks = upload(h_ks), P.d_mul = upload(h_mul), P.d_rs = upload(h_rs), P.d_ew = upload(h_ew), P.d_sum = upload(h_sum);
     P.h_ew = h_ew;
     P.d_sum_srcs = upload(h_srcs);
@@ -1203,7 +1277,12 @@ void HEVM::issue_step(const Step &st, hipStream_t q)
             break;
         }
         hyb_rotate_sum(c, w, P.d_ks + st.first, st.count, P.d_ks + st.gfirst, st.gcount, st.level, q, st.unique); break;
-    case P_MULCC: b_mul_relin(c, w, P.d_mul + st.first, keys.relin, st.count, st.level, q, st.h); break;
+    case P_MULCC:
+        if (st.fold_rs) {
+            b_mul_relin_rescale(c, w, P.d_mulrs + st.first, keys.relin, st.count, st.level, q, st.h);
+            break;
+        }
+        b_mul_relin(c, w, P.d_mul + st.first, keys.relin, st.count, st.level, q, st.h); break;
     case P_RESCALE: b_rescale(c, w, P.d_rs + st.first, st.count, st.level, q, P.d_sum_srcs, st.h); break;
     case P_SUM:
         if (st.gcount > 0)
@@ -1450,7 +1529,7 @@ void HEVM::run_plan()
     for (const WireOp &op : ops)
         if (op.opcode <= 10) op_counts[op.opcode]++;
     n_keyswitch = P.n_keyswitch, n_ntt = P.n_ntt;
-    n_hops = P.n_hops, n_decomp = P.n_decomp;
+    n_hops = P.n_hops, n_decomp = P.n_decomp, n_fold = P.n_fold;
     t_bootstrap = 0.0;
     const long ps = (long)c.K * (long)c.N;
     if (plan_graph) { // the plan is a fixed launch sequence: recorded once (normally by preprocess()), replayed as one graph launch

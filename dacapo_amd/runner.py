@@ -101,6 +101,7 @@ def bind_vm_lib(path):
     L.hevm_last_run_stats.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
                                        ctypes.POINTER(ctypes.c_int64)]
     L.hevm_last_run_hoist_stats.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
+    L.hevm_last_run_fold_rescale_stats.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)]
     L.hevm_plan_lazy_groups.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32), ctypes.c_int64]
     L.hevm_plan_lazy_groups.restype = ctypes.c_int64
     L.hevm_set_streams.argtypes = [ctypes.c_void_p, ctypes.c_int]
@@ -395,6 +396,12 @@ class HEVM:
         hops, dec = ctypes.c_int64(), ctypes.c_int64()
         self.lw.hevm_last_run_hoist_stats(self.vm, ctypes.byref(hops), ctypes.byref(dec))
         return {"hops": hops.value, "decompositions": dec.value}
+
+    def fold_rescale_stats(self):
+        """option ks_fold_rescale: items (multiply-rescale pairs, once per stream) the last run() executed as one merged step"""
+        pairs = ctypes.c_int64()
+        self.lw.hevm_last_run_fold_rescale_stats(self.vm, ctypes.byref(pairs))
+        return pairs.value
 
     def stats(self):
         counts = (ctypes.c_int64 * 11)()

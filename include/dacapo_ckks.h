@@ -96,6 +96,16 @@ void dc_ct_mul_plain(dc_context *ctx, uint64_t *dst, long dst_stride, const uint
 /* Evaluator::multiply + relinearize_inplace   SEAL_HEVM.cpp:315-316 */
 void dc_ct_mul_relin(dc_context *ctx, uint64_t *dst, long dst_stride, const uint64_t *a, long a_stride, const uint64_t *b,
                      long b_stride, const uint64_t *relin_key, int ell, void *stream);
+/* Evaluator::multiply + relinearize_inplace [+ add_plain + multiply_plain by a constant polynomial] + rescale_to_next, limb for limb;
+ * dst at level ell-1.  add_plain: [>= ell][N] NTT form or NULL.  mul_const: HOST array of ell residues (the constant polynomial's value
+ * modulo each prime) or NULL.  ell >= 2.  dst may be a or b; a may be b.  SEAL-layout contexts only.
+ * The rescale is folded into the multiply's key switch: ONE exact pass divides by P q_{ell-1} (five launches instead of seven, ell-1 forward
+ * transforms per polynomial instead of 2 ell-1) and every limb equals dc_ct_mul_relin [+ dc_ct_add_plain + dc_ct_mul_plain] + dc_ct_rescale.
+ * Launch shapes without a folded form (options ks_big_tiles, ks_fuse_mac, ks_fuse_mac_tiles) run that default sequence instead.  A
+ * grouped-digit context aborts with a message: its mod-down is an approximate base conversion.  Scratch is kept in the context. */
+void dc_ct_mul_relin_rescale(dc_context *ctx, uint64_t *dst, long dst_stride, const uint64_t *a, long a_stride, const uint64_t *b,
+                             long b_stride, const uint64_t *relin_key, const uint64_t *add_plain, const uint64_t *mul_const, int ell,
+                             void *stream);
 /* Evaluator::apply_galois_inplace: one hop of Evaluator::rotate_vector   SEAL_HEVM.cpp:273 */
 void dc_ct_rotate_hop(dc_context *ctx, uint64_t *dst, long dst_stride, const uint64_t *src, long src_stride,
                       uint32_t galois_elt, const uint64_t *galois_key, int ell, void *stream);

@@ -131,6 +131,10 @@ void hevm_last_run_stats(void *vm, int64_t *op_counts /*[11]*/, int64_t *keyswit
  * them.  With the option on, the hops of a plan step that read one source ciphertext share one decomposition; with it off, or under option
  * "plan" = 0, every hop computes its own and the two numbers are equal. */
 void hevm_last_run_hoist_stats(void *vm, int64_t *hops, int64_t *decompositions);
+/* option "ks_fold_rescale" (SEAL-layout keys, off by default): the items -- multiply-rescale pairs, once per stream -- that the last run()'s plan
+ * executed as ONE merged step, the rescale folded into the multiply's key switch.  Every limb equals the default
+ * path's; hevm_last_run_stats still counts a merged pair as one multiply and one rescale.  0 with the option off and under option "plan" = 0. */
+void hevm_last_run_fold_rescale_stats(void *vm, int64_t *pairs);
 /* options "hyb_lazy_sum" (grouped-digit mode) / "ks_lazy_sum" (SEAL-layout keys, with "ks_hoist"; both off by default): the rotate instructions
  * the last run()'s plan executed as lazy sums -- the accumulators of a group's key switches added in the raised basis, ONE division by P per
  * group.  The form is the same in both modes.  out = [n_0, op ...,
