@@ -59,23 +59,29 @@ __device__ __forceinline__ double reencoded_coeff_fixed(const u64 *__restrict__ 
     return round((crt_centered_fixed<ELL>(coef, g, N, mods, c) - crt_centered_fixed<ELL>(coef, N - g, N, mods, c)) * 0.5 * ratio);
 }
 
-// residue mod q of an integral double |x| < 2^120 (exact: at most 53 significant bits, shifted)
-__device__ __forceinline__ u64 residue_of_double(double x, const DModulus &M)
+// an integral double 0 <= a < 2^120 as the 128-bit integer h 2^64 + l (exact: at most 53 significant bits, shifted).  The one copy of
+// the step every "double -> residue" lift starts with: the encoder's, opcode 10's three, all followed by reduce128_any.
+__device__ __forceinline__ void split_integral_double(double a, u64 &h, u64 &l)
 {
-    const bool neg = x < 0.0;
-    const double a = fabs(x);
-    u64 l, h;
     if (a < 0x1p63) {
         l = (u64)a;
         h = 0;
     } else {
         int e;
-        const double fr = frexp(a, &e);
+        const double fr = frexp(a, &e); // a = fr * 2^e, fr in [0.5, 1)
         const u64 mant = (u64)ldexp(fr, 53);
-        const int sh = e - 53;
+        const int sh = e - 53; // 11 .. 67
         l = sh < 64 ? mant << sh : 0;
         h = sh < 64 ? mant >> (64 - sh) : mant << (sh - 64);
     }
+}
+
+// residue mod q of an integral double |x| < 2^120
+__device__ __forceinline__ u64 residue_of_double(double x, const DModulus &M)
+{
+    const bool neg = x < 0.0;
+    u64 l, h;
+    split_integral_double(fabs(x), h, l);
     const u64 r = reduce128_any(h, l, M);
     return (neg && r) ? M.q - r : r;
 }

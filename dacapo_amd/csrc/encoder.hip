@@ -6,6 +6,7 @@
 // host encoder's; only who executes them changes (5 894 plaintexts of ResNet-20: 3 s of host FFTs -> ~0.1 s).
 #pragma clang fp contract(off)
 #include "encoder.hpp"
+#include "crt_device.hpp"
 
 namespace dacapo {
 
@@ -64,17 +65,7 @@ __global__ __launch_bounds__(kEncThreads) void enc_round_lift_kernel(u64 *__rest
     }
     const bool neg = c < 0.0;
     u64 l, h;
-    if (a < 0x1p63) {
-        l = (u64)a;
-        h = 0;
-    } else { // exact: a is integral and has at most 53 significant bits
-        int e;
-        const double fr = frexp(a, &e);
-        const u64 mant = (u64)ldexp(fr, 53);
-        const int sh = e - 53;
-        l = sh < 64 ? mant << sh : 0;
-        h = sh < 64 ? mant >> (64 - sh) : mant << (sh - 64);
-    }
+    split_integral_double(a, h, l); // exact: a is integral and has at most 53 significant bits
     u64 *o = out + (size_t)blockIdx.y * level * N + j;
     for (int k = 0; k < level; k++) {
         const DModulus M = mods[prime_base + k];

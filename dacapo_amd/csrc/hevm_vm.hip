@@ -207,19 +207,8 @@ __global__ __launch_bounds__(kVmThreads) void decrypt_kernel(u64 *__restrict__ o
 __device__ inline void store_i128(u64 *lo, u64 *hi, size_t idx, double x)
 { // x is integral, |x| < 2^120
     const bool neg = x < 0.0;
-    const double a = fabs(x);
     u64 l, h;
-    if (a < 0x1p63) {
-        l = (u64)a;
-        h = 0;
-    } else {
-        int e;
-        const double fr = frexp(a, &e); // a = fr * 2^e, fr in [0.5, 1)
-        const u64 mant = (u64)ldexp(fr, 53);
-        const int sh = e - 53; // > 9
-        l = sh < 64 ? mant << sh : 0;
-        h = sh < 64 ? mant >> (64 - sh) : mant << (sh - 64);
-    }
+    split_integral_double(fabs(x), h, l);
     if (neg) {
         l = ~l + 1;
         h = ~h + (l == 0);
@@ -273,22 +262,12 @@ __device__ inline void store_residues(u64 *__restrict__ out, size_t idx, size_t 
                                       const DModulus *__restrict__ mods)
 { // x integral, |x| < 2^120: writes (flip ? -x : x) mod q_k for k < t
     const bool neg = (x < 0.0) != flip;
-    const double a = fabs(x);
     u64 l, h;
-    if (a < 0x1p63) {
-        l = (u64)a;
-        h = 0;
-    } else {
-        int e;
-        const double fr = frexp(a, &e);
-        const u64 mant = (u64)ldexp(fr, 53);
-        const int sh = e - 53;
-        l = sh < 64 ? mant << sh : 0;
-        h = sh < 64 ? mant >> (64 - sh) : mant << (sh - 64);
-    }
+    split_integral_double(fabs(x), h, l);
     for (int k = 0; k < t; k++) {
         const DModulus M = mods[k];
-        const u64 r = canon(reduce128_lazy(h, l, M.delta), M);
+        // (not reduce128_lazy alone: |x| reaches 2^119, beyond the 2^(2b+4) it takes for a prime narrower than 60 bits)
+        const u64 r = reduce128_any(h, l, M);
         out[(size_t)k * N + idx] = (neg && r) ? M.q - r : r;
     }
 }

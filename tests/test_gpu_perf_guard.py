@@ -3,7 +3,9 @@ shape has a parity test, this is the timing side).  With every option at its def
 rotation hop at 13 primes, config 3 (ct x ct + relinearise, N = 2^16, 24 + 1 primes) and one run() of the headline program -- and holds each to
 within 5 % of the figure committed for the round (tests/golden/perf_guard.json, written by THIS file's own measurement code on the round's
 final build: `python tests/test_gpu_perf_guard.py --record gpurun_out/perf_guard.json` on the GPU box).  Boxes are not identical: the device-to-device copy rate is measured first and the test is SKIPPED when it
-is more than 3 % off the box the committed figures came from -- a slower box is not a regression.  Faster than the committed figure never fails."""
+is more than 3 % BELOW that of the box the committed figures came from -- a slower box is not a regression.  A box that copies faster (boxes of
+the same model differ by 10 %) runs the checks against the same committed figures: it has no excuse to be slower.  Faster than the committed
+figure never fails."""
 import json
 import sys
 from pathlib import Path
@@ -47,8 +49,8 @@ def guard():
     for L in runner._option_libs():
         L.hevm_reset_options()
     gbs = _copy_gbs(ll)
-    if abs(gbs / g["copy_kernel_gbs"] - 1.0) > BOX_TOLERANCE:
-        pytest.skip(f"this box copies at {gbs:.0f} GB/s, the committed figures' box at {g['copy_kernel_gbs']:.0f}: more than 3 % apart")
+    if gbs / g["copy_kernel_gbs"] - 1.0 < -BOX_TOLERANCE:
+        pytest.skip(f"this box copies at {gbs:.0f} GB/s, the committed figures' box at {g['copy_kernel_gbs']:.0f}: more than 3 % slower")
     return g
 
 
