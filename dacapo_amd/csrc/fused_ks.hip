@@ -264,6 +264,118 @@ __global__ __launch_bounds__(kTileThreads) void f_dr_icols_lift_fcols_kernel(con
     }
 }
 
+// ---- zero-encryptions of a plan (HEVM::plan_zero_encrypt, option zenc_head = 1) -----------------------------------------------------------
+// rescale(pk_p * U + NTT(e_p)) over the primes 0..l, U = NTT(u), from U alone: the three kernels of a rescale (R1 - R3 above) with the
+// key's product formed in the first and the last one and the noise e_p -- small signed coefficients, one byte each, never transformed --
+// joining in the coefficient domain of the middle one:
+//   delta = iNTT_l(pk_{p,l} * U_l) + [e_p]_{q_l}     rho = [delta + floor(q_l/2)]_{q_l}     t_i = (rho mod q_i) - (floor(q_l/2) mod q_i)
+//   z_i   = q_l^-1 (pk_{p,i} * U_i - NTT_i(t_i - [e_p]_{q_i}))  =  q_l^-1 ((pk_{p,i} * U_i + NTT_i(e_p)) - NTT_i(t_i))      exactly, mod q_i
+// A ROWS tile's first inverse / last forward pass gives a thread 2^LOGE CONSECUTIVE coefficients: the loaders and the epilogue run on
+// 16-byte vectors.  z = b*2 + p in the first two kernels, (b*2 + p)*l + i in the last.
+template <int K, int LOGE>
+__global__ __launch_bounds__(kTileThreads) void f_irows_zenc_kernel(const ZencItem *__restrict__ items, const u64 *__restrict__ pk, long pk_ps,
+                                                                     int l, u64 *__restrict__ out, const DModulus *__restrict__ mods,
+                                                                     const u64 *__restrict__ itw, int logN)
+{
+    __shared__ __attribute__((aligned(16))) u64 lds[TileGeo<LOGE>::LDS_ELEMS];
+    constexpr int E = 1 << LOGE;
+    const int z = blockIdx.y;
+    const size_t N = (size_t)1 << logN;
+    const DModulus M = mods[l];
+    u64 *o = out + (size_t)z * N;
+    const int g0 = tile_gidx<K, LOGE, false>(num_passes<LOGE>(K) - 1, logN, blockIdx.x, 0);
+    const u64 *u = items[z >> 1].u + (size_t)l * N + g0, *k = pk + (z & 1) * pk_ps + (size_t)l * N + g0;
+    u64 x[E];
+#pragma unroll
+    for (int j = 0; j < E; j += 2) {
+        const u64x2 a = *reinterpret_cast<const u64x2 *>(u + j), b = *reinterpret_cast<const u64x2 *>(k + j);
+        x[j] = mulmod(a.x, b.x, M), x[j + 1] = mulmod(a.y, b.y, M);
+    }
+    auto nold = [](int) -> u64 { return 0; };
+    ntt_tile_x<K, LOGE, false, true, false, true, false>(x, M, itw + ((size_t)l << logN), logN, blockIdx.x, nold,
+                                                         [=](int gi, u64 v) { o[gi] = v; }, lds);
+}
+
+// the middle kernel: f_dr_icols_lift_fcols_kernel with the noise.  An inverse COLS tile ends with pass 0: register r holds coefficient
+// tile_gidx<K, LOGE, true>(0, ..., r), which is where this thread's bytes of e are.
+template <int K, int LOGE, bool MERGE>
+__global__ __launch_bounds__(kTileThreads) void f_dr_noise_icols_lift_fcols_kernel(const u64 *__restrict__ last, long last_stride,
+                                                                                    u64 *__restrict__ tmp, int cnt, int l, int Kp,
+                                                                                    const DModulus *__restrict__ mods,
+                                                                                    const u64 *__restrict__ half_mod,
+                                                                                    const u64 *__restrict__ tw, const u64 *__restrict__ itw,
+                                                                                    int logN, const u64 *__restrict__ tw2,
+                                                                                    const signed char *__restrict__ noise)
+{
+    __shared__ __attribute__((aligned(16))) u64 lds[TileGeo<LOGE>::LDS_ELEMS];
+    const int z = blockIdx.y, bp = MERGE ? z : z / cnt;
+    const size_t N = (size_t)1 << logN;
+    const u64 *in = last + (long)bp * last_stride;
+    const signed char *ep = noise + (size_t)bp * N;
+    u64 x[1 << LOGE];
+    int e[1 << LOGE];
+#pragma unroll
+    for (int r = 0; r < (1 << LOGE); r++) e[r] = ep[tile_gidx<K, LOGE, true>(0, logN, blockIdx.x, r)];
+    auto nost = [](int, u64) {};
+    ntt_tile_x<K, LOGE, true, true, true, false, true>(
+        x, mods[l], itw + ((size_t)l << logN), logN, blockIdx.x, [=](int g) { return in[g]; }, nost, lds);
+    const u64 ql = mods[l].q, half = ql >> 1;
+#pragma unroll
+    for (int r = 0; r < (1 << LOGE); r++) { // + [e]_{q_l}, then + floor(q_l / 2), both mod q_l
+        u64 y = x[r] + (e[r] < 0 ? ql - (u64)(-e[r]) : (u64)e[r]);
+        y = y >= ql ? y - ql : y;
+        y += half;
+        x[r] = y >= ql ? y - ql : y;
+    }
+    auto nold = [](int) -> u64 { return 0; };
+    for (int i = MERGE ? 0 : z % cnt; i < (MERGE ? cnt : z % cnt + 1); i++) {
+        u64 *out = tmp + ((size_t)bp * cnt + i) * N;
+        const DModulus Mi = mods[i];
+        const u64 qi = Mi.q, neg_half = qi - half_mod[(size_t)l * Kp + i];
+        u64 y[1 << LOGE];
+#pragma unroll
+        for (int r = 0; r < (1 << LOGE); r++) { // ... reduced into q_i, - floor(q_l / 2) mod q_i, - [e]_{q_i}
+            u64 v = recanon(x[r], Mi) + neg_half;
+            v = v >= qi ? v - qi : v;
+            v += e[r] > 0 ? qi - (u64)e[r] : (u64)(-e[r]);
+            y[r] = v >= qi ? v - qi : v;
+        }
+        __syncthreads();
+        ntt_tile_fcols<K, LOGE, false, true, false>(
+            y, Mi, tw + ((size_t)i << logN), tw2 ? tw2 + ((size_t)i << (K + 1)) : nullptr, logN, blockIdx.x, nold, [=](int g, u64 v) { out[g] = v; }, lds);
+    }
+}
+
+template <int K, int LOGE>
+__global__ __launch_bounds__(kTileThreads) void f_frows_zenc_final_kernel(const u64 *__restrict__ tmp, const ZencItem *__restrict__ items,
+                                                                           const u64 *__restrict__ pk, long pk_ps, int l, int Kp,
+                                                                           const DModulus *__restrict__ mods,
+                                                                           const u64 *__restrict__ inv_last, const u64 *__restrict__ tw,
+                                                                           int logN)
+{
+    __shared__ __attribute__((aligned(16))) u64 lds[TileGeo<LOGE>::LDS_ELEMS];
+    constexpr int E = 1 << LOGE;
+    const int z = blockIdx.y, i = z % l, bp = z / l, b = bp >> 1, p = bp & 1;
+    const size_t N = (size_t)1 << logN;
+    const DModulus M = mods[i];
+    const u64 inv = inv_last[(size_t)l * Kp + i];
+    const u64 *in = tmp + (size_t)z * N;
+    const ZencItem it = items[b];
+    const int g0 = tile_gidx<K, LOGE, false>(num_passes<LOGE>(K) - 1, logN, blockIdx.x, 0);
+    const u64 *u = it.u + (size_t)i * N + g0, *k = pk + p * pk_ps + (size_t)i * N + g0;
+    u64 *o = it.dst.limb(p, i, N) + g0;
+    u64 v[E];
+    auto nost = [](int, u64) {};
+    ntt_tile_x<K, LOGE, false, false, true, false, true>(v, M, tw + ((size_t)i << logN), logN, blockIdx.x, [=](int gi) { return in[gi]; }, nost, lds);
+#pragma unroll
+    for (int j = 0; j < E; j += 2) {
+        const u64x2 a = *reinterpret_cast<const u64x2 *>(u + j), c = *reinterpret_cast<const u64x2 *>(k + j);
+        u64x2 r;
+        r.x = mulmod(submod(mulmod(a.x, c.x, M), v[j], M.q), inv, M), r.y = mulmod(submod(mulmod(a.y, c.y, M), v[j + 1], M.q), inv, M);
+        *reinterpret_cast<u64x2 *>(o + j) = r;
+    }
+}
+
 // L6 + R2 of a multiply whose rescale is folded in (option ks_fold_rescale): z = bp*cnt + i, cnt = l - 1 kept limbs.  Both dropped limbs of
 // accumulator bp -- the special prime's (slot l of acc) and row l - 1's, which carries P (d + A) (f_ks_frows_mac_kernel, FOLD) -- finish their
 // inverse transforms here, and per coefficient
@@ -1120,6 +1232,23 @@ void f_dr_icols_lift_fcols(const Context &c, const u64 *last, long last_stride, 
 {
     DC_MERGED_LAUNCH(polys * cnt, polys, cnt, f_dr_icols_lift_fcols_kernel, last, last_stride, tmp, cnt, l, c.K, c.d_mods, c.d_half_mod, c.d_tw,
                      c.d_itw, c.logN, c.twc2())
+}
+
+void f_irows_zenc(const Context &c, const ZencItem *items, const u64 *pk, int l, u64 *out, int B, hipStream_t s)
+{
+    DC_GEO_SWITCH(c.k2, 2 * B, DC_LAUNCH((f_irows_zenc_kernel<KK, LE>), grid, dim3(kTileThreads), 0, s, items, pk, (long)c.K * (long)c.N, l, out,
+                                                  c.d_mods, c.d_itw, c.logN));
+}
+void f_dr_noise_icols_lift_fcols(const Context &c, const u64 *last, long last_stride, u64 *tmp, int polys, int cnt, int l,
+                                 const signed char *noise, hipStream_t s)
+{
+    DC_MERGED_LAUNCH(polys * cnt, polys, cnt, f_dr_noise_icols_lift_fcols_kernel, last, last_stride, tmp, cnt, l, c.K, c.d_mods, c.d_half_mod,
+                     c.d_tw, c.d_itw, c.logN, c.twc2(), noise)
+}
+void f_frows_zenc_final(const Context &c, const u64 *tmp, const ZencItem *items, const u64 *pk, int B, int l, hipStream_t s)
+{
+    DC_GEO_SWITCH(c.k2, 2 * B * l, DC_LAUNCH((f_frows_zenc_final_kernel<KK, LE>), grid, dim3(kTileThreads), 0, s, tmp, items, pk,
+                                                      (long)c.K * (long)c.N, l, c.K, c.d_mods, c.d_inv_last, c.d_tw, c.logN));
 }
 
 void f_dr2_icols_lift_fcols(const Context &c, const u64 *acc, const MulRsItem *items, u64 *tmp, int B, int ell, hipStream_t s)

@@ -108,6 +108,31 @@ __global__ __launch_bounds__(kVmThreads) void sample_enc_batch_kernel(u64 *__res
     for (int i = 0; i < cnt; i++) store_small8(out + (((size_t)b * 3 + z) * cnt + i) * N + blk * kRngCoefs, v, mods[i].q);
 }
 
+// The same draws for the zero-encryptions of a plan (plan_zero_encrypt, option zenc_head = 1): u[b] lifted to `cnt` primes as above, e0 and
+// e1 ONCE each, as the signed values themselves (|e| <= 21: one byte per coefficient, e[b][2][N]) -- they are never transformed.
+// grid = (N/2048, 3B)
+__global__ __launch_bounds__(kVmThreads) void sample_zenc_batch_kernel(u64 *__restrict__ u, signed char *__restrict__ e, size_t N, int cnt,
+                                                                        ChaChaKey key, u64 object0, const DModulus *__restrict__ mods,
+                                                                        const u64 *__restrict__ epoch)
+{
+    const int b = blockIdx.y / 3, z = blockIdx.y % 3;
+    const size_t blk = (size_t)blockIdx.x * kVmThreads + threadIdx.x;
+    u64 w[kRngCoefs];
+    rng_words8(key, object0 + (u64)b, blk, *epoch, 0, RNG_ENC_U + (u32)z, w);
+    int v[kRngCoefs];
+#pragma unroll
+    for (int k = 0; k < kRngCoefs; k++) v[k] = z ? rng_cbd(w[k]) : rng_ternary(w[k]);
+    if (z == 0) {
+        for (int i = 0; i < cnt; i++) store_small8(u + ((size_t)b * cnt + i) * N + blk * kRngCoefs, v, mods[i].q);
+    } else {
+        static_assert(kRngCoefs == 8, "one 8-byte store per thread");
+        u64 packed = 0;
+#pragma unroll
+        for (int k = 0; k < kRngCoefs; k++) packed |= (u64)(unsigned char)(signed char)v[k] << (8 * k);
+        *reinterpret_cast<u64 *>(e + ((size_t)b * 2 + (z - 1)) * N + blk * kRngCoefs) = packed;
+    }
+}
+
 // test hook: `blocks` consecutive ChaCha20 blocks starting at `counter` (16 words each)
 __global__ void chacha_blocks_kernel(u32 *__restrict__ out, ChaChaKey key, u64 counter, u64 nonce, int blocks)
 {
@@ -454,6 +479,7 @@ void HEVM::init_context(int logN, int K, const u64 *primes, int dir_ksp, int dir
                         "is an approximate base conversion, and dividing by P q in one exact pass does not reproduce it\n", ksp, alpha);
         abort();
     }
+    zenc_head = option(OPT_ZENC_HEAD) != 0;
     // prime_bits = b (45..60; the generic-width build only): the chain CoeffModulus::Create(N, {b, b, ...}) instead of the reference's
     // 60-bit one (SEAL_HEVM.cpp:48-53) -- e.g. 51 for rescale primes of the HEaaN configuration's width
     const int bits = (int)option(OPT_PRIME_BITS);
@@ -1798,7 +1824,7 @@ void HEVM::boot_item(CtView src, int ell, double src_scale, hevm_ctxt &dst, int 
 }
 
 // batched opcode 10, randomness half: zero-encryptions of items [first, first+B) of the plan's boot table (all with target
-// level t) into their zenc slots.  7 launches whatever B is.
+// level t) into their zenc slots.  At most 7 launches whatever B is (option zenc_head = 0: Encryptor::encrypt's sequence, batched).
 void HEVM::plan_zero_encrypt(int first, int B, int t, hipStream_t s)
 {
     Context &c = *ctx;
@@ -1809,6 +1835,23 @@ void HEVM::plan_zero_encrypt(int first, int B, int t, hipStream_t s)
         abort();
     }
     Plan &P = plan;
+    if (zenc_head) {
+        // The same limbs from 3t + 3 transforms per item instead of 5t + 5 (transforms are linear, every step exact mod q_i).  With D = t
+        // the dropped prime and U_i = NTT_i([u]_{q_i}):
+        //   delta_p = iNTT_D(pk_{p,D} * U_D) + [e_p]_{q_D}             rho_p = [delta_p + floor(q_D/2)]_{q_D}
+        //   t_{p,i} = (rho_p mod q_i) - (floor(q_D/2) mod q_i)          z_{p,i} = q_D^-1 (pk_{p,i} * U_i - NTT_i(t_{p,i} - [e_p]_{q_i}))
+        // Only u is lifted and transformed; e0, e1 are stored once, as bytes, and join in the coefficient domain of the rescale's middle
+        // kernel; the products with the key are formed in the loader of its first and the epilogue of its last kernel (fused_ks.hip,
+        // "zero-encryptions").  5 or 6 launches whatever B is.
+        DC_LAUNCH(sample_zenc_batch_kernel, dim3((unsigned)(N / (kRngCoefs * kVmThreads)), (unsigned)(3 * B)), dim3(kVmThreads), 0, s,
+                           P.boot_ue, P.boot_e, N, cnt, rng.secret, ((u64)1 << 32) + (u64)first, c.d_mods, d_epoch);
+        launch_ntt(c, false, P.boot_ue, (long)N, cnt * B, nullptr, 0, cnt, s);
+        const ZencItem *items = P.d_boot_zenc + first;
+        f_irows_zenc(c, items, keys.pk, t, P.ws[0].digits, B, s);
+        f_dr_noise_icols_lift_fcols(c, P.ws[0].digits, (long)N, P.ws[0].tmp, 2 * B, t, t, P.boot_e, s);
+        f_frows_zenc_final(c, P.ws[0].tmp, items, keys.pk, B, t, s);
+        return;
+    }
     DC_LAUNCH(sample_enc_batch_kernel, dim3((unsigned)(N / (kRngCoefs * kVmThreads)), (unsigned)(3 * B)), dim3(kVmThreads), 0, s,
                        P.boot_ue, N, cnt, rng.secret, ((u64)1 << 32) + (u64)first, c.d_mods, d_epoch);
     launch_ntt(c, false, P.boot_ue, (long)N, 3 * cnt * B, nullptr, 0, cnt, s);

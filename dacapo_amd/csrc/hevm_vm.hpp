@@ -227,9 +227,11 @@ class HEVM {
         size_t n_fused = 0;
         // opcode 10: item table, the divide-and-round items of the zero-encryptions, the zero-encryption arena and scratch
         BootItem *d_boot = nullptr;
-        RsItem *d_boot_rs = nullptr;
+        RsItem *d_boot_rs = nullptr;         // (option zenc_head = 0)
+        ZencItem *d_boot_zenc = nullptr;     // (option zenc_head = 1)
         size_t zenc_bytes = 0;
         u64 *zenc = nullptr, *boot_ue = nullptr, *boot_tmp = nullptr, *boot_pt[2] = { nullptr, nullptr }, *boot_ptx[2] = { nullptr, nullptr };
+        signed char *boot_e = nullptr; // option zenc_head = 1: the noise polynomials of a chunk, [chunk][2][N] bytes at the end of boot_ue (which then holds u alone; no boot_tmp)
         struct BootChunk { int first, count, target; };
         std::vector<BootChunk> boot_chunks; // zero-encryption launches at the start of every run
         BatchWs ws[2]; // per lane
@@ -280,6 +282,11 @@ class HEVM {
     // option ks_fold_rescale = 1 (SEAL-layout keys): a multiply and the rescale that alone reads it run as one step
     // (plan_exec.hip section 4; plan.hpp b_mul_relin_rescale).  Every limb equals the default path's.
     bool ks_fold_rescale = false;
+    // option zenc_head = 1: the zero-encryptions at the start of a plan's run() transform only u (plan_zero_encrypt).  Every limb equals
+    // zenc_head = 0's.  zenc_chunk_hook (hooks build, test_hooks.hip: HEVM_TEST_ZENC_CHUNK): items per chunk of that head instead of kZencChunk, 0 = unset
+    bool zenc_head = true;
+    static constexpr int kZencChunk = 64;  // items per chunk of that head (measured: profiles/zenc_head_ab.txt)
+    int zenc_chunk_hook = 0;
     KsItem *d_hoist_items = nullptr; // the loop's (plan = 0) two-entry item table: the hop and its source
     void rotate_hop_vm(CtView dst, CtView src, u32 elt, const u64 *key, int ell);
     bool chain_fusion = true; // option chain_fusion = 0: every step runs all of its own launches

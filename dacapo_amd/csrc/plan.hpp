@@ -43,6 +43,10 @@ struct RsItem {   // dst = rescale_to_next(expr), expr = ((src | sum of `count` 
     const u64 *add = nullptr;          // plaintext [level][N] added to c0 (a single-use addcp folded in), or null
     const u64 *mul = nullptr;          // plaintext multiplying both polys (a single-use mulcp folded in), or null
 };
+struct ZencItem { // dst = rescale_to_next(pk * u + e): one zero-encryption of a plan (hevm_vm.hip plan_zero_encrypt, option zenc_head = 1)
+    const u64 *u;  // NTT(u) over the target's primes and the dropped one, [t + 1][N]; pk and e are the launch's (one key, e by position)
+    CtView dst;
+};
 struct EwItem {   // dst = a (op) b ; plaintext operand: b.p = limbs, b.poly_stride = 0
     CtView dst, a, b;
 };
@@ -181,6 +185,14 @@ void f_boot_reencode_fcols(const Context &c, const u64 *pt, u64 *ptx, const Boot
 void f_frows_boot_final(const Context &c, const u64 *ptx, const BootItem *items, int B, int t, hipStream_t s);
 void f_ks_icols_lift_fcols(const Context &c, const u64 *digits, u64 *ext, int B, int ell, hipStream_t s);
 void f_dr_icols_lift_fcols(const Context &c, const u64 *last, long last_stride, u64 *tmp, int polys, int cnt, int l, hipStream_t s);
+// The divide-and-round of B zero-encryptions pk_p * NTT(u_b) + NTT(e_{b,p}) by prime l, from NTT(u) alone (fused_ks.hip, "zero-encryptions"):
+// inverse ROWS phase of pk_{p,l} * NTT(u_b)_l -> out[B][2][N]; the middle kernel, which adds [e]_{q_l} after the inverse COLS phase and
+// subtracts [e]_{q_i} from each lifted polynomial before its forward COLS phase (noise[B][2][N], one signed byte per coefficient); the
+// last ROWS phase with pk_{p,i} * NTT(u_b)_i formed in its epilogue, written to the items' destinations.  pk: [2][K][N], NTT form.
+void f_irows_zenc(const Context &c, const ZencItem *items, const u64 *pk, int l, u64 *out, int B, hipStream_t s);
+void f_dr_noise_icols_lift_fcols(const Context &c, const u64 *last, long last_stride, u64 *tmp, int polys, int cnt, int l,
+                                 const signed char *noise, hipStream_t s);
+void f_frows_zenc_final(const Context &c, const u64 *tmp, const ZencItem *items, const u64 *pk, int B, int l, hipStream_t s);
 // L3 + L4 + L5 fused (small batches): second NTT phase of the lifted digits, inner products with the key, first inverse phase of
 // the special-prime accumulators.  mode 0 rotation (items[b].key, operand through the Galois permutation) / 1 relinearisation
 // fold_base (rotations): the accumulators of the data primes leave with P galois(c0) added, and f_frows_final is told so (base_folded)

@@ -41,10 +41,10 @@ void HEVM::build_plan()
     if (P.d_cont_other) (void)vm_free(P.d_cont_other), P.d_cont_other = nullptr;
     if (P.d_mulrs) (void)vm_free(P.d_mulrs), P.d_mulrs = nullptr;
     for (void *p : { (void *)P.d_ks, (void *)P.d_mul, (void *)P.d_rs, (void *)P.d_ew, (void *)P.d_sum, (void *)P.d_sum_srcs, (void *)P.d_sumg, (void *)P.d_sumg_srcs, (void *)P.d_boot,
-                     (void *)P.d_boot_rs, (void *)P.zenc, (void *)P.boot_ue, (void *)P.boot_tmp, (void *)P.boot_pt[0], (void *)P.boot_ptx[0],
+                     (void *)P.d_boot_rs, (void *)P.d_boot_zenc, (void *)P.zenc, (void *)P.boot_ue, (void *)P.boot_tmp, (void *)P.boot_pt[0], (void *)P.boot_ptx[0],
                      (void *)P.boot_pt[1], (void *)P.boot_ptx[1] })
         if (p) (void)vm_free(p);
-    P.d_boot = nullptr, P.d_boot_rs = nullptr, P.zenc = P.boot_ue = P.boot_tmp = nullptr;
+    P.d_boot = nullptr, P.d_boot_rs = nullptr, P.d_boot_zenc = nullptr, P.zenc = P.boot_ue = P.boot_tmp = nullptr, P.boot_e = nullptr;
     P.boot_pt[0] = P.boot_pt[1] = P.boot_ptx[0] = P.boot_ptx[1] = nullptr;
     P.boot_chunks.clear();
     if (P.graph_exec) (void)hipGraphExecDestroy(P.graph_exec);
@@ -1088,16 +1088,23 @@ void HEVM::build_plan()
         std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
             return O[(size_t)h_boot_pops[(size_t)a].first].target_level < O[(size_t)h_boot_pops[(size_t)b].first].target_level;
         });
-        const size_t bc = std::min<size_t>(nb, (size_t)std::max(max_batch, 1));
+        // zenc_head = 1 samples a third of the limbs per item and keeps no product buffer, so its chunks are its own (kZencChunk), not max_batch's
+        const size_t bc = std::min<size_t>(nb, zenc_head ? (size_t)(zenc_chunk_hook > 0 ? zenc_chunk_hook : kZencChunk) : (size_t)std::max(max_batch, 1));
         const size_t cmax = (size_t)boot_tmax + 1;
-        DC_HIP_CHECK(vm_malloc(&P.boot_ue, bc * 3 * cmax * N * sizeof(u64)));
-        DC_HIP_CHECK(vm_malloc(&P.boot_tmp, bc * 2 * cmax * N * sizeof(u64)));
+        if (zenc_head) { // u [bc][cmax][N] words, then e0, e1 [bc][2][N] bytes
+            DC_HIP_CHECK(vm_malloc(&P.boot_ue, bc * cmax * N * sizeof(u64) + bc * 2 * N));
+            P.boot_e = reinterpret_cast<signed char *>(P.boot_ue + bc * cmax * N);
+        } else {
+            DC_HIP_CHECK(vm_malloc(&P.boot_ue, bc * 3 * cmax * N * sizeof(u64)));
+            DC_HIP_CHECK(vm_malloc(&P.boot_tmp, bc * 2 * cmax * N * sizeof(u64)));
+        }
         for (int ln = 0; ln < plan_lanes; ln++) {
             DC_HIP_CHECK(vm_malloc(&P.boot_pt[ln], std::max<size_t>(need_bpt, 1) * N * sizeof(u64)));
             DC_HIP_CHECK(vm_malloc(&P.boot_ptx[ln], std::max<size_t>(need_bptx, 1) * N * sizeof(u64)));
         }
         std::vector<BootItem> h_boot(nb);
-        std::vector<RsItem> h_brs(nb);
+        std::vector<RsItem> h_brs(zenc_head ? 0 : nb);
+        std::vector<ZencItem> h_bz(zenc_head ? nb : 0);
         for (size_t k = 0; k < nb;) { // chunks over the sorted order
             const int t = O[(size_t)h_boot_pops[(size_t)order[k]].first].target_level;
             size_t e = k;
@@ -1106,10 +1113,13 @@ void HEVM::build_plan()
             for (size_t j = k; j < e; j++) { // sorted position j <-> item order[j]; zenc slot = item index
                 const size_t item = (size_t)order[j];
                 u64 *z = P.zenc + item * slot;
-                h_brs[j] = RsItem{ CtView{ P.boot_tmp + (j - k) * 2 * (size_t)(t + 1) * N, (long)(t + 1) * (long)N }, CtView{ z, (long)t * (long)N } };
+                if (zenc_head)
+                    h_bz[j] = ZencItem{ P.boot_ue + (j - k) * (size_t)(t + 1) * N, CtView{ z, (long)t * (long)N } };
+                else
+                    h_brs[j] = RsItem{ CtView{ P.boot_tmp + (j - k) * 2 * (size_t)(t + 1) * N, (long)(t + 1) * (long)N }, CtView{ z, (long)t * (long)N } };
             }
-            need_d = std::max(need_d, (e - k) * 2), need_m = std::max(need_m, (e - k) * 2 * (size_t)(t + 1));
-            P.launches += 7;
+            need_d = std::max(need_d, (e - k) * 2), need_m = std::max(need_m, (e - k) * 2 * (size_t)(zenc_head ? t : t + 1));
+            P.launches += zenc_head ? 6 : 7; // (the transform of a chunk is one launch or two)
             k = e;
         }
         for (size_t item = 0; item < nb; item++) {
@@ -1135,7 +1145,7 @@ void HEVM::build_plan()
             if (p.rs_mul >= 0) bi.mul = plains.at((size_t)p.rs_mul).d;
             h_boot[item] = bi;
         }
-        P.d_boot = upload(h_boot), P.d_boot_rs = upload(h_brs);
+        P.d_boot = upload(h_boot), P.d_boot_rs = upload(h_brs), P.d_boot_zenc = upload(h_bz);
     }
     P.d_mulrs = upload(h_mulrs);
     P.d_ks = upload(h_ks), P.d_mul = upload(h_mul), P.d_rs = upload(h_rs), P.d_ew = upload(h_ew), P.d_sum = upload(h_sum);

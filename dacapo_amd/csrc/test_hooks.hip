@@ -4,6 +4,7 @@
 //   hevm_init_seeded / hevm_init_seeded_primes   every key expanded from a 64-bit seed: reproducible, hence NOT secret
 //   hevm_secret_key                              device pointer to the secret key
 //   hevm_test_zero_encryption                    every encryption of zero becomes (0, 0)
+// (and, no symbol: HEVM_TEST_ZENC_CHUNK in the environment sizes the zero-encryption chunks of the seeded VMs created under it)
 // tests/ run on the hooks build (the same objects + this file); bench.py, __graft_entry__.smoke() and INTEGRATION.md use the release build.
 #define DC_TEST_HOOKS 1 // include/hevm_abi.h declares the hooks (with default visibility) only under this macro
 #include "hevm_vm.hpp"
@@ -12,6 +13,7 @@
 #include "options.hpp"
 
 #include <stdio.h>
+#include <stdlib.h>
 
 namespace dacapo {
 
@@ -29,6 +31,15 @@ RngKeys rng_keys_from_test_seed(uint64_t seed)
         w[i] = (uint32_t)x, w[i + 1] = (uint32_t)(x >> 32);
     }
     return k;
+}
+
+// Items per chunk of the zero-encryption head (option zenc_head = 1) of the seeded VMs created while the environment variable
+// HEVM_TEST_ZENC_CHUNK is set: a test reaches the chunk boundaries with a handful of opcode-10 items, the measurement sweeps the size.
+// Not an option: the release build has one size (hevm_vm.hpp kZencChunk).
+static void apply_test_zenc_chunk(HEVM *vm)
+{
+    const char *v = getenv("HEVM_TEST_ZENC_CHUNK");
+    if (v && atoi(v) > 0) vm->zenc_chunk_hook = atoi(v);
 }
 
 } // namespace dacapo
@@ -49,6 +60,7 @@ void *hevm_init_seeded(int logN, int num_primes, uint64_t seed)
     auto vm = new HEVM();
     vm->init_context(logN > 0 ? logN : dl, num_primes > 0 ? num_primes : dk, nullptr);
     vm->generate_keys(dacapo::rng_keys_from_test_seed(seed), true, true, true); // reproducible and therefore insecure
+    dacapo::apply_test_zenc_chunk(vm);
     return vm;
 }
 void *hevm_init_seeded_primes(int logN, const uint64_t *primes, int num_primes, uint64_t seed)
@@ -56,6 +68,7 @@ void *hevm_init_seeded_primes(int logN, const uint64_t *primes, int num_primes, 
     auto vm = new HEVM();
     vm->init_context(logN, num_primes, primes);
     vm->generate_keys(dacapo::rng_keys_from_test_seed(seed), true, true, true);
+    dacapo::apply_test_zenc_chunk(vm);
     return vm;
 }
 const uint64_t *hevm_secret_key(void *vm) { return V(vm)->keys.sk; }

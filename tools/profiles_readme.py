@@ -231,6 +231,7 @@ rows = [bench_row6("r06"), traffic_row("r06"), step_row("r06"), valu_row("r06"),
         "| `r06_hybrid_ks_kernels.txt`, `r06_boot_kernel_bytes.txt`, `r06_per_op.json`, `r06_per_op_kernel_stats.csv`, `r06_lowering_sweep.txt`, `r06_per_op_sweep.txt`, `r06_chain_latency.txt`, `r06_profiled_SEAL_MI355X.json` | as in round 5 on this build | see round 5's rows |"]
 rows.append("| `ks_hoist_ab.txt` | hoisted rotations on SEAL-layout keys (option `ks_hoist`, after round 6): `dc_ct_rotate_hoisted` for r = 1, 2, 4, 8 hops of one source against r × `dc_ct_rotate_hop` under device events at N = 2^15 / 13 primes and N = 2^16 / 24 primes, and `run()` of the headline and of its 13-prime lowering with the option off and on: time, hops, decompositions, rms against the torch logits; which programs gain is stated in the file | `python tools/legs/ks_hoist_ab.py --out profiles/ks_hoist_ab.txt` |")
 rows.append("| `ks_lazy_sum_ab.txt` | lazy sums on SEAL-layout keys (option `ks_lazy_sum` with `ks_hoist`): `run()` of the headline and of its 13-prime lowering under the default options, `ks_hoist`, and `ks_hoist` with `ks_lazy_sum` = 1 and 2: time, groups and members, hops, decompositions, rms against the torch logits | `python tools/legs/ks_lazy_sum_ab.py --out profiles/ks_lazy_sum_ab.txt` |")
+rows.append("| `zenc_head_ab.txt` | the zero-encryption head of `run()` (option `zenc_head`, `HEVM::plan_zero_encrypt`): the head's own duration and its kernels on the parent commit and under both values (kernel traces of plain `bench.py` runs, `tools/summarize/zenc_head.py`), `run()` of the headline on three VMs with the option 0, 1, 0 (0/0 spread beside the difference), the chunk-size sweep 64 / 128 / 192 / 256 on the hooks build, the head's scratch under both values, `bench.py`'s `ms_per_step` on the parent commit and on the branch on one box, and the compile-time VGPR / LDS / scratch figures of the new kernels | `python tools/legs/zenc_head_ab.py --out profiles/zenc_head_ab.txt`; `DACAPO_AMD_HOOKS=1 python tools/legs/zenc_head_ab.py --sweep --out profiles/zenc_head_ab.txt` |")
 rows.append("| `ks_fold_rescale_ab.txt` | a rescale folded into the multiply's key switch (option `ks_fold_rescale`, `dc_ct_mul_relin_rescale`): `dc_ct_mul_relin` + `dc_ct_rescale` against the one call under device events at N = 2^15 / 2, 3, 5, 13 primes and N = 2^16 / 24 primes, `run()` of the headline and of its 13-prime lowering with the option off, on, off (off/off spread beside the difference), pair counts, and the compile-time VGPR / LDS / scratch figures of the new kernels | `python tools/legs/ks_fold_rescale_ab.py --out profiles/ks_fold_rescale_ab.txt` |")
 rows.append("| `ks_mac_regs.txt` | compile-time figures, not runs: VGPRs, SGPRs, spills, scratch and LDS of `f_ks_gmac_kernel`, `f_ks_gsum_kernel`, `hyb_mac_kernel` and `hyb_mac_group_kernel` before and after their shared pieces moved to `ks_mac.hpp` / `galois.hpp`, both builds, with `identical` / `differs` per instantiation, and which pieces were left written out because of what they cost | `hipcc -S --cuda-device-only` of parent and branch, `python tools/experiments/asm_compare.py <parent dir> <branch dir> --table '<regex>'` |")
 print("\n".join(r for r in rows if r))
