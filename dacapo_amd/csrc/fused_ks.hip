@@ -151,8 +151,9 @@ struct SrcDecrypt { // limb z of c0 + c1*s  (Decryptor::decrypt fused into the f
     }
 };
 
+template <class Item> // MulItem, or MulRsItem (a multiply with its rescale folded in)
 struct SrcTensorC2 { // limb z = b*ell + i of a1*b1, the c2 of item b's tensor product (ckks_multiply) -- never materialised
-    const MulItem *items;
+    const Item *items;
     const DModulus *mods;
     int ell;
     __device__ int prime(int z) const { return z % ell; }
@@ -160,20 +161,7 @@ struct SrcTensorC2 { // limb z = b*ell + i of a1*b1, the c2 of item b's tensor p
     {
         const size_t N = (size_t)1 << logN;
         const int i = z % ell;
-        const MulItem &it = items[z / ell];
-        return mulmod(it.a.limb(1, i, N)[g], it.b.limb(1, i, N)[g], mods[i]);
-    }
-};
-struct SrcTensorC2Rs { // the same from a MulRsItem table (a multiply with its rescale folded in)
-    const MulRsItem *items;
-    const DModulus *mods;
-    int ell;
-    __device__ int prime(int z) const { return z % ell; }
-    __device__ u64 load(int z, int g, int logN) const
-    {
-        const size_t N = (size_t)1 << logN;
-        const int i = z % ell;
-        const MulRsItem &it = items[z / ell];
+        const Item &it = items[z / ell];
         return mulmod(it.a.limb(1, i, N)[g], it.b.limb(1, i, N)[g], mods[i]);
     }
 };
@@ -190,6 +178,10 @@ __global__ __launch_bounds__(kTileThreads) void f_irows_kernel(Src src, u64 *__r
         mods[p], itw + ((size_t)p << logN), logN, blockIdx.x, [=](int g) { return src.load(z, g, logN); },
         [=](int g, u64 v) { o[g] = v; }, lds);
 }
+
+// ---- L2 / L6 / R2: inverse COLS phase, base change, first forward phase -------------------------------------------------------------------
+// (Their target loop is written out in f_ks_, f_dr_ and f_dr2_icols_lift_fcols_kernel: as one function with a per-target functor every
+// listing changes, f_ks_icols_lift_fcols_kernel<7, 2, true> 89 -> 90 VGPRs; profiles/fused_tail_share.txt)
 
 // L2: z = (b*l + j)*l + e
 // MERGE (throughput-bound launches, grid.y = B*l): one workgroup finishes the iNTT of digit (b, j) ONCE and runs the base change + first
@@ -223,29 +215,54 @@ __global__ __launch_bounds__(kTileThreads) void f_ks_icols_lift_fcols_kernel(con
     }
 }
 
+// RNSTool::divide_and_round_q_last_ntt_inplace, coefficient-domain part: rho = x + floor(q_l / 2) mod q_l ...
+__device__ __forceinline__ u64 dr_round(u64 x, u64 half, u64 ql)
+{
+    const u64 y = x + half;
+    return y >= ql ? y - ql : y;
+}
+// ... reduced into q_i, - floor(q_l / 2) mod q_i  (neg_half = q_i - (floor(q_l / 2) mod q_i))
+__device__ __forceinline__ u64 dr_reduce(u64 rho, const DModulus &Mi, u64 neg_half)
+{
+    const u64 v = recanon(rho, Mi) + neg_half;
+    return v >= Mi.q ? v - Mi.q : v;
+}
+
 // L6 / R2: z = bp*cnt + i : finish the iNTT of the dropped limb bp (prime l), round, change base to prime i, first NTT phase
 // MERGE (grid.y = polys): the same sharing as in L2 -- the dropped limb's inverse phase once, then every target modulus in turn
-template <int K, int LOGE, bool MERGE>
+// NOISE: the middle kernel of a zero-encryption (f_irows_zenc_kernel below); `noise` is null otherwise.  An inverse COLS tile ends with
+// pass 0: register r holds coefficient tile_gidx<K, LOGE, true>(0, ..., r), which is where this thread's bytes of e are.
+template <int K, int LOGE, bool MERGE, bool NOISE>
 __global__ __launch_bounds__(kTileThreads) void f_dr_icols_lift_fcols_kernel(const u64 *__restrict__ last, long last_stride,
                                                                               u64 *__restrict__ tmp, int cnt, int l, int Kp,
                                                                               const DModulus *__restrict__ mods,
                                                                               const u64 *__restrict__ half_mod,
                                                                               const u64 *__restrict__ tw, const u64 *__restrict__ itw,
-                                                                              int logN, const u64 *__restrict__ tw2)
+                                                                              int logN, const u64 *__restrict__ tw2,
+                                                                              const signed char *__restrict__ noise)
 {
     __shared__ __attribute__((aligned(16))) u64 lds[TileGeo<LOGE>::LDS_ELEMS];
     const int z = blockIdx.y, bp = MERGE ? z : z / cnt;
     const size_t N = (size_t)1 << logN;
     const u64 *in = last + (long)bp * last_stride;
     u64 x[1 << LOGE];
+    int e[1 << LOGE];
+    if (NOISE) {
+        const signed char *ep = noise + (size_t)bp * N;
+#pragma unroll
+        for (int r = 0; r < (1 << LOGE); r++) e[r] = ep[tile_gidx<K, LOGE, true>(0, logN, blockIdx.x, r)];
+    }
     auto nost = [](int, u64) {};
     ntt_tile_x<K, LOGE, true, true, true, false, true>(
         x, mods[l], itw + ((size_t)l << logN), logN, blockIdx.x, [=](int g) { return in[g]; }, nost, lds);
     const u64 ql = mods[l].q, half = ql >> 1;
 #pragma unroll
-    for (int r = 0; r < (1 << LOGE); r++) { // RNSTool::divide_and_round_q_last_ntt_inplace, coefficient-domain part: + floor(q_l / 2) mod q_l
-        const u64 y = x[r] + half;
-        x[r] = y >= ql ? y - ql : y;
+    for (int r = 0; r < (1 << LOGE); r++) { // (+ [e]_{q_l},) then + floor(q_l / 2), both mod q_l
+        if (NOISE) {
+            const u64 y = x[r] + (e[r] < 0 ? ql - (u64)(-e[r]) : (u64)e[r]);
+            x[r] = y >= ql ? y - ql : y;
+        }
+        x[r] = dr_round(x[r], half, ql);
     }
     auto nold = [](int) -> u64 { return 0; };
     for (int i = MERGE ? 0 : z % cnt; i < (MERGE ? cnt : z % cnt + 1); i++) {
@@ -254,11 +271,15 @@ __global__ __launch_bounds__(kTileThreads) void f_dr_icols_lift_fcols_kernel(con
         const u64 qi = Mi.q, neg_half = qi - half_mod[(size_t)l * Kp + i];
         u64 y[1 << LOGE];
 #pragma unroll
-        for (int r = 0; r < (1 << LOGE); r++) { // ... reduced into q_i, - floor(q_l / 2) mod q_i
-            const u64 v = recanon(x[r], Mi) + neg_half;
-            y[r] = v >= qi ? v - qi : v;
+        for (int r = 0; r < (1 << LOGE); r++) { // (NOISE: - [e]_{q_i})
+            u64 v = dr_reduce(x[r], Mi, neg_half);
+            if (NOISE) {
+                v += e[r] > 0 ? qi - (u64)e[r] : (u64)(-e[r]);
+                v = v >= qi ? v - qi : v;
+            }
+            y[r] = v;
         }
-        __syncthreads();
+        __syncthreads(); // the previous tile's last LDS image has been read by everyone
         ntt_tile_fcols<K, LOGE, false, true, false>(
             y, Mi, tw + ((size_t)i << logN), tw2 ? tw2 + ((size_t)i << (K + 1)) : nullptr, logN, blockIdx.x, nold, [=](int g, u64 v) { out[g] = v; }, lds);
     }
@@ -296,56 +317,7 @@ __global__ __launch_bounds__(kTileThreads) void f_irows_zenc_kernel(const ZencIt
                                                          [=](int gi, u64 v) { o[gi] = v; }, lds);
 }
 
-// the middle kernel: f_dr_icols_lift_fcols_kernel with the noise.  An inverse COLS tile ends with pass 0: register r holds coefficient
-// tile_gidx<K, LOGE, true>(0, ..., r), which is where this thread's bytes of e are.
-template <int K, int LOGE, bool MERGE>
-__global__ __launch_bounds__(kTileThreads) void f_dr_noise_icols_lift_fcols_kernel(const u64 *__restrict__ last, long last_stride,
-                                                                                    u64 *__restrict__ tmp, int cnt, int l, int Kp,
-                                                                                    const DModulus *__restrict__ mods,
-                                                                                    const u64 *__restrict__ half_mod,
-                                                                                    const u64 *__restrict__ tw, const u64 *__restrict__ itw,
-                                                                                    int logN, const u64 *__restrict__ tw2,
-                                                                                    const signed char *__restrict__ noise)
-{
-    __shared__ __attribute__((aligned(16))) u64 lds[TileGeo<LOGE>::LDS_ELEMS];
-    const int z = blockIdx.y, bp = MERGE ? z : z / cnt;
-    const size_t N = (size_t)1 << logN;
-    const u64 *in = last + (long)bp * last_stride;
-    const signed char *ep = noise + (size_t)bp * N;
-    u64 x[1 << LOGE];
-    int e[1 << LOGE];
-#pragma unroll
-    for (int r = 0; r < (1 << LOGE); r++) e[r] = ep[tile_gidx<K, LOGE, true>(0, logN, blockIdx.x, r)];
-    auto nost = [](int, u64) {};
-    ntt_tile_x<K, LOGE, true, true, true, false, true>(
-        x, mods[l], itw + ((size_t)l << logN), logN, blockIdx.x, [=](int g) { return in[g]; }, nost, lds);
-    const u64 ql = mods[l].q, half = ql >> 1;
-#pragma unroll
-    for (int r = 0; r < (1 << LOGE); r++) { // + [e]_{q_l}, then + floor(q_l / 2), both mod q_l
-        u64 y = x[r] + (e[r] < 0 ? ql - (u64)(-e[r]) : (u64)e[r]);
-        y = y >= ql ? y - ql : y;
-        y += half;
-        x[r] = y >= ql ? y - ql : y;
-    }
-    auto nold = [](int) -> u64 { return 0; };
-    for (int i = MERGE ? 0 : z % cnt; i < (MERGE ? cnt : z % cnt + 1); i++) {
-        u64 *out = tmp + ((size_t)bp * cnt + i) * N;
-        const DModulus Mi = mods[i];
-        const u64 qi = Mi.q, neg_half = qi - half_mod[(size_t)l * Kp + i];
-        u64 y[1 << LOGE];
-#pragma unroll
-        for (int r = 0; r < (1 << LOGE); r++) { // ... reduced into q_i, - floor(q_l / 2) mod q_i, - [e]_{q_i}
-            u64 v = recanon(x[r], Mi) + neg_half;
-            v = v >= qi ? v - qi : v;
-            v += e[r] > 0 ? qi - (u64)e[r] : (u64)(-e[r]);
-            y[r] = v >= qi ? v - qi : v;
-        }
-        __syncthreads();
-        ntt_tile_fcols<K, LOGE, false, true, false>(
-            y, Mi, tw + ((size_t)i << logN), tw2 ? tw2 + ((size_t)i << (K + 1)) : nullptr, logN, blockIdx.x, nold, [=](int g, u64 v) { out[g] = v; }, lds);
-    }
-}
-
+// (the middle kernel is f_dr_icols_lift_fcols_kernel<K, LOGE, MERGE, NOISE = true>)
 template <int K, int LOGE>
 __global__ __launch_bounds__(kTileThreads) void f_frows_zenc_final_kernel(const u64 *__restrict__ tmp, const ZencItem *__restrict__ items,
                                                                            const u64 *__restrict__ pk, long pk_ps, int l, int Kp,
@@ -384,6 +356,7 @@ __global__ __launch_bounds__(kTileThreads) void f_frows_zenc_final_kernel(const 
 //   v_i = (s_i P^-1 t_i + u_i) q_L^-1              (L = l - 1; s the constant polynomial folded into the rescale, 1 when absent)
 // is ONE lifted polynomial per kept limb, whose first NTT phase follows: SEAL's two roundings, limb for limb, from l - 1 forward
 // transforms instead of 2l - 1.  Every step is exact arithmetic mod q_i.  MERGE as in f_dr_icols_lift_fcols_kernel.
+// (the roundings are written out, not dr_round / dr_reduce: through the functions all 24 listings change, at the parent's VGPR counts; not timed)
 template <int K, int LOGE, bool MERGE>
 __global__ __launch_bounds__(kTileThreads) void f_dr2_icols_lift_fcols_kernel(const u64 *__restrict__ acc, const MulRsItem *__restrict__ items,
                                                                                u64 *__restrict__ tmp, int ell, int Kp,
@@ -483,18 +456,12 @@ __global__ __launch_bounds__(kTileThreads) void f_dr_lift_fcols_kernel(const u64
     const u64 *in = last + (long)bp * last_stride;
     u64 *out = tmp + (size_t)z * N;
     const DModulus Mi = mods[i];
-    const u64 ql = mods[l].q, qi = Mi.q, half = ql >> 1;
-    const u64 neg_half = qi - half_mod[(size_t)l * Kp + i];
+    const u64 ql = mods[l].q, half = ql >> 1;
+    const u64 neg_half = Mi.q - half_mod[(size_t)l * Kp + i];
     u64 x[1 << LOGE];
     ntt_tile_fcols<K, LOGE, false, false, false>(
         x, Mi, tw + ((size_t)i << logN), tw2 ? tw2 + ((size_t)i << (K + 1)) : nullptr, logN, blockIdx.x,
-        [=](int g) {
-            u64 y = in[g] + half;
-            y = y >= ql ? y - ql : y;
-            y = recanon(y, Mi);
-            y += neg_half;
-            return y >= qi ? y - qi : y;
-        },
+        [=](int g) { return dr_reduce(dr_round(in[g], half, ql), Mi, neg_half); },
         [=](int g, u64 v) { out[g] = v; }, lds);
 }
 
@@ -611,6 +578,10 @@ __global__ __launch_bounds__(kTileThreads) void f_frows_final_kernel(const u64 *
 }
 
 // ---- L7 / R3 with a continuation into the consumer's first phase (plan.hpp Handoff) ---------------------------------------------------
+// (Bodies written out more than once below, each with the figure of its shared form; the rest is in profiles/fused_tail_share.txt:
+//   tensor terms, staged: f_frows_final_kernel<K, L, 4> up to +18 VGPRs, f_frows_final_cont_kernel<K, L, 4, CONT_RS> +20 to +42
+//   continuations as device functions: 6-8 of the 12 listings of each form need more VGPRs, up to +20
+//   MODE 2 / 4 epilogues through final_value, final_value MODE 0 without base_folded: every listing changes, not timed)
 // Output polynomial p, limb i of item b at this tile's coefficients g[] (pass NP-1 layout of a ROWS tile): computed exactly as
 // f_frows_final_kernel does for the same MODE, stored to the item's destination, and left in v[] (canonical).
 template <int K, int LOGE, int MODE>
@@ -1136,11 +1107,11 @@ void f_irows_decrypt(const Context &c, CtView ct, const u64 *sk, int ell, u64 *o
 
 void f_irows_tensor_c2(const Context &c, const MulItem *items, int ell, u64 *out, int B, hipStream_t s)
 {
-    launch_irows(c, SrcTensorC2{ items, c.d_mods, ell }, out, (long)c.N, B * ell, s);
+    launch_irows(c, SrcTensorC2<MulItem>{ items, c.d_mods, ell }, out, (long)c.N, B * ell, s);
 }
 void f_irows_tensor_c2_rs(const Context &c, const MulRsItem *items, int ell, u64 *out, int B, hipStream_t s)
 {
-    launch_irows(c, SrcTensorC2Rs{ items, c.d_mods, ell }, out, (long)c.N, B * ell, s);
+    launch_irows(c, SrcTensorC2<MulRsItem>{ items, c.d_mods, ell }, out, (long)c.N, B * ell, s);
 }
 void f_irows_decrypt_items(const Context &c, const BootItem *items, const SumSrc *srcs, const u64 *sk, int ell, u64 *out, int B,
                            hipStream_t s)
@@ -1200,50 +1171,56 @@ static long ks_merge_lift_min_wgs()
   // leaves CUs idle, 115 us against 93); a huge value = never
     return (long)option(OPT_KS_MERGE_LIFT_MIN_WGS);
 }
+// L2 / L6 / R2: `sources` source limbs with `per_source` target moduli each.  launch(K, LE, MERGE, grid) with the first three as
+// std::integral_constant values; grid.y = the limbs, or the sources when merged.
 // (the tile geometry is chosen from the unmerged limb count either way: the merged form is a throughput form of the same launch)
-#define DC_MERGED_LAUNCH(limbs, sources, per_source, KERNEL, ...)                                                                          \
-    {                                                                                                                                     \
-        const bool tiny = use_tiny_tiles(c.N, (limbs)), small = !tiny && use_small_tiles(c.N, (limbs));                                  \
-        const int le = tiny ? 1 : small ? 2 : 3;                                                                                          \
-        const bool merge = (per_source) > 1 && (long)(c.N >> (le == 1 ? TileGeo<1>::LOG : le == 2 ? TileGeo<2>::LOG : TileGeo<3>::LOG)) * (sources) >= ks_merge_lift_min_wgs(); \
-        if (!merge) {                                                                                                                     \
-            DC_GEO_SWITCH(c.k1, (limbs), DC_LAUNCH((KERNEL<KK, LE, false>), grid, dim3(kTileThreads), 0, s, __VA_ARGS__));      \
-        } else if (le == 1) {                                                                                                             \
-            constexpr int LE = 1;                                                                                                         \
-            const dim3 grid((unsigned)(c.N >> TileGeo<LE>::LOG), (unsigned)(sources));                                                    \
-            DC_K_SWITCH(c.k1, DC_LAUNCH((KERNEL<KK, LE, true>), grid, dim3(kTileThreads), 0, s, __VA_ARGS__))                    \
-        } else if (le == 2) {                                                                                                             \
-            constexpr int LE = 2;                                                                                                         \
-            const dim3 grid((unsigned)(c.N >> TileGeo<LE>::LOG), (unsigned)(sources));                                                    \
-            DC_K_SWITCH(c.k1, DC_LAUNCH((KERNEL<KK, LE, true>), grid, dim3(kTileThreads), 0, s, __VA_ARGS__))                    \
-        } else {                                                                                                                          \
-            constexpr int LE = 3;                                                                                                         \
-            const dim3 grid((unsigned)(c.N >> TileGeo<LE>::LOG), (unsigned)(sources));                                                    \
-            DC_K_SWITCH(c.k1, DC_LAUNCH((KERNEL<KK, LE, true>), grid, dim3(kTileThreads), 0, s, __VA_ARGS__))                    \
-        }                                                                                                                                 \
-    }
+template <class Launch>
+static void merged_dispatch(const Context &c, int sources, int per_source, Launch launch)
+{
+    const int limbs = sources * per_source, le = tile_geo_le(c.N, limbs);
+    const unsigned tiles = (unsigned)(c.N >> tile_geo_log(le));
+    const bool merge = per_source > 1 && (long)tiles * sources >= ks_merge_lift_min_wgs();
+    const dim3 grid(tiles, (unsigned)(merge ? sources : limbs));
+    tile_dispatch(c.k1, le, [&](auto k, auto le_c) {
+        if (merge)
+            launch(k, le_c, std::true_type{}, grid);
+        else
+            launch(k, le_c, std::false_type{}, grid);
+    });
+}
 
 void f_ks_icols_lift_fcols(const Context &c, const u64 *digits, u64 *ext, int B, int ell, hipStream_t s)
 {
-    DC_MERGED_LAUNCH(B * ell * ell, B * ell, ell, f_ks_icols_lift_fcols_kernel, digits, ext, ell, c.K - 1, c.d_mods, c.d_tw, c.d_itw, c.logN, c.twc2())
+    merged_dispatch(c, B * ell, ell, [&](auto k, auto le, auto merge, dim3 grid) {
+        DC_LAUNCH((f_ks_icols_lift_fcols_kernel<k(), le(), merge()>), grid, dim3(kTileThreads), 0, s, digits, ext, ell, c.K - 1, c.d_mods, c.d_tw,
+                  c.d_itw, c.logN, c.twc2());
+    });
 }
 
+// (noise: the byte noise of zero-encryptions, f_dr_noise_icols_lift_fcols; null = the plain divide-and-round)
+template <bool NOISE>
+static void launch_dr_icols_lift_fcols(const Context &c, const u64 *last, long last_stride, u64 *tmp, int polys, int cnt, int l,
+                                       const signed char *noise, hipStream_t s)
+{
+    merged_dispatch(c, polys, cnt, [&](auto k, auto le, auto merge, dim3 grid) {
+        DC_LAUNCH((f_dr_icols_lift_fcols_kernel<k(), le(), merge(), NOISE>), grid, dim3(kTileThreads), 0, s, last, last_stride, tmp, cnt, l, c.K,
+                  c.d_mods, c.d_half_mod, c.d_tw, c.d_itw, c.logN, c.twc2(), noise);
+    });
+}
 void f_dr_icols_lift_fcols(const Context &c, const u64 *last, long last_stride, u64 *tmp, int polys, int cnt, int l, hipStream_t s)
 {
-    DC_MERGED_LAUNCH(polys * cnt, polys, cnt, f_dr_icols_lift_fcols_kernel, last, last_stride, tmp, cnt, l, c.K, c.d_mods, c.d_half_mod, c.d_tw,
-                     c.d_itw, c.logN, c.twc2())
+    launch_dr_icols_lift_fcols<false>(c, last, last_stride, tmp, polys, cnt, l, nullptr, s);
+}
+void f_dr_noise_icols_lift_fcols(const Context &c, const u64 *last, long last_stride, u64 *tmp, int polys, int cnt, int l,
+                                 const signed char *noise, hipStream_t s)
+{
+    launch_dr_icols_lift_fcols<true>(c, last, last_stride, tmp, polys, cnt, l, noise, s);
 }
 
 void f_irows_zenc(const Context &c, const ZencItem *items, const u64 *pk, int l, u64 *out, int B, hipStream_t s)
 {
     DC_GEO_SWITCH(c.k2, 2 * B, DC_LAUNCH((f_irows_zenc_kernel<KK, LE>), grid, dim3(kTileThreads), 0, s, items, pk, (long)c.K * (long)c.N, l, out,
                                                   c.d_mods, c.d_itw, c.logN));
-}
-void f_dr_noise_icols_lift_fcols(const Context &c, const u64 *last, long last_stride, u64 *tmp, int polys, int cnt, int l,
-                                 const signed char *noise, hipStream_t s)
-{
-    DC_MERGED_LAUNCH(polys * cnt, polys, cnt, f_dr_noise_icols_lift_fcols_kernel, last, last_stride, tmp, cnt, l, c.K, c.d_mods, c.d_half_mod,
-                     c.d_tw, c.d_itw, c.logN, c.twc2(), noise)
 }
 void f_frows_zenc_final(const Context &c, const u64 *tmp, const ZencItem *items, const u64 *pk, int B, int l, hipStream_t s)
 {
@@ -1253,10 +1230,11 @@ void f_frows_zenc_final(const Context &c, const u64 *tmp, const ZencItem *items,
 
 void f_dr2_icols_lift_fcols(const Context &c, const u64 *acc, const MulRsItem *items, u64 *tmp, int B, int ell, hipStream_t s)
 {
-    DC_MERGED_LAUNCH(2 * B * (ell - 1), 2 * B, ell - 1, f_dr2_icols_lift_fcols_kernel, acc, items, tmp, ell, c.K, c.d_mods, c.d_half_mod, c.d_inv_last,
-                     c.d_tw, c.d_itw, c.logN, c.twc2())
+    merged_dispatch(c, 2 * B, ell - 1, [&](auto k, auto le, auto merge, dim3 grid) {
+        DC_LAUNCH((f_dr2_icols_lift_fcols_kernel<k(), le(), merge()>), grid, dim3(kTileThreads), 0, s, acc, items, tmp, ell, c.K, c.d_mods,
+                  c.d_half_mod, c.d_inv_last, c.d_tw, c.d_itw, c.logN, c.twc2());
+    });
 }
-#undef DC_MERGED_LAUNCH
 
 void f_frows_fold_final(const Context &c, const u64 *tmp, const MulRsItem *items, const u64 *acc, int B, int ell, hipStream_t s, const Handoff &h)
 {

@@ -26,3 +26,23 @@
         const dim3 grid((unsigned)(c.N >> TileGeo<LE>::LOG), (unsigned)(limbs));                          \
         DC_K_SWITCH(Kval, __VA_ARGS__)                                                                         \
     }
+
+namespace dacapo {
+
+// The same choice as a function, for launches whose grid is not (tiles, limbs): log2 coefficients per thread of the geometry DC_GEO_SWITCH
+// takes for `limbs`, its tile size, and launch(K, LE) with both as std::integral_constant values (ks_mac.hpp ks_mac_dispatch has the form)
+inline int tile_geo_le(size_t N, long limbs) { return use_tiny_tiles(N, limbs) ? 1 : use_small_tiles(N, limbs) ? 2 : 3; }
+inline int tile_geo_log(int le) { return le == 1 ? TileGeo<1>::LOG : le == 2 ? TileGeo<2>::LOG : TileGeo<3>::LOG; }
+template <class Launch>
+inline void tile_dispatch(int k, int le, Launch launch)
+{
+    auto with_k = [&](auto le_c) { DC_K_SWITCH(k, launch(std::integral_constant<int, KK>{}, le_c)) };
+    if (le == 1)
+        with_k(std::integral_constant<int, 1>{});
+    else if (le == 2)
+        with_k(std::integral_constant<int, 2>{});
+    else
+        with_k(std::integral_constant<int, 3>{});
+}
+
+} // namespace dacapo

@@ -947,3 +947,91 @@ def test_explicit_dag_equals_captured_graph_with_fused_links_and_opcode10(tmp_pa
         hevm.close()
     assert outs[1][1] == outs[2][1]
     assert outs[1][0].ell == outs[2][0].ell and outs[1][0].scale == outs[2][0].scale and (outs[1][0].data == outs[2][0].data).all()
+
+
+import re  # noqa: E402
+
+
+# ---- chain fusion, form by form (plan_exec.hip 4b links; fused_ks.hip f_frows_final_cont_kernel / f_frows_fold_final_kernel) ---------------
+def _link_program(name, slots):
+    """a program of a few instructions at level 3 that forms exactly one producer -> consumer pair; outputs: the producer's result (the
+    continuation kernel still stores it), then the consumer's"""
+    from dacapo_amd import hevm_asm as ha
+
+    rng = np.random.default_rng(41)
+    b = ha.Builder(slots=slots, init_level=3, policy="eager", shadow=True)
+    x, y = b.input(rng.uniform(-1, 1, slots)), b.input(rng.uniform(-1, 1, slots))
+    if name.startswith("mulrs"):                      # ct x ct -> (all-ones upscale folded into the) rescale: scale 80 -> 100 -> 40, level 2
+        r = b.rescale(b.upscale(b.mul(x, y), 20))
+    elif name.startswith("rs"):                       # ct x pt at one prime's worth of scale -> rescale: scale 100 -> 40, level 2
+        r = b.rescale(b.mul_plain(x, rng.uniform(0.5, 1, slots), scale_bits=60, normalise=False))
+    else:                                             # "rot": one hop at level 3
+        r = b.rotate(x, 1)
+    b.output(r)
+    if name.endswith("_mul"):
+        b.output(b.mul(r, r))                         # the consumer's key-switch operand is c1^2 of the producer's result
+    elif name.endswith("_boot"):
+        b.output(b.bootstrap(r, 3))
+    return b
+
+
+# (program, ks_fold_rescale, links, merged multiply-rescale pairs) -> the kernel form that the producer's last launch takes
+LINK_FORMS = {
+    "f_frows_final_cont_kernel<4, CONT_RS>": ("mulrs", 0, 1, 0),
+    "f_frows_final_cont_kernel<2, CONT_MUL>": ("rs_mul", 0, 1, 0),
+    "f_frows_final_cont_kernel<2, CONT_BOOT>": ("rs_boot", 0, 1, 0),
+    "f_frows_final_cont_kernel<0, CONT_BOOT>": ("rot_boot", 0, 1, 0),
+    "f_frows_fold_final_kernel<CONT_NONE>": ("mulrs", 1, 0, 1),
+    "f_frows_fold_final_kernel<CONT_MUL>": ("mulrs_mul", 1, 1, 1),
+    "f_frows_fold_final_kernel<CONT_BOOT>": ("mulrs_boot", 1, 1, 1),
+}
+
+
+@pytest.mark.parametrize("form", list(LINK_FORMS), ids=lambda f: re.sub(r"\W+", "_", f).strip("_"))
+def test_every_continuation_form_equals_the_unlinked_sequence_and_the_oracle_vm(tmp_path, capfd, form):
+    """N = 2^12, 6 primes, level 3: one program per continuation form (LINK_FORMS), run with chain_fusion 1 and 0.  The plan's trace line says
+    how many steps were fused into their producer's last kernel (exactly the one link with the option on, none with it off) and the VM how many
+    multiply-rescale pairs ran merged; every output limb is equal between the two runs and equal to the oracle VM's.  An opcode-10 result is
+    compared under the zero-encryption hook (c1 = 0, c0 the re-encoded plaintext): identical between the two runs, and against the oracle's
+    decrypt -> decode -> encode within the one unit per coefficient that tests/test_gpu_opcode10.py states for a source at scale 2^40 (the
+    oracle's FFT round-off can flip a rounding; the oracle VM's own opcode 10 draws a fresh encryption and cannot be compared limb for limb)."""
+    from dacapo_amd import lowlevel as ll
+    from dacapo_amd import runner
+    from test_gpu_opcode10 import _centered_diff
+
+    name, fold, links, pairs = LINK_FORMS[form]
+    logN, K = 12, 6
+    b = _link_program(name, 1 << (logN - 1))
+    cst, hv, _ = b.assemble()
+    outs = {}
+    for chain in (1, 0):
+        hevm = runner.HEVM(seed=77, logN=logN, num_primes=K, vm_options={"chain_fusion": chain, "ks_fold_rescale": fold})
+        o = Oracle(logN, K)
+        _import_keys(o, hevm, ll)
+        hevm.lw.hevm_test_zero_encryption(hevm.vm, True)
+        capfd.readouterr()
+        with runner.options(trace=1):
+            hevm.load_mem(cst, hv)
+            ovm = _mirror_vm(hevm, ll, o, cst, hv, tmp_path)
+            for i, a in enumerate(b.args):
+                hevm.setInput(i, a.plain)
+                ovm.ciphers[i] = _get_ct(hevm, ll, i)
+            hevm.run()
+        m = re.findall(r"(\d+) fused into their producer's last kernel", capfd.readouterr().err)
+        assert m and int(m[-1]) == (links if chain else 0), (form, chain, m)
+        assert hevm.fold_rescale_stats() == pairs, (form, chain)
+        ovm.run()
+        regs = [int(r) for r in ovm.prog.res_dst]
+        outs[chain] = [_get_ct(hevm, ll, r) for r in regs]
+        for k, (r, got) in enumerate(zip(regs, outs[chain])):
+            if k == 1 and name.endswith("_boot"):
+                src = outs[chain][0]
+                assert got.ell == 3 and got.scale == 2.0 ** int(np.log2(src.scale)) and not got.data[1].any()
+                want = o.encode(o.decode(o.decrypt(src)), got.scale, 3)
+                assert np.abs(_centered_diff(o, got.data[0], want.data, 3)).max() <= 1
+            else:
+                want = ovm.ciphers[r]
+                assert got.ell == want.ell and got.scale == want.scale and (got.data == want.data).all(), (form, chain, k)
+        hevm.close()
+    for g1, g0 in zip(outs[1], outs[0]):
+        assert g1.ell == g0.ell and g1.scale == g0.scale and (g1.data == g0.data).all(), form

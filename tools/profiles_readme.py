@@ -234,6 +234,7 @@ rows.append("| `ks_lazy_sum_ab.txt` | lazy sums on SEAL-layout keys (option `ks_
 rows.append("| `zenc_head_ab.txt` | the zero-encryption head of `run()` (option `zenc_head`, `HEVM::plan_zero_encrypt`): the head's own duration and its kernels on the parent commit and under both values (kernel traces of plain `bench.py` runs, `tools/summarize/zenc_head.py`), `run()` of the headline on three VMs with the option 0, 1, 0 (0/0 spread beside the difference), the chunk-size sweep 64 / 128 / 192 / 256 on the hooks build, the head's scratch under both values, `bench.py`'s `ms_per_step` on the parent commit and on the branch on one box, and the compile-time VGPR / LDS / scratch figures of the new kernels | `python tools/legs/zenc_head_ab.py --out profiles/zenc_head_ab.txt`; `DACAPO_AMD_HOOKS=1 python tools/legs/zenc_head_ab.py --sweep --out profiles/zenc_head_ab.txt` |")
 rows.append("| `ks_fold_rescale_ab.txt` | a rescale folded into the multiply's key switch (option `ks_fold_rescale`, `dc_ct_mul_relin_rescale`): `dc_ct_mul_relin` + `dc_ct_rescale` against the one call under device events at N = 2^15 / 2, 3, 5, 13 primes and N = 2^16 / 24 primes, `run()` of the headline and of its 13-prime lowering with the option off, on, off (off/off spread beside the difference), pair counts, and the compile-time VGPR / LDS / scratch figures of the new kernels | `python tools/legs/ks_fold_rescale_ab.py --out profiles/ks_fold_rescale_ab.txt` |")
 rows.append("| `ks_mac_regs.txt` | compile-time figures, not runs: VGPRs, SGPRs, spills, scratch and LDS of `f_ks_gmac_kernel`, `f_ks_gsum_kernel`, `hyb_mac_kernel` and `hyb_mac_group_kernel` before and after their shared pieces moved to `ks_mac.hpp` / `galois.hpp`, both builds, with `identical` / `differs` per instantiation, and which pieces were left written out because of what they cost | `hipcc -S --cuda-device-only` of parent and branch, `python tools/experiments/asm_compare.py <parent dir> <branch dir> --table '<regex>'` |")
+rows.append("| `fused_tail_share.txt` | compile-time figures, not runs: every kernel of `fused_ks.hip` (and of `hybrid_fused.hip`, `hoist_ks.hip`, which include the touched header) against the parent's listing after the divide-and-round middle (plain / noise), the `a1·b1` loader, the rounding arithmetic and the merged-launch dispatch got one definition each, both builds, the renamed kernels paired by hand; and each shared form that was built and NOT kept (tensor terms, continuations, target loop, `base_folded`) with the VGPR figures that decided it | `hipcc -S --cuda-device-only` of parent and branch, `python tools/experiments/asm_compare.py <parent dir> <branch dir> --rename 'OLD=NEW' [--table '<regex>']` |")
 print("\n".join(r for r in rows if r))
 print()
 print("## Round 5 (everything `r05_*`; one `gpurun` call of `tools/collect_profiles.sh r05` on the committed build -- the JSON files that `bench.py` reads carry "
@@ -246,7 +247,7 @@ rows = [bench_row("r05"), traffic_row("r05"), step_row("r05"), valu_row("r05"),
         f"| `r05_run_budget_b13.txt` / `.json` | one `run()` of the 13-prime lowering kernel by kernel with the same floors: {budget_head('r05_run_budget_b13.txt')}; "
         f"{budget_rows('r05_run_budget_b13.txt', 'f_ks_frows_mac_kernel<8, 2, 0, true>|f_ks_lift_fcols_kernel<7, 3>', 2)} | `tools/collect_run_budget.sh r05 b13`, `tools/summarize/run_budget.py` |",
         f"| `r05_run_budget_headline.txt` / `.json` | the same for the headline program: {budget_head('r05_run_budget_headline.txt')}; "
-        f"{budget_rows('r05_run_budget_headline.txt', 'f_ks_frows_mac_kernel<8, 2, 0, true>|f_dr_icols_lift_fcols_kernel<7, 1, false>', 2)} | `tools/collect_run_budget.sh r05 headline` |",
+        f"{budget_rows('r05_run_budget_headline.txt', 'f_ks_frows_mac_kernel<8, 2, 0, true>|f_dr_icols_lift_fcols_kernel<7, 1, false(, false)?>', 2)} | `tools/collect_run_budget.sh r05 headline` |",
         f"| `r05_lowering_sweep.txt`, `r05_per_op_sweep.txt` | this round's launch-shape options switched off one at a time on one box (HIP events / best of 6 runs): {sweep_lines('r05_lowering_sweep.txt', 5)} //// {sweep_lines('r05_per_op_sweep.txt', 5)} | `tools/legs/lowering_sweep.py`, `tools/legs/per_op_sweep.py` |",
         f"| `r05_ntt_full_check.txt` | single-crossing kernel / two-launch tiles, µs, by limb count (bit-exactness checked in the same run): {check_lines('r05_ntt_full_check.txt')} | `tools/legs/ntt_full_check.py <limbs> 20` |",
         f"| `r05_hybrid_ks_kernels.txt` | one grouped-digit rotation hop at N = 2^17 under round 5's key shape (4 digits of 8 under 9 special primes), kernel by kernel with measured HBM bytes for the three "
