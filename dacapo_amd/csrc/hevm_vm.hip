@@ -500,6 +500,9 @@ void HEVM::init_context(int logN, int K, const u64 *primes, int dir_ksp, int dir
     boot_secret_weight = (int)option(OPT_BOOT_SECRET_HW);
     rot_compose = option(OPT_ROT_COMPOSE) != 0;
     online_encode = option(OPT_ONLINE_ENCODE) != 0 && use_plan && !host_encoder;
+    // (the options without a parity run of the re-levelled plan keep the ASAP plan)
+    plan_level = (int)option(OPT_PLAN_LEVEL);
+    if (online_encode || lazy_sums || ks_hoist || ks_lazy || ks_fold_rescale || rot_compose || ksp > 1 || alpha > 1) plan_level = 0;
     lanes.resize(1);
     DC_HIP_CHECK(hipStreamCreateWithFlags(&lanes[0].stream, hipStreamNonBlocking));
     lanes[0].ws = ctx->ws0;

@@ -300,6 +300,9 @@ class HEVM {
     bool lazy_sums = false; // option hyb_lazy_sum = 1: sums of direct-key rotations share one division by P (plan_exec.hip section 2b)
     bool fold_rescale_into_boot = false; // option fold_rescale_boot = 1: do a rescale that only feeds an opcode 10 inside its re-encoder
     int plan_lanes = 2; // independent steps of a wave also use an auxiliary stream (pays off only inside the graph; option plan_lanes = 1: one stream)
+    // option plan_level: 0 the plan levels its operations ASAP; 1 slack-aware levelling (plan_levels.hpp) and a plaintext addend hoisted out of a
+    // rescale's folded sum (plan_exec.hip section 2); 2 the hoist alone (a measurement leg).  Every limb is the same under all three
+    int plan_level = 1;
     void bump_epoch(hipStream_t s);
 
     // statistics of the last run()

@@ -29,6 +29,7 @@ static const OptDef kDefs[OPT_COUNT] = {
     { "plan_lanes", 2 },
     { "plan_aux_min_cost", 3 },
     { "max_batch", 64 },
+    { "plan_level", 1 }, // measured: profiles/plan_levels_ab.txt
     { "chain_fusion", 1 },
     { "host_encoder", 0 },
     { "online_encode", 0 },

@@ -30,6 +30,7 @@ enum Opt : int {
     OPT_PLAN_LANES,        // streams the plan's independent steps are spread over (1 or 2)
     OPT_PLAN_AUX_MIN_COST, // a wave's auxiliary-stream share must be worth a fork / join: at least this many cost units (key switch 8, opcode 10 5, rescale 3, element-wise 1)
     OPT_MAX_BATCH,         // items per heavy batched step
+    OPT_PLAN_LEVEL,        // how the plan levels its operations: 0 ASAP (wave = deepest producer + 1); 1 slack-aware (plan_levels.hpp): an operation off the longest chain waits inside its window [ASAP, ALAP] for a wave that already holds a step of its kind, level and target -- and a plaintext addend inside a rescale's folded sum becomes the rescale's own "+ a" (plan_exec.hip section 2); 2 that hoist alone (a measurement leg).  Same depth or less, fewer steps, every limb the same (default 1: profiles/plan_levels_ab.txt).  ASAP is kept under online_encode, hyb_lazy_sum, ks_hoist / ks_lazy_sum, ks_fold_rescale, rot_compose and grouped digits (no parity run there)
     OPT_CHAIN_FUSION,      // producer's last kernel runs the consumer's first phase
     OPT_HOST_ENCODER,      // encode / decode on the host (comparison only)
     OPT_ONLINE_ENCODE,     // encode plaintexts at use instead of pre-encoding the pool

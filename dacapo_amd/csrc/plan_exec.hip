@@ -13,6 +13,7 @@
 #include <tuple>
 
 #include "hevm_vm.hpp"
+#include "plan_levels.hpp"
 
 namespace dacapo {
 
@@ -364,6 +365,20 @@ void HEVM::build_plan()
             p.srcs = O[(size_t)dp].srcs, p.src_plain = O[(size_t)dp].src_plain;
             O[(size_t)dp].dead = true;
         }
+        // (option plan_level) ... and ONE plaintext addend hoisted out of the folded sum: a bare term (x * m) + a -- a single-use addcp, which is
+        // neither the rescale's own "+ a" nor a ct * pt term, so it and its mulcp would stay steps of their own -- gives its plaintext to the
+        // rescale's free rs_add and becomes the term x * m.  RsItem means ((sum of terms) + add on c0) * mul and modular addition is exact: the
+        // same limbs.  A rescale that already has an rs_add is left alone.
+        if (plan_level >= 1 && p.rs_sum && p.rs_add < 0) {
+            if (p.src_plain.size() != p.srcs.size()) p.src_plain.assign(p.srcs.size(), -1);
+            for (size_t k = 0; k < p.srcs.size(); k++) {
+                if (p.src_plain[k] >= 0 || (dp = single_def(p.srcs[k], P_ADDP)) < 0 || O[(size_t)dp].level != p.level) continue;
+                p.rs_add = O[(size_t)dp].plain, p.srcs[k] = O[(size_t)dp].srcs[0], O[(size_t)dp].dead = true;
+                if ((dp = single_def(p.srcs[k], P_MULP)) >= 0)
+                    p.src_plain[k] = O[(size_t)dp].plain, p.srcs[k] = O[(size_t)dp].srcs[0], O[(size_t)dp].dead = true;
+                break;
+            }
+        }
     }
 
     // ... and a rescale whose only consumer is an opcode 10 is not executed at all.  Opcode 10 decrypts, re-encodes and
@@ -473,6 +488,53 @@ void HEVM::build_plan()
         }
         p.wave = w + 1;
         max_wave = std::max(max_wave, p.wave);
+    }
+    // ---- 3b. slack-aware levelling (option plan_level = 1; plan_levels.hpp): an operation off the longest chain waits, inside its window
+    // [ASAP, ALAP], for a wave that already holds a step of its bucket.  Sections 4 ... 5 below work on the new waves as they are: a step is
+    // still (wave, kind, level, target), steps of one wave are still independent, and a pool buffer is recycled by wave order.
+    int levels_moved = 0;
+    if (plan_level == 1) {
+        std::vector<int> live, idx(O.size(), -1);
+        for (size_t i = 0; i < O.size(); i++)
+            if (!O[i].dead) idx[i] = (int)live.size(), live.push_back((int)i);
+        const size_t n = live.size();
+        std::vector<int> kind(n), level(n), target(n), cap(n), fixed(n), launches(n), link_prev(n, -1), asap(n), first(n + 1, 0), prod, wave(n);
+        const bool links = chain_fusion && chain_fusion_supported();
+        auto live_def = [&](int v, bool own) -> int { // live pop that defines value v (own: v is its result itself, not a view of it), or -1
+            const Val &sv = V[(size_t)v];
+            if (sv.def_pop < 0 || O[(size_t)sv.def_pop].dead || (own && (sv.root != v || O[(size_t)sv.def_pop].dst != v))) return -1;
+            return sv.def_pop;
+        };
+        for (size_t k = 0; k < n; k++) {
+            const Pop &p = O[(size_t)live[k]];
+            const bool heavy = p.kind == P_ROT || p.kind == P_MULCC || p.kind == P_RESCALE || p.kind == P_BOOT || p.kind == P_ROTSUM;
+            kind[k] = (int)p.kind, level[k] = p.level, target[k] = p.target_level, asap[k] = p.wave;
+            cap[k] = (int)std::max<size_t>(1, (heavy ? (size_t)max_batch : (size_t)4096) / (size_t)S); // (section 4's chunk)
+            fixed[k] = p.kind == P_ROTSUM;
+            launches[k] = p.kind == P_ROT || p.kind == P_MULCC || p.kind == P_ROTSUM ? 5 : p.kind == P_RESCALE ? 3 : p.kind == P_BOOT ? 4 : 1;
+            for (int s : p.srcs) {
+                const int dp = live_def(s, false);
+                if (dp >= 0) prod.push_back(idx[(size_t)dp]);
+            }
+            first[k + 1] = (int)prod.size();
+            // the producer whose step could hand its result to this operation's first phase (section 4b's rule, operation for operation)
+            const bool consumer = p.kind == P_RESCALE || p.kind == P_BOOT || p.kind == P_MULCC;
+            if (!links || !consumer || p.rs_sum || p.boot_drop >= 0 || (p.kind != P_RESCALE && (p.rs_add >= 0 || p.rs_mul >= 0))) continue;
+            for (size_t w = 0; w < (p.kind == P_MULCC ? 2u : 1u) && link_prev[k] < 0; w++) {
+                const int dp = live_def(p.srcs[w], true);
+                if (dp < 0) continue;
+                const Pop &a = O[(size_t)dp];
+                if ((p.kind == P_RESCALE && a.kind == P_MULCC && a.level == p.level) ||
+                    (p.kind == P_BOOT && ((a.kind == P_RESCALE && a.level - 1 == p.level) || (a.kind == P_ROT && a.target_level >= 0 && a.level == p.level))) ||
+                    (p.kind == P_MULCC && a.kind == P_RESCALE && a.level - 1 == p.level))
+                    link_prev[k] = idx[(size_t)dp];
+            }
+        }
+        LevelOps in;
+        in.n = (int)n, in.kind = kind.data(), in.level = level.data(), in.target = target.data(), in.cap = cap.data(), in.fixed = fixed.data();
+        in.launches = launches.data(), in.prod_first = first.data(), in.prod = prod.data(), in.link_prev = link_prev.data(), in.asap = asap.data();
+        levels_moved = plan_levels(in, 1, wave.data());
+        for (size_t k = 0; k < n; k++) O[(size_t)live[k]].wave = wave[k];
     }
 
     // ---- 4. steps: per wave, one batch per (kind, level) -----------------------------------------------------------------
@@ -1266,6 +1328,22 @@ void HEVM::build_plan()
         fprintf(stderr, "[dacapo_amd] plan: %zu ops -> %zu pseudo-ops -> %zu steps (%zu on the auxiliary stream, %zu fused into their producer's last kernel) in %d waves, ~%zu launches, %zu live buffers (%.1f GB pool)\n",
                 ops.size(), O.size(), P.steps.size(), (size_t)std::count_if(P.steps.begin(), P.steps.end(), [](const Step &st) { return st.lane == 1; }), P.n_fused,
                 max_wave, P.launches, P.max_live, (double)P.pool.size() * buf_elems * 8 / 1e9);
+    if (option(OPT_TRACE)) { // what option plan_level changes, counted on the plan as built (the head's zero-encryptions are not steps)
+        size_t multi = 0, launches = 0;
+        for (size_t a = 0; a < P.steps.size();) {
+            size_t b = a;
+            while (b < P.steps.size() && P.steps[b].wave == P.steps[a].wave) b++;
+            multi += b - a > 1;
+            a = b;
+        }
+        for (const Step &st : P.steps)
+            launches += st.kind == P_ROT || st.kind == P_MULCC || st.kind == P_ROTSUM ? 5 : st.kind == P_RESCALE ? 3 : st.kind == P_BOOT ? 4 : 1;
+        fprintf(stderr, "[dacapo_amd] plan levels: plan_level %d moved %d operations: %zu steps in %d waves, %zu waves with more than one step, %zu links, "
+                        "%zu step launches (5 per key switch, 3 per rescale, 4 per opcode 10, 1 per limb-wise step, -1 per link), %zu live buffers, "
+                        "%zu pool buffers (%.3f GB)\n",
+                plan_level, levels_moved, P.steps.size(), max_wave, multi, P.n_fused, launches - P.n_fused, P.max_live, P.pool.size(),
+                (double)P.pool.size() * buf_elems * (double)S * 8 / 1e9);
+    }
 }
 
 // the launches of one step, on stream q, with the scratch of the step's lane
