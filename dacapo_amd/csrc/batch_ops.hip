@@ -107,9 +107,12 @@ static long fuse_mac_threshold() { return (long)option(OPT_KS_FUSE_MAC_TILES); }
 bool chain_fusion_supported() { return fuse_mac() && fuse_mac_threshold() == (1L << 40); }
 
 // `digits`: output of the inverse ROWS phase of the key-switch target [B][l][N] (w.digits, or the buffer a fused producer filled)
-template <int MODE>
+// `own`: MODE 1 only -- the target itself in NTT form [B][l][N], where the fused middle reads the digit a modulus owns (a sum of products:
+// b_mul_sum_relin); null: the fused middle recomputes a1*b1 from the MulItem table
+// `last(fused_mac)`: the launch of the last forward ROWS phase
+template <int MODE, class Last>
 static void b_ks_tail(Context &c, const BatchWs &w, u64 *digits, const KsItem *items, const void *final_items, const u64 *shared_key, int B,
-                      int ell, hipStream_t s, const Handoff &h)
+                      int ell, hipStream_t s, const u64 *own, Last last)
 {
     const size_t N = c.N;
     const int K = c.K, sp = K - 1;
@@ -130,15 +133,24 @@ static void b_ks_tail(Context &c, const BatchWs &w, u64 *digits, const KsItem *i
                            shared_key, ell, K, N, c.logN, c.d_mods);
         f_irows_strided(c, acc_last, acc_ps, sp, 1, acc_last, acc_ps, 2 * B, s);
     } else // MODE 1: the operand a1*b1 is recomputed from the MulItem table (no tensor launch, see b_mul_relin)
-        f_ks_frows_mac(c, MODE, w.ext, MODE == 1 ? nullptr : w.target, MODE == 1 ? reinterpret_cast<const KsItem *>(final_items) : items,
+        f_ks_frows_mac(c, MODE, w.ext, MODE == 1 ? own : w.target, MODE == 1 ? reinterpret_cast<const KsItem *>(final_items) : items,
                        shared_key, w.acc, B, ell, s, MODE == 0);
     if (big) {
         launch_ntt_cols_inv(c, acc_last, acc_ps, 2 * B, nullptr, sp, 1, s);
         f_dr_lift_fcols(c, acc_last, acc_ps, w.tmp, 2 * B, ell, sp, s);
     } else
         f_dr_icols_lift_fcols(c, acc_last, acc_ps, w.tmp, 2 * B, ell, sp, s);
-    f_frows_final(c, (MODE == 1 && fused_mac) ? 4 : MODE, w.tmp, final_items, w.acc, 2 * B, ell, sp, s, RsItem{}, nullptr, nullptr, h,
-                  MODE == 0 && fused_mac); // (a rotation's base term was folded into the fused middle's accumulators)
+    last(fused_mac);
+}
+// ... with the last kernel of a rotation / a multiply (f_frows_final modes 0 / 1 / 4)
+template <int MODE>
+static void b_ks_tail(Context &c, const BatchWs &w, u64 *digits, const KsItem *items, const void *final_items, const u64 *shared_key, int B,
+                      int ell, hipStream_t s, const Handoff &h)
+{
+    b_ks_tail<MODE>(c, w, digits, items, final_items, shared_key, B, ell, s, nullptr, [&](bool fused_mac) {
+        f_frows_final(c, (MODE == 1 && fused_mac) ? 4 : MODE, w.tmp, final_items, w.acc, 2 * B, ell, c.K - 1, s, RsItem{}, nullptr, nullptr, h,
+                      MODE == 0 && fused_mac); // (a rotation's base term was folded into the fused middle's accumulators)
+    });
 }
 
 void b_rotate_hops(Context &c, const BatchWs &w, const KsItem *d_items, int B, int ell, hipStream_t s, const Handoff &h, int unique)
@@ -168,6 +180,82 @@ void b_mul_relin(Context &c, const BatchWs &w, const MulItem *d_items, const u64
     } else // small batches: a1*b1 is formed in the loaders and a0*b0, a0*b1 + a1*b0 in the last kernel's epilogue
         f_irows_tensor_c2(c, d_items, ell, w.digits, B, s);
     b_ks_tail<1>(c, w, digits, nullptr, d_items, relin_key, B, ell, s, h);
+}
+
+// prologue of a product sum where the fused middle is not used: dst.c0 = sum_k s_k a_k0 b_k0, dst.c1 = sum_k s_k (a_k0 b_k1 + a_k1 b_k0),
+// target[b] = sum_k s_k a_k1 b_k1.  grid = (N/512, l, B).  A thread reads every term at its own two coefficients before it writes them.
+// Accumulators as in fused_ks.hip tensor_sum: a term adds at most 2 products of canonical residues (< 2^120 each) to one of them, all are
+// folded every 8 terms and restart from the canonical residue: 16 (q - 1)^2 + 2^60 < 2^124, the range Acc128 reduces, for any count.
+__global__ __launch_bounds__(kBT) void b_tensor_sum_kernel(const MulSumItem *__restrict__ items, const MulTerm *__restrict__ terms,
+                                                            u64 *__restrict__ target, int ell, size_t N, const DModulus *__restrict__ mods)
+{
+    const int i = blockIdx.y, b = blockIdx.z;
+    const MulSumItem it = items[b];
+    const DModulus m = mods[i];
+    const size_t k = ((size_t)blockIdx.x * kBT + threadIdx.x) * 2;
+    Acc128 acc[2][3][2]; // [sign][component][element]
+#pragma unroll
+    for (int sg = 0; sg < 2; sg++)
+#pragma unroll
+        for (int cp = 0; cp < 3; cp++) acc[sg][cp][0].clear(), acc[sg][cp][1].clear();
+    for (int t = 0; t < it.count; t++) {
+        const MulTerm tm = terms[it.first + t];
+        const u64x2 a0 = *reinterpret_cast<const u64x2 *>(tm.a.limb(0, i, N) + k), a1 = *reinterpret_cast<const u64x2 *>(tm.a.limb(1, i, N) + k);
+        const u64x2 b0 = *reinterpret_cast<const u64x2 *>(tm.b.limb(0, i, N) + k), b1 = *reinterpret_cast<const u64x2 *>(tm.b.limb(1, i, N) + k);
+#pragma unroll
+        for (int sg = 0; sg < 2; sg++) {
+            if ((tm.sign > 0) == (sg == 0)) { // (wave-uniform; written as a loop so that the accumulators are indexed by constants)
+#pragma unroll
+                for (int e = 0; e < 2; e++) {
+                    acc[sg][0][e].mac(a0[e], b0[e]);
+                    acc[sg][1][e].mac(a0[e], b1[e]);
+                    acc[sg][1][e].mac(a1[e], b0[e]);
+                    acc[sg][2][e].mac(a1[e], b1[e]);
+                }
+            }
+        }
+        if ((t & 7) == 7 && t + 1 < it.count) {
+#pragma unroll
+            for (int sg = 0; sg < 2; sg++)
+#pragma unroll
+                for (int cp = 0; cp < 3; cp++)
+#pragma unroll
+                    for (int e = 0; e < 2; e++) {
+                        const u64 f = acc[sg][cp][e].reduce(m);
+                        acc[sg][cp][e].clear(), acc[sg][cp][e].lo = f;
+                    }
+        }
+    }
+    u64x2 c[3];
+#pragma unroll
+    for (int cp = 0; cp < 3; cp++)
+#pragma unroll
+        for (int e = 0; e < 2; e++) c[cp][e] = submod(acc[0][cp][e].reduce(m), acc[1][cp][e].reduce(m), m.q);
+    *reinterpret_cast<u64x2 *>(it.dst.limb(0, i, N) + k) = c[0];
+    *reinterpret_cast<u64x2 *>(it.dst.limb(1, i, N) + k) = c[1];
+    *reinterpret_cast<u64x2 *>(target + ((size_t)b * ell + i) * N + k) = c[2];
+}
+
+// b_mul_relin's launch sequence for sums of products: the first kernel (or the tensor launch) and the last one walk the item's terms; the
+// key switch between them is b_ks_tail<1> itself, reading the summed c2 from w.target.
+void b_mul_sum_relin(Context &c, const BatchWs &w, const MulSumItem *d_items, const MulTerm *d_terms, const u64 *relin_key, int B, int ell,
+                     hipStream_t s)
+{
+    if (c.hybrid()) {
+        fprintf(stderr, "[dacapo_amd] b_mul_sum_relin: this context switches keys with grouped digits; sums of products are relinearised once on "
+                        "SEAL-layout keys only\n");
+        abort();
+    }
+    const size_t N = c.N;
+    const bool fused_mac = fuse_mac() && (long)(N >> 10) * B * ell * ell < fuse_mac_threshold(); // same split as b_ks_tail
+    if (fused_mac)
+        f_irows_tensor_sum(c, d_items, d_terms, ell, w.digits, w.target, B, s);
+    else {
+        DC_LAUNCH(b_tensor_sum_kernel, dim3((unsigned)(N / (2 * kBT)), ell, B), dim3(kBT), 0, s, d_items, d_terms, w.target, ell, N, c.d_mods);
+        f_irows_strided(c, w.target, (long)N, 0, ell, w.digits, (long)N, B * ell, s);
+    }
+    b_ks_tail<1>(c, w, w.digits, nullptr, nullptr, relin_key, B, ell, s, w.target,
+                 [&](bool fused) { f_frows_sum_final(c, w.tmp, d_items, fused ? d_terms : nullptr, w.acc, B, ell, s); });
 }
 
 bool mul_relin_rescale_fused(const Context &c, int B, int ell)

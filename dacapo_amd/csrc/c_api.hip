@@ -1,6 +1,8 @@
 // Kernel-level C ABI (include/dacapo_ckks.h): thin extern "C" shims over the launchers.
 #include "../../include/dacapo_ckks.h"
 
+#include <string.h>
+
 #include <algorithm>
 #include <vector>
 
@@ -118,7 +120,7 @@ void dc_context_destroy(dc_context *ctx)
     if (ctx && ctx->item_ring) (void)hipFree(ctx->item_ring);
     if (ctx)
         for (void *p : { ctx->hoist_items, (void *)ctx->hoist_acc, (void *)ctx->hoist_tmp, (void *)ctx->hoist_digits, (void *)ctx->hoist_ext, (void *)ctx->fold_consts,
-                         (void *)ctx->fold_tmp })
+                         (void *)ctx->fold_tmp, ctx->mulsum_table })
             if (p) (void)hipFree(p);
     if (ctx && ctx->owned) delete ctx->c;
     delete ctx;
@@ -290,6 +292,73 @@ void dc_ct_mul_relin_rescale(dc_context *ctx, uint64_t *dst, long dst_stride, co
     b_mul_relin(c, batch_ws(c.ws0), static_cast<const MulItem *>(item_slot(ctx, &mi, sizeof(mi), s)), relin_key, 1, ell, s);
     const RsItem ri{ prod, V(dst, dst_stride), 0, 0, add_plain, mul_plain };
     b_rescale(c, batch_ws(c.ws0), static_cast<const RsItem *>(item_slot(ctx, &ri, sizeof(ri), s)), 1, ell, s);
+}
+void dc_ct_mul(dc_context *ctx, uint64_t *dst3, long dst_stride, const uint64_t *a, long a_stride, const uint64_t *b, long b_stride, int ell,
+               void *stream)
+{
+    launch_tensor(*ctx->c, V(dst3, dst_stride), dst3 + 2 * dst_stride, V(a, a_stride), V(b, b_stride), ell, S(stream));
+}
+void dc_ct_relin(dc_context *ctx, uint64_t *dst, long dst_stride, const uint64_t *src3, long src_stride, const uint64_t *relin_key, int ell,
+                 void *stream)
+{
+    keyswitch(*ctx->c, ctx->c->ws0, V(dst, dst_stride), src3, src3 + src_stride, src3 + 2 * src_stride, relin_key, ell, S(stream));
+}
+// dst = relin(sum_k signs[k] as[k] (x) bs[k]) with one key-switch sequence (batch_ops.hip b_mul_sum_relin).  The table -- the item, then its
+// terms -- is kept in the handle and copied as dc_ct_rotate_sum_hoisted copies its own.
+void dc_ct_mul_sum_relin(dc_context *ctx, uint64_t *dst, long dst_stride, const uint64_t *const *as, const uint64_t *const *bs, const int32_t *signs,
+                         int count, long src_stride, const uint64_t *relin_key, int ell, void *stream)
+{
+    Context &c = *ctx->c;
+    hipStream_t s = S(stream);
+    if (c.hybrid()) {
+        fprintf(stderr, "[dacapo_amd] dc_ct_mul_sum_relin: this context switches keys with grouped digits (ks_special > 1); the call is for "
+                        "SEAL-layout keys (use dc_ct_mul_relin and dc_ct_add)\n");
+        abort();
+    }
+    if (count < 1 || count > kMulSumMax || ell < 1 || ell > c.max_level()) {
+        fprintf(stderr, "[dacapo_amd] dc_ct_mul_sum_relin: %d products at level %d (1..%d products, level 1..%d)\n", count, ell, kMulSumMax,
+                c.max_level());
+        abort();
+    }
+    const size_t N = c.N;
+    bool alias = false;
+    for (int k = 0; k < count; k++) {
+        if (signs[k] != 1 && signs[k] != -1) {
+            fprintf(stderr, "[dacapo_amd] dc_ct_mul_sum_relin: sign %d of product %d (+1 or -1)\n", (int)signs[k], k);
+            abort();
+        }
+        alias = alias || overlaps(dst, as[k]) || overlaps(dst, bs[k]);
+    }
+    if (alias) { // the last kernel reads the operands where other workgroups write dst: such a destination is written through scratch
+        const size_t need = (size_t)2 * ell * N * sizeof(u64);
+        if (need > ctx->fold_tmp_cap) { // (growing waits for the device: hipFree)
+            if (ctx->fold_tmp) DC_HIP_CHECK(hipFree(ctx->fold_tmp));
+            ctx->fold_tmp = nullptr;
+            DC_HIP_CHECK(hipMalloc(&ctx->fold_tmp, need));
+            ctx->fold_tmp_cap = need;
+        }
+    }
+    const CtView out = alias ? CtView{ ctx->fold_tmp, (long)ell * (long)N } : V(dst, dst_stride);
+    constexpr size_t kTermsAt = 64; // the item, then the terms
+    static_assert(sizeof(MulSumItem) <= kTermsAt && kTermsAt % alignof(MulTerm) == 0, "product-sum table layout");
+    std::vector<char> h(kTermsAt + (size_t)count * sizeof(MulTerm));
+    const MulSumItem item{ out, 0, count };
+    memcpy(h.data(), &item, sizeof(item));
+    for (int k = 0; k < count; k++) {
+        const MulTerm t{ V(as[k], src_stride), V(bs[k], src_stride), (int)signs[k] };
+        memcpy(h.data() + kTermsAt + (size_t)k * sizeof(MulTerm), &t, sizeof(t));
+    }
+    if (h.size() > ctx->mulsum_cap) {
+        if (ctx->mulsum_table) DC_HIP_CHECK(hipFree(ctx->mulsum_table));
+        ctx->mulsum_table = nullptr;
+        DC_HIP_CHECK(hipMalloc(&ctx->mulsum_table, kTermsAt + (size_t)kMulSumMax * sizeof(MulTerm)));
+        ctx->mulsum_cap = kTermsAt + (size_t)kMulSumMax * sizeof(MulTerm);
+    }
+    DC_HIP_CHECK(hipMemcpyAsync(ctx->mulsum_table, h.data(), h.size(), hipMemcpyHostToDevice, s));
+    DC_HIP_CHECK(hipStreamSynchronize(s)); // (the host table goes out of scope)
+    const char *d = static_cast<const char *>(ctx->mulsum_table);
+    b_mul_sum_relin(c, batch_ws(c.ws0), reinterpret_cast<const MulSumItem *>(d), reinterpret_cast<const MulTerm *>(d + kTermsAt), relin_key, 1, ell, s);
+    if (alias) launch_ew(c, EwOp::Copy, V(dst, dst_stride), out, out, 2, 2, ell, s);
 }
 void dc_ct_rotate_hop(dc_context *ctx, uint64_t *dst, long dst_stride, const uint64_t *src, long src_stride,
                       uint32_t galois_elt, const uint64_t *galois_key, int ell, void *stream)

@@ -17,4 +17,7 @@ struct dc_context {
     // dc_ct_mul_relin_rescale: a ring of mul_const residue tables, and [3][l][N] for a destination that aliases an operand / the default sequence
     dacapo::u64 *fold_consts = nullptr, *fold_tmp = nullptr;
     size_t fold_tmp_cap = 0;
+    // dc_ct_mul_sum_relin: the item and its term table (a destination that aliases an operand goes through fold_tmp)
+    void *mulsum_table = nullptr;
+    size_t mulsum_cap = 0;
 };

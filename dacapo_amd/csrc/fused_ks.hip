@@ -179,6 +179,114 @@ __global__ __launch_bounds__(kTileThreads) void f_irows_kernel(Src src, u64 *__r
         [=](int g, u64 v) { o[g] = v; }, lds);
 }
 
+// ---- sums of signed ct x ct products relinearised once (plan.hpp MulSumItem, b_mul_sum_relin) ----------------------------------------------
+// Component COMP of sum_k s_k (a_k (x) b_k) at limb i, for the E coefficients g[] a thread owns: 0 = a0 b0, 1 = a0 b1 + a1 b0, 2 = a1 b1.
+// Terms of either sign gather in an accumulator of their own and the canonical difference is taken once at the end: modular arithmetic is
+// exact, so the value is what tensor + poly_add / poly_sub give term by term, in any order.
+// Ranges (modarith.hpp): an operand is a canonical residue, at most q - 1 < 2^60, so a product is below 2^120 and Acc128 takes 16 of them with
+// hi < 2^60, the precondition of reduce128_lazy.  A term adds at most 2 products (COMP 1) to ONE accumulator; both are folded every 8 terms
+// -- at most 16 products since the last fold -- and a folded accumulator restarts from its canonical residue, one more term below 2^60:
+// 16 (q - 1)^2 + 2^60 < 2^124 for operands q - 1 throughout, whatever the count and the signs.
+template <int E, int COMP>
+__device__ __forceinline__ void tensor_sum(u64 (&v)[E], const int (&g)[E], const MulTerm *__restrict__ terms, int first, int count, int i, size_t N,
+                                           const DModulus &M)
+{
+    Acc128 pos[E], neg[E];
+#pragma unroll
+    for (int j = 0; j < E; j++) pos[j].clear(), neg[j].clear();
+    auto mac_all = [&](Acc128(&a)[E], const u64 *x, const u64 *y) {
+#pragma unroll
+        for (int j = 0; j < E; j++) a[j].mac(x[g[j]], y[g[j]]);
+    };
+    for (int t = 0; t < count; t++) {
+        const MulTerm tm = terms[first + t];
+        const u64 *x = tm.a.limb(COMP == 2 ? 1 : 0, i, N), *y = tm.b.limb(COMP == 0 ? 0 : 1, i, N);
+        if (tm.sign > 0) // (wave-uniform)
+            mac_all(pos, x, y);
+        else
+            mac_all(neg, x, y);
+        if (COMP == 1) {
+            const u64 *x1 = tm.a.limb(1, i, N), *y0 = tm.b.limb(0, i, N);
+            if (tm.sign > 0)
+                mac_all(pos, x1, y0);
+            else
+                mac_all(neg, x1, y0);
+        }
+        if ((t & 7) == 7 && t + 1 < count) {
+#pragma unroll
+            for (int j = 0; j < E; j++) {
+                const u64 fp = pos[j].reduce(M), fn = neg[j].reduce(M);
+                pos[j].clear(), neg[j].clear();
+                pos[j].lo = fp, neg[j].lo = fn;
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < E; j++) v[j] = submod(pos[j].reduce(M), neg[j].reduce(M), M.q);
+}
+
+// L1 of a product sum: the term-walking form of f_irows_kernel<SrcTensorC2>.  z = b*ell + i.  The sum's c2 limb also goes to target[z] in NTT
+// form: the key switch's middle reads the digit a modulus owns from there (f_ks_frows_mac_kernel with a target, as it stands).
+template <int K, int LOGE>
+__global__ __launch_bounds__(kTileThreads) void f_irows_tensor_sum_kernel(const MulSumItem *__restrict__ items, const MulTerm *__restrict__ terms,
+                                                                           int ell, u64 *__restrict__ out, u64 *__restrict__ target,
+                                                                           const DModulus *__restrict__ mods, const u64 *__restrict__ itw, int logN)
+{
+    __shared__ __attribute__((aligned(16))) u64 lds[TileGeo<LOGE>::LDS_ELEMS];
+    constexpr int E = 1 << LOGE;
+    const int z = blockIdx.y, i = z % ell;
+    const size_t N = (size_t)1 << logN;
+    const MulSumItem it = items[z / ell];
+    const DModulus M = mods[i];
+    u64 *o = out + (size_t)z * N, *tg = target + (size_t)z * N;
+    int g[E];
+#pragma unroll
+    for (int j = 0; j < E; j++) g[j] = tile_gidx<K, LOGE, false>(num_passes<LOGE>(K) - 1, logN, blockIdx.x, j);
+    u64 x[E];
+    tensor_sum<E, 2>(x, g, terms, it.first, it.count, i, N, M);
+#pragma unroll
+    for (int j = 0; j < E; j++) tg[g[j]] = x[j];
+    auto nold = [](int) -> u64 { return 0; };
+    ntt_tile_x<K, LOGE, false, true, false, true, false>(x, M, itw + ((size_t)i << logN), logN, blockIdx.x, nold,
+                                                         [=](int gi, u64 v) { o[gi] = v; }, lds);
+}
+
+// L7 of a product sum: the term-walking form of f_frows_final_kernel mode 4 (TENSOR: the base terms sum_k s_k d_k0 / sum_k s_k d_k1 are
+// computed in the epilogue; dst holds nothing yet and must not be an operand) and of mode 1 (!TENSOR: a tensor-sum launch left them in dst).
+// z = (b*2 + p)*cnt + i
+template <int K, int LOGE, bool TENSOR>
+__global__ __launch_bounds__(kTileThreads) void f_frows_sum_final_kernel(const u64 *__restrict__ tmp, const MulSumItem *__restrict__ items,
+                                                                          const MulTerm *__restrict__ terms, const u64 *__restrict__ acc, int cnt,
+                                                                          int l, int Kp, const DModulus *__restrict__ mods,
+                                                                          const u64 *__restrict__ inv_last, const u64 *__restrict__ tw, int logN)
+{
+    __shared__ __attribute__((aligned(16))) u64 lds[TileGeo<LOGE>::LDS_ELEMS];
+    constexpr int E = 1 << LOGE;
+    const int z = blockIdx.y, i = z % cnt, bp = z / cnt, b = bp >> 1, p = bp & 1;
+    const size_t N = (size_t)1 << logN;
+    const DModulus M = mods[i];
+    const u64 inv = inv_last[(size_t)l * Kp + i];
+    const u64 *in = tmp + (size_t)z * N;
+    const MulSumItem it = items[b];
+    const u64 *x = acc + (((size_t)bp) * (cnt + 1) + i) * N;
+    u64 *o = it.dst.limb(p, i, N);
+    u64 v[E], base[E];
+    int g[E];
+    auto nost = [](int, u64) {};
+    ntt_tile_x<K, LOGE, false, false, true, false, true>(v, M, tw + ((size_t)i << logN), logN, blockIdx.x, [=](int gi) { return in[gi]; }, nost, lds);
+#pragma unroll
+    for (int j = 0; j < E; j++) g[j] = tile_gidx<K, LOGE, false>(num_passes<LOGE>(K) - 1, logN, blockIdx.x, j);
+    if (!TENSOR) {
+#pragma unroll
+        for (int j = 0; j < E; j++) base[j] = o[g[j]];
+    } else if (p == 0)
+        tensor_sum<E, 0>(base, g, terms, it.first, it.count, i, N, M);
+    else
+        tensor_sum<E, 1>(base, g, terms, it.first, it.count, i, N, M);
+#pragma unroll
+    for (int j = 0; j < E; j++) o[g[j]] = addmod(base[j], mulmod(submod(x[g[j]], v[j], M.q), inv, M), M.q);
+}
+
 // ---- L2 / L6 / R2: inverse COLS phase, base change, first forward phase -------------------------------------------------------------------
 // (Their target loop is written out in f_ks_, f_dr_ and f_dr2_icols_lift_fcols_kernel: as one function with a per-target functor every
 // listing changes, f_ks_icols_lift_fcols_kernel<7, 2, true> 89 -> 90 VGPRs; profiles/fused_tail_share.txt)
@@ -1112,6 +1220,22 @@ void f_irows_tensor_c2(const Context &c, const MulItem *items, int ell, u64 *out
 void f_irows_tensor_c2_rs(const Context &c, const MulRsItem *items, int ell, u64 *out, int B, hipStream_t s)
 {
     launch_irows(c, SrcTensorC2<MulRsItem>{ items, c.d_mods, ell }, out, (long)c.N, B * ell, s);
+}
+void f_irows_tensor_sum(const Context &c, const MulSumItem *items, const MulTerm *terms, int ell, u64 *out, u64 *target, int B, hipStream_t s)
+{
+    DC_GEO_SWITCH(c.k2, B * ell, DC_LAUNCH((f_irows_tensor_sum_kernel<KK, LE>), grid, dim3(kTileThreads), 0, s, items, terms, ell, out, target,
+                                                    c.d_mods, c.d_itw, c.logN));
+}
+void f_frows_sum_final(const Context &c, const u64 *tmp, const MulSumItem *items, const MulTerm *terms, const u64 *acc, int B, int ell, hipStream_t s)
+{
+    const int sp = c.K - 1;
+    if (terms) {
+        DC_GEO_SWITCH(c.k2, 2 * B * ell, DC_LAUNCH((f_frows_sum_final_kernel<KK, LE, true>), grid, dim3(kTileThreads), 0, s, tmp, items, terms, acc,
+                                                            ell, sp, c.K, c.d_mods, c.d_inv_last, c.d_tw, c.logN));
+    } else {
+        DC_GEO_SWITCH(c.k2, 2 * B * ell, DC_LAUNCH((f_frows_sum_final_kernel<KK, LE, false>), grid, dim3(kTileThreads), 0, s, tmp, items, terms, acc,
+                                                            ell, sp, c.K, c.d_mods, c.d_inv_last, c.d_tw, c.logN));
+    }
 }
 void f_irows_decrypt_items(const Context &c, const BootItem *items, const SumSrc *srcs, const u64 *sk, int ell, u64 *out, int B,
                            hipStream_t s)

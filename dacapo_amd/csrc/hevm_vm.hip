@@ -479,6 +479,12 @@ void HEVM::init_context(int logN, int K, const u64 *primes, int dir_ksp, int dir
                         "is an approximate base conversion, and dividing by P q in one exact pass does not reproduce it\n", ksp, alpha);
         abort();
     }
+    ks_lazy_relin = option(OPT_KS_LAZY_RELIN) != 0;
+    if (ks_lazy_relin && (ksp > 1 || alpha > 1)) {
+        fprintf(stderr, "[dacapo_amd] option ks_lazy_relin = 1 is for SEAL-layout keys (ks_special = 1); with ks_special = %d, ks_alpha = %d the summed "
+                        "three-part ciphertext has no grouped-digit key switch here\n", ksp, alpha);
+        abort();
+    }
     zenc_head = option(OPT_ZENC_HEAD) != 0;
     // prime_bits = b (45..60; the generic-width build only): the chain CoeffModulus::Create(N, {b, b, ...}) instead of the reference's
     // 60-bit one (SEAL_HEVM.cpp:48-53) -- e.g. 51 for rescale primes of the HEaaN configuration's width
@@ -502,7 +508,7 @@ void HEVM::init_context(int logN, int K, const u64 *primes, int dir_ksp, int dir
     online_encode = option(OPT_ONLINE_ENCODE) != 0 && use_plan && !host_encoder;
     // (the options without a parity run of the re-levelled plan keep the ASAP plan)
     plan_level = (int)option(OPT_PLAN_LEVEL);
-    if (online_encode || lazy_sums || ks_hoist || ks_lazy || ks_fold_rescale || rot_compose || ksp > 1 || alpha > 1) plan_level = 0;
+    if (online_encode || lazy_sums || ks_hoist || ks_lazy || ks_fold_rescale || ks_lazy_relin || rot_compose || ksp > 1 || alpha > 1) plan_level = 0;
     lanes.resize(1);
     DC_HIP_CHECK(hipStreamCreateWithFlags(&lanes[0].stream, hipStreamNonBlocking));
     lanes[0].ws = ctx->ws0;
@@ -1918,7 +1924,7 @@ void HEVM::execute()
 {
     memset(op_counts, 0, sizeof(op_counts));
     n_keyswitch = n_ntt = 0;
-    n_hops = n_decomp = 0, n_fold = 0;
+    n_hops = n_decomp = 0, n_fold = 0, n_relin_groups = n_relin_products = 0;
     t_bootstrap = 0.0;
     int i = (int)((header.hevm_header_size + config.config_body_length) / 8), j = 0;
     for (const WireOp &op : ops) {
@@ -2329,6 +2335,31 @@ int64_t hevm_plan_lazy_groups(void *vm, int32_t *out, int64_t cap)
         }
     if (out && cap >= (int64_t)flat.size()) memcpy(out, flat.data(), flat.size() * sizeof(int32_t));
     return (int64_t)flat.size();
+}
+
+// option ks_lazy_relin: the groups of ct x ct products that the plan of the last run() relinearises with one key switch each.
+// out = [n, closing_op, (mul_op, sign) x n, ...]: per group its size, the instruction index of the addcc / negate whose result it computes, and
+// per product the mulcc's instruction index (ascending) and its sign (+1 / -1).  Return conventions of hevm_plan_lazy_groups.
+int64_t hevm_plan_relin_groups(void *vm, int32_t *out, int64_t cap)
+{
+    auto h = V(vm);
+    if (!h->plan.ready) return -1;
+    std::vector<int32_t> flat;
+    for (const auto &p : h->plan.pops)
+        if (!p.dead && p.kind == HEVM::P_MULSUM) {
+            flat.push_back((int32_t)p.ops.size());
+            flat.push_back((int32_t)p.op);
+            for (size_t k = 0; k < p.ops.size(); k++) flat.push_back((int32_t)p.ops[k]), flat.push_back((int32_t)p.signs[k]);
+        }
+    if (out && cap >= (int64_t)flat.size()) memcpy(out, flat.data(), flat.size() * sizeof(int32_t));
+    return (int64_t)flat.size();
+}
+
+// ... and how many the last run() executed: groups and the products in them, once per stream; 0 with the option off and in the loop (plan = 0)
+void hevm_last_run_relin_stats(void *vm, int64_t *groups, int64_t *products)
+{
+    if (groups) *groups = V(vm)->n_relin_groups;
+    if (products) *products = V(vm)->n_relin_products;
 }
 
 // the reference never frees a VM (no destroy symbol); a long-lived host that creates many can return one's HBM with this

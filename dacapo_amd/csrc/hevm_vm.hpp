@@ -144,8 +144,8 @@ class HEVM {
     const CrtTables &crt_tables(int ell);
 
     // ---- batched plan (plan.hpp): built on the first run() of a loaded program -----------------------------
-    enum PopKind { P_ROT, P_MULCC, P_RESCALE, P_SUM, P_NEG, P_MULP, P_ADDP, P_COPY, P_BOOT, P_MODRAISE, P_ROTSUM };
-    static constexpr int kPopKinds = 11;
+    enum PopKind { P_ROT, P_MULCC, P_RESCALE, P_SUM, P_NEG, P_MULP, P_ADDP, P_COPY, P_BOOT, P_MODRAISE, P_ROTSUM, P_MULSUM };
+    static constexpr int kPopKinds = 12;
     struct Val {
         int level = 0;
         double scale = 1.0;
@@ -180,6 +180,9 @@ class HEVM {
         std::vector<u32> elts;
         std::vector<const u64 *> keys;
         std::vector<int> ops;
+        // a P_MULSUM (option ks_lazy_relin: dst = relin(sum_k signs[k] srcs[2k] (x) srcs[2k + 1]), plan.hpp b_mul_sum_relin) lists its products: ops[k]
+        // the mulcc instruction, op the addcc / negate instruction whose result it computes
+        std::vector<int> signs;
         std::vector<int> plains; // P_ROTSUM, option hyb_double_hoist: the plaintext register multiplying rotation k before it joins the sum, or -1
     };
     struct Step {
@@ -206,6 +209,8 @@ class HEVM {
         std::vector<int> final_val; // architectural register -> value at program end
         KsItem *d_ks = nullptr;
         MulItem *d_mul = nullptr;
+        MulSumItem *d_mulsum = nullptr;      // option ks_lazy_relin: the P_MULSUM steps' items ...
+        MulTerm *d_mulsum_terms = nullptr;   // ... and their terms
         MulRsItem *d_mulrs = nullptr;        // items of the multiply steps whose rescale is folded in (Step::fold_rs)
         RsItem *d_rs = nullptr;
         EwItem *d_ew = nullptr;
@@ -239,6 +244,7 @@ class HEVM {
         std::vector<u64 *> pool; // every pool buffer ever allocated (reused across plans)
         int64_t n_keyswitch = 0, n_ntt = 0;
         int64_t n_hops = 0, n_decomp = 0; // rotation hops and the decompositions computed for them (hevm_last_run_hoist_stats)
+        int64_t n_relin_groups = 0, n_relin_products = 0; // P_MULSUM items and their terms (hevm_last_run_relin_stats)
         int64_t n_fold = 0;               // items of multiply steps that run with their rescale folded in (hevm_last_run_fold_rescale_stats)
         size_t launches = 0, max_live = 0;
         hipGraph_t graph = nullptr;
@@ -282,6 +288,9 @@ class HEVM {
     // option ks_fold_rescale = 1 (SEAL-layout keys): a multiply and the rescale that alone reads it run as one step
     // (plan_exec.hip section 4; plan.hpp b_mul_relin_rescale).  Every limb equals the default path's.
     bool ks_fold_rescale = false;
+    // option ks_lazy_relin = 1 (SEAL-layout keys): sums of single-use ct x ct products are relinearised once (plan_exec.hip section 1b;
+    // plan_relin.hpp names the groups, plan.hpp b_mul_sum_relin runs them).  Changes the rounding: off by default.
+    bool ks_lazy_relin = false;
     // option zenc_head = 1: the zero-encryptions at the start of a plan's run() transform only u (plan_zero_encrypt).  Every limb equals
     // zenc_head = 0's.  zenc_chunk_hook (hooks build, test_hooks.hip: HEVM_TEST_ZENC_CHUNK): items per chunk of that head instead of kZencChunk, 0 = unset
     bool zenc_head = true;
@@ -310,6 +319,7 @@ class HEVM {
     int64_t n_keyswitch = 0, n_ntt = 0;
     int64_t n_hops = 0, n_decomp = 0; // hevm_last_run_hoist_stats
     int64_t n_fold = 0;               // hevm_last_run_fold_rescale_stats
+    int64_t n_relin_groups = 0, n_relin_products = 0; // hevm_last_run_relin_stats
     double t_bootstrap = 0.0; // host wall time spent inside opcode 10
 
     VmAllocs allocs;   // device memory held by this VM (hevm_destroy)

@@ -30,7 +30,7 @@ enum Opt : int {
     OPT_PLAN_LANES,        // streams the plan's independent steps are spread over (1 or 2)
     OPT_PLAN_AUX_MIN_COST, // a wave's auxiliary-stream share must be worth a fork / join: at least this many cost units (key switch 8, opcode 10 5, rescale 3, element-wise 1)
     OPT_MAX_BATCH,         // items per heavy batched step
-    OPT_PLAN_LEVEL,        // how the plan levels its operations: 0 ASAP (wave = deepest producer + 1); 1 slack-aware (plan_levels.hpp): an operation off the longest chain waits inside its window [ASAP, ALAP] for a wave that already holds a step of its kind, level and target -- and a plaintext addend inside a rescale's folded sum becomes the rescale's own "+ a" (plan_exec.hip section 2); 2 that hoist alone (a measurement leg).  Same depth or less, fewer steps, every limb the same (default 1: profiles/plan_levels_ab.txt).  ASAP is kept under online_encode, hyb_lazy_sum, ks_hoist / ks_lazy_sum, ks_fold_rescale, rot_compose and grouped digits (no parity run there)
+    OPT_PLAN_LEVEL,        // how the plan levels its operations: 0 ASAP (wave = deepest producer + 1); 1 slack-aware (plan_levels.hpp): an operation off the longest chain waits inside its window [ASAP, ALAP] for a wave that already holds a step of its kind, level and target -- and a plaintext addend inside a rescale's folded sum becomes the rescale's own "+ a" (plan_exec.hip section 2); 2 that hoist alone (a measurement leg).  Same depth or less, fewer steps, every limb the same (default 1: profiles/plan_levels_ab.txt).  ASAP is kept under online_encode, hyb_lazy_sum, ks_hoist / ks_lazy_sum, ks_fold_rescale, ks_lazy_relin, rot_compose and grouped digits (no parity run there)
     OPT_CHAIN_FUSION,      // producer's last kernel runs the consumer's first phase
     OPT_HOST_ENCODER,      // encode / decode on the host (comparison only)
     OPT_ONLINE_ENCODE,     // encode plaintexts at use instead of pre-encoding the pool
@@ -42,6 +42,7 @@ enum Opt : int {
     OPT_KS_HOIST,          // SEAL-layout keys: rotation hops take the digits before the automorphism, and the hops of a plan step that read one source ciphertext share one decomposition (changes the rounding: off; with ks_special > 1 it aborts -- that mode already hoists)
     OPT_KS_LAZY_SUM,       // SEAL-layout keys, with ks_hoist: rotations (the last hop of a rotate instruction) whose single-use results are bare terms of one sum share ONE mod-down (hoist_ks.hip f_ks_gsum_kernel); 2: a rotation times a plaintext before it joins the sum is a member too, the product taken in the raised basis (changes the rounding: off; hevm_plan_lazy_groups names the groups; without ks_hoist, or with ks_special > 1, it aborts)
     OPT_KS_FOLD_RESCALE,   // SEAL-layout keys: a ct x ct multiply whose value only a rescale reads runs with that rescale as ONE five-launch sequence -- one exact pass divides by P q_{l-1} (fused_ks.hip f_dr2_icols_lift_fcols_kernel); every limb equals the default path's (off until measured; hevm_last_run_fold_rescale_stats counts the pairs; with ks_special > 1 it aborts)
+    OPT_KS_LAZY_RELIN,     // SEAL-layout keys: ct x ct products whose single-use results are only added / negated together (plan_relin.hpp: a tree of addcc / negate over mulcc leaves at one level) are relinearised by ONE key switch of the summed three-part ciphertext (batch_ops.hip b_mul_sum_relin) (changes the rounding: off; hevm_plan_relin_groups names the groups, hevm_last_run_relin_stats counts them; with ks_special > 1 it aborts)
     OPT_ZENC_HEAD,         // plan mode, the zero-encryptions made at the start of run(): 1 transforms only u -- the public key's product and the noise ride on the divide-and-round (hevm_vm.hip plan_zero_encrypt: 3l + 3 transforms per item at target level l); 0 the encryption as Encryptor::encrypt does it, batched (5l + 5).  Every limb is the same
     OPT_SEAL_COMPR,        // compression of written .seal files: 0 none, 1 zlib, 2 zstd
     OPT_TRACE,             // plan statistics on stderr (2: per wave)

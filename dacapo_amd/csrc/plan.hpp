@@ -37,6 +37,20 @@ struct MulRsItem : MulItem {
     const u64 *mul = nullptr;
     long mul_stride = 0;
 };
+// dst = relinearize(sum of `count` signed tensor products terms[first ...]) with ONE key switch (dc_ct_mul_sum_relin; fused_ks.hip
+// f_irows_tensor_sum_kernel / f_frows_sum_final_kernel).  The three-part sum is formed in exact modular arithmetic, so c0, c1 and the key-switch
+// target equal Oracle.tensor per term + poly_add / poly_sub; the rounding is that of one mod-down instead of `count`.
+struct MulTerm {  // sign * (a (x) b)
+    CtView a, b;
+    int sign;     // +1 or -1
+};
+struct MulSumItem {
+    CtView dst;
+    int first, count; // 1 <= count <= kMulSumMax
+};
+// The cap bounds the dependent walk (table entry -> pointers -> limbs, one round trip per term) that the first and the last kernel of the key
+// switch make per tile; the accumulators themselves fold every 8 terms and hold any count (fused_ks.hip tensor_sum).
+constexpr int kMulSumMax = 32;
 struct RsItem {   // dst = rescale_to_next(expr), expr = ((src | sum of `count` terms srcs[first ...]) + add on c0) * mul
     CtView src, dst;
     int first = 0, count = 0;          // count == 0: expr starts from src
@@ -123,6 +137,10 @@ void b_mul_relin_rescale(Context &c, const BatchWs &w, const MulRsItem *d_items,
                          const Handoff &h = Handoff{});
 void b_rescale(Context &c, const BatchWs &w, const RsItem *d_items, int B, int ell, hipStream_t s, const SumSrc *d_srcs = nullptr,
                const Handoff &h = Handoff{});
+// B sums of signed ct x ct products, each relinearised by ONE key switch: b_mul_relin's launch sequence (same count, same middle) with the
+// term-walking first and last kernels.  SEAL-layout keys only (aborts otherwise).  No destination may be an operand of the batch.
+void b_mul_sum_relin(Context &c, const BatchWs &w, const MulSumItem *d_items, const MulTerm *d_terms, const u64 *relin_key, int B, int ell,
+                     hipStream_t s);
 // hoisted rotations on SEAL-layout keys (hoist_ks.hip; option ks_hoist, dc_ct_rotate_hoisted): B hops over U <= B decompositions, digits taken
 // BEFORE the automorphism (oracle orc_rotate_ks_hybrid at one special prime).  d_items[b].slot indexes d_sources[0 .. U): items with the
 // identity element whose src is the source ciphertext.  w is sized as for B default hops.
@@ -167,6 +185,13 @@ void f_irows_rs_single(const Context &c, CtView src, int l, u64 *out, hipStream_
 void f_irows_decrypt(const Context &c, CtView ct, const u64 *sk, int ell, u64 *out, hipStream_t s);
 // first inverse phase of a1*b1 of every item (the tensor product's c2, computed in the loader)
 void f_irows_tensor_c2(const Context &c, const MulItem *items, int ell, u64 *out, int B, hipStream_t s);
+// ... of sum_k s_k a_k1*b_k1 of every item (b_mul_sum_relin); the sum itself is also stored to target[B][ell][N] (NTT form), where the key
+// switch's middle reads the digit a modulus owns
+void f_irows_tensor_sum(const Context &c, const MulSumItem *items, const MulTerm *terms, int ell, u64 *out, u64 *target, int B, hipStream_t s);
+// last forward phase of b_mul_sum_relin: dst = base + (acc - t) P^-1 with base = (sum_k s_k d_k0, sum_k s_k d_k1) computed in the epilogue
+// (terms != nullptr; mode 4's term-walking form) or already lying in dst (terms == nullptr; mode 1's)
+void f_frows_sum_final(const Context &c, const u64 *tmp, const MulSumItem *items, const MulTerm *terms, const u64 *acc, int B, int ell,
+                       hipStream_t s);
 // batched opcode 10: inverse ROWS phase of c0 + c1*s of every item -> out[B][ell][N] ...
 void f_irows_decrypt_items(const Context &c, const BootItem *items, const SumSrc *srcs, const u64 *sk, int ell, u64 *out, int B,
                            hipStream_t s);

@@ -14,6 +14,7 @@
 
 #include "hevm_vm.hpp"
 #include "plan_levels.hpp"
+#include "plan_relin.hpp"
 
 namespace dacapo {
 
@@ -41,6 +42,8 @@ void HEVM::build_plan()
     P.enc_groups.clear(), P.enc_arena_bytes = P.enc_scratch_bytes = 0;
     if (P.d_cont_other) (void)vm_free(P.d_cont_other), P.d_cont_other = nullptr;
     if (P.d_mulrs) (void)vm_free(P.d_mulrs), P.d_mulrs = nullptr;
+    if (P.d_mulsum) (void)vm_free(P.d_mulsum), P.d_mulsum = nullptr;
+    if (P.d_mulsum_terms) (void)vm_free(P.d_mulsum_terms), P.d_mulsum_terms = nullptr;
     for (void *p : { (void *)P.d_ks, (void *)P.d_mul, (void *)P.d_rs, (void *)P.d_ew, (void *)P.d_sum, (void *)P.d_sum_srcs, (void *)P.d_sumg, (void *)P.d_sumg_srcs, (void *)P.d_boot,
                      (void *)P.d_boot_rs, (void *)P.d_boot_zenc, (void *)P.zenc, (void *)P.boot_ue, (void *)P.boot_tmp, (void *)P.boot_pt[0], (void *)P.boot_ptx[0],
                      (void *)P.boot_pt[1], (void *)P.boot_ptx[1] })
@@ -53,7 +56,7 @@ void HEVM::build_plan()
     P.graph_exec = nullptr, P.graph = nullptr;
     P.vals.clear(), P.pops.clear(), P.steps.clear();
     P.n_keyswitch = P.n_ntt = 0;
-    P.n_hops = P.n_decomp = 0, P.n_fold = 0;
+    P.n_hops = P.n_decomp = 0, P.n_fold = 0, P.n_relin_groups = P.n_relin_products = 0;
     const size_t nreg = ciphers.size();
     const int S = streams; // independent ciphertext streams executed side by side (items of every step are replicated)
     std::vector<int> cur(nreg, -1);
@@ -148,7 +151,7 @@ void HEVM::build_plan()
             const int a = need(op.lhs, "negate");
             const Val s = P.vals[(size_t)a];
             const int nv = new_val(s.level, s.scale);
-            add_pop(P_NEG, s.level, { a }, nv);
+            add_pop(P_NEG, s.level, { a }, nv).op = (int)(&op - ops.data());
             cur[op.dst] = nv;
             break;
         }
@@ -190,7 +193,7 @@ void HEVM::build_plan()
                 abort();
             }
             const int nv = new_val(P.vals[(size_t)a].level, P.vals[(size_t)b].scale);
-            add_pop(P_SUM, P.vals[(size_t)a].level, { a, b }, nv);
+            add_pop(P_SUM, P.vals[(size_t)a].level, { a, b }, nv).op = (int)(&op - ops.data());
             cur[op.dst] = nv;
             break;
         }
@@ -215,7 +218,7 @@ void HEVM::build_plan()
                 abort();
             }
             const int nv = new_val(sa.level, sa.scale * sb.scale);
-            add_pop(P_MULCC, sa.level, { a, b }, nv);
+            add_pop(P_MULCC, sa.level, { a, b }, nv).op = (int)(&op - ops.data());
             P.n_keyswitch++, P.n_ntt += ks_ntts(sa.level);
             cur[op.dst] = nv;
             break;
@@ -312,6 +315,57 @@ void HEVM::build_plan()
         for (int s : p.srcs) V[(size_t)s].uses++;
     for (int v : cur)
         if (v >= 0) V[(size_t)v].uses++, V[(size_t)V[(size_t)v].root].pinned = true;
+
+    // ---- 1b. lazy relinearisation (option ks_lazy_relin; SEAL-layout keys) ---------------------------------------------------------
+    // relin(sum_k s_k a_k (x) b_k) is ONE key switch of the summed three-part ciphertext (plan.hpp b_mul_sum_relin) where the program's mulcc
+    // instructions run one each.  plan_relin.hpp finds the groups -- maximal trees of addcc / negate over mulcc results that nothing else reads,
+    // at one level -- on the pops as the walk above left them, before any other folding.  A group becomes ONE pop where its closing addcc /
+    // negate stood: it defines that instruction's value, whose scale the walk has already computed in program order exactly as the default run
+    // does; the tree's other pops go away and their values are never materialised.  A value counts as read by the program's end only through a
+    // RESULT register: a register that merely still names an absorbed product when the program ends is not refreshed by such a run.  That is a
+    // different rounding than n mulcc instructions (one mod-down instead of n): off by default, and the groups are exported
+    // (hevm_plan_relin_groups) for the oracle's replay.
+    if (ks_lazy_relin && !c.hybrid()) {
+        std::vector<int> named(V.size(), 0), is_result(V.size(), 0);
+        for (int v : cur)
+            if (v >= 0) named[(size_t)v]++;
+        for (uint64_t r : res_dst)
+            if (r < nreg && cur[(size_t)r] >= 0) is_result[(size_t)cur[(size_t)r]] = 1;
+        const size_t n = O.size();
+        std::vector<int> kind(n, RELIN_OTHER), src0(n, -1), src1(n, -1), readers(n, 0), level(n, 0), result(n, 0);
+        auto own_def = [&](int v) -> int { // pop whose own result (not a view of it) value v is, or -1
+            const Val &sv = V[(size_t)v];
+            return (sv.root == v && sv.def_pop >= 0 && O[(size_t)sv.def_pop].dst == v) ? sv.def_pop : -1;
+        };
+        for (size_t i = 0; i < n; i++) {
+            const Pop &p = O[i];
+            kind[i] = p.kind == P_MULCC ? RELIN_MULCC : (p.kind == P_SUM && p.srcs.size() == 2) ? RELIN_ADDCC : p.kind == P_NEG ? RELIN_NEGATE : RELIN_OTHER;
+            if (kind[i] != RELIN_OTHER) src0[i] = own_def(p.srcs[0]);
+            if (kind[i] == RELIN_MULCC || kind[i] == RELIN_ADDCC) src1[i] = own_def(p.srcs[1]);
+            readers[i] = V[(size_t)p.dst].uses - named[(size_t)p.dst], level[i] = p.level, result[i] = is_result[(size_t)p.dst];
+        }
+        RelinOps in;
+        in.n = (int)n, in.kind = kind.data(), in.src0 = src0.data(), in.src1 = src1.data(), in.readers = readers.data(), in.level = level.data();
+        in.result = result.data();
+        for (const RelinGroup &g : plan_relin_groups(in, kMulSumMax)) {
+            Pop grp;
+            grp.kind = P_MULSUM, grp.level = O[(size_t)g.members[0].mul_op].level, grp.dst = O[(size_t)g.closing_op].dst, grp.op = O[(size_t)g.closing_op].op;
+            for (const RelinMember &m : g.members) {
+                const Pop &mp = O[(size_t)m.mul_op];
+                grp.srcs.push_back(mp.srcs[0]), grp.srcs.push_back(mp.srcs[1]), grp.signs.push_back(m.sign), grp.ops.push_back(mp.op);
+            }
+            auto drop = [&](int pi) { // (no pop defines or reads this value any more)
+                O[(size_t)pi].dead = true;
+                V[(size_t)O[(size_t)pi].dst].uses = 0, V[(size_t)O[(size_t)pi].dst].def_pop = -1;
+            };
+            for (const RelinMember &m : g.members) drop(m.mul_op);
+            for (int pi : g.interior)
+                if (pi != g.closing_op) drop(pi);
+            O[(size_t)g.closing_op] = grp;
+            const int64_t fewer = (int64_t)g.members.size() - 1;
+            P.n_keyswitch -= fewer, P.n_ntt -= fewer * ks_ntts(grp.level);
+        }
+    }
 
     // ---- 2. fold ct+ct chains into n-ary sums (only through intermediates nothing else observes) ------------------
     for (Pop &p : O) {
@@ -507,11 +561,11 @@ void HEVM::build_plan()
         };
         for (size_t k = 0; k < n; k++) {
             const Pop &p = O[(size_t)live[k]];
-            const bool heavy = p.kind == P_ROT || p.kind == P_MULCC || p.kind == P_RESCALE || p.kind == P_BOOT || p.kind == P_ROTSUM;
+            const bool heavy = p.kind == P_ROT || p.kind == P_MULCC || p.kind == P_RESCALE || p.kind == P_BOOT || p.kind == P_ROTSUM || p.kind == P_MULSUM;
             kind[k] = (int)p.kind, level[k] = p.level, target[k] = p.target_level, asap[k] = p.wave;
             cap[k] = (int)std::max<size_t>(1, (heavy ? (size_t)max_batch : (size_t)4096) / (size_t)S); // (section 4's chunk)
             fixed[k] = p.kind == P_ROTSUM;
-            launches[k] = p.kind == P_ROT || p.kind == P_MULCC || p.kind == P_ROTSUM ? 5 : p.kind == P_RESCALE ? 3 : p.kind == P_BOOT ? 4 : 1;
+            launches[k] = p.kind == P_ROT || p.kind == P_MULCC || p.kind == P_ROTSUM || p.kind == P_MULSUM ? 5 : p.kind == P_RESCALE ? 3 : p.kind == P_BOOT ? 4 : 1;
             for (int s : p.srcs) {
                 const int dp = live_def(s, false);
                 if (dp >= 0) prod.push_back(idx[(size_t)dp]);
@@ -544,6 +598,8 @@ void HEVM::build_plan()
     std::vector<KsItem> h_ks;
     std::vector<MulItem> h_mul;
     std::vector<MulRsItem> h_mulrs;
+    std::vector<MulSumItem> h_mulsum;
+    std::vector<MulTerm> h_mulsum_terms;
     std::vector<RsItem> h_rs;
     std::vector<EwItem> h_ew;
     std::vector<SumItem> h_sum;
@@ -609,7 +665,7 @@ void HEVM::build_plan()
                 });
             else if (kind == P_ROT && !c.hybrid() && option(OPT_KS_ITEMS_FAST))
                 std::stable_sort(kv.second.begin(), kv.second.end(), [&](int x, int y) { return O[(size_t)x].elt < O[(size_t)y].elt; });
-            const bool heavy = kind == P_ROT || kind == P_MULCC || kind == P_RESCALE || kind == P_BOOT || kind == P_ROTSUM;
+            const bool heavy = kind == P_ROT || kind == P_MULCC || kind == P_RESCALE || kind == P_BOOT || kind == P_ROTSUM || kind == P_MULSUM;
             const size_t chunk = std::max<size_t>(1, (heavy ? (size_t)max_batch : (size_t)4096) / (size_t)S);
             if (kind == P_ROTSUM) { // whole groups, counted by their rotations
                 for (size_t off = 0; off < kv.second.size();) {
@@ -726,7 +782,7 @@ void HEVM::build_plan()
     // steps of one wave are mutually independent: the costliest stays on the main stream, the rest is balanced over
     // (main, auxiliary) when the auxiliary share is worth a fork/join (>= 3 launches)
     if (plan_lanes >= 2) {
-        auto cost = [](const Step &st) { return st.kind == P_ROT || st.kind == P_MULCC || st.kind == P_ROTSUM ? 8 : st.kind == P_BOOT ? 5 : st.kind == P_RESCALE ? 3 : 1; };
+        auto cost = [](const Step &st) { return st.kind == P_ROT || st.kind == P_MULCC || st.kind == P_ROTSUM || st.kind == P_MULSUM ? 8 : st.kind == P_BOOT ? 5 : st.kind == P_RESCALE ? 3 : 1; };
         for (size_t a = 0; a < P.steps.size();) {
             size_t b = a;
             while (b < P.steps.size() && P.steps[b].wave == P.steps[a].wave) b++;
@@ -967,6 +1023,17 @@ void HEVM::build_plan()
                 for (int q = 0; q < S; q++)
                     h_mul.push_back(MulItem{ view(O[(size_t)pi].srcs[0], q), view(O[(size_t)pi].srcs[1], q), view(O[(size_t)pi].dst, q) });
             break;
+        case P_MULSUM: // one item per group and stream; its terms in the group's program order
+            st.first = (int)h_mulsum.size();
+            for (int pi : step_pops[s])
+                for (int q = 0; q < S; q++) {
+                    const Pop &gp = O[(size_t)pi];
+                    h_mulsum.push_back(MulSumItem{ view(gp.dst, q), (int)h_mulsum_terms.size(), (int)gp.signs.size() });
+                    for (size_t k = 0; k < gp.signs.size(); k++)
+                        h_mulsum_terms.push_back(MulTerm{ view(gp.srcs[2 * k], q), view(gp.srcs[2 * k + 1], q), gp.signs[k] });
+                    P.n_relin_groups++, P.n_relin_products += (int64_t)gp.signs.size();
+                }
+            break;
         case P_RESCALE:
             st.first = (int)h_rs.size();
             for (int pi : step_pops[s])
@@ -1109,7 +1176,7 @@ void HEVM::build_plan()
             boot_tmax = std::max(boot_tmax, st.target);
             break;
         }
-        if (st.kind == P_ROT || st.kind == P_MULCC || st.kind == P_ROTSUM) {
+        if (st.kind == P_ROT || st.kind == P_MULCC || st.kind == P_ROTSUM || st.kind == P_MULSUM) {
             need_t = std::max(need_t, B * l), need_d = std::max(need_d, B * std::max<size_t>(l, 2));
             need_e = std::max(need_e, B * (c.hybrid() ? (size_t)c.hyb_ext((int)l) : l * l));
             need_a = std::max(need_a, B * 2 * (l + (size_t)c.ksp)), need_m = std::max(need_m, B * 2 * l);
@@ -1210,6 +1277,7 @@ void HEVM::build_plan()
         P.d_boot = upload(h_boot), P.d_boot_rs = upload(h_brs), P.d_boot_zenc = upload(h_bz);
     }
     P.d_mulrs = upload(h_mulrs);
+    P.d_mulsum = upload(h_mulsum), P.d_mulsum_terms = upload(h_mulsum_terms);
     P.d_ks = upload(h_ks), P.d_mul = upload(h_mul), P.d_rs = upload(h_rs), P.d_ew = upload(h_ew), P.d_sum = upload(h_sum);
     P.h_ew = h_ew;
     P.d_sum_srcs = upload(h_srcs);
@@ -1272,12 +1340,12 @@ void HEVM::build_plan()
     P.ready = true;
     if (plan_graph) capture_plan(); // part of the (untimed) preparation, like the plan itself
     if (option(OPT_TRACE)) {
-        static const char *kn[] = { "rot", "mulcc", "rescale", "sum", "neg", "mulp", "addp", "copy", "boot", "modraise", "rotsum" };
+        static const char *kn[] = { "rot", "mulcc", "rescale", "sum", "neg", "mulp", "addp", "copy", "boot", "modraise", "rotsum", "mulsum" };
         size_t nsteps[kPopKinds] = { 0 }, nitems[kPopKinds] = { 0 };
         std::map<std::pair<int, int>, std::pair<size_t, size_t>> ks; // (kind, level) -> steps, items
         for (const Step &st : P.steps) {
             nsteps[st.kind]++, nitems[st.kind] += (size_t)st.count;
-            if (st.kind == P_ROT || st.kind == P_MULCC || st.kind == P_RESCALE || st.kind == P_BOOT || st.kind == P_ROTSUM) {
+            if (st.kind == P_ROT || st.kind == P_MULCC || st.kind == P_RESCALE || st.kind == P_BOOT || st.kind == P_ROTSUM || st.kind == P_MULSUM) {
                 auto &e = ks[{ (int)st.kind, st.level }];
                 e.first++, e.second += (size_t)st.count;
             }
@@ -1337,7 +1405,7 @@ void HEVM::build_plan()
             a = b;
         }
         for (const Step &st : P.steps)
-            launches += st.kind == P_ROT || st.kind == P_MULCC || st.kind == P_ROTSUM ? 5 : st.kind == P_RESCALE ? 3 : st.kind == P_BOOT ? 4 : 1;
+            launches += st.kind == P_ROT || st.kind == P_MULCC || st.kind == P_ROTSUM || st.kind == P_MULSUM ? 5 : st.kind == P_RESCALE ? 3 : st.kind == P_BOOT ? 4 : 1;
         fprintf(stderr, "[dacapo_amd] plan levels: plan_level %d moved %d operations: %zu steps in %d waves, %zu waves with more than one step, %zu links, "
                         "%zu step launches (5 per key switch, 3 per rescale, 4 per opcode 10, 1 per limb-wise step, -1 per link), %zu live buffers, "
                         "%zu pool buffers (%.3f GB)\n",
@@ -1371,6 +1439,7 @@ void HEVM::issue_step(const Step &st, hipStream_t q)
             break;
         }
         b_mul_relin(c, w, P.d_mul + st.first, keys.relin, st.count, st.level, q, st.h); break;
+    case P_MULSUM: b_mul_sum_relin(c, w, P.d_mulsum + st.first, P.d_mulsum_terms, keys.relin, st.count, st.level, q); break;
     case P_RESCALE: b_rescale(c, w, P.d_rs + st.first, st.count, st.level, q, P.d_sum_srcs, st.h); break;
     case P_SUM:
         if (st.gcount > 0)
@@ -1448,7 +1517,7 @@ void HEVM::issue_plan(hipStream_t s)
     }
     bump_epoch(s);
     if (step_profile) {
-        static const char *kn[] = { "rot", "mulcc", "rescale", "sum", "neg", "mulp", "addp", "copy", "boot", "modraise", "rotsum" };
+        static const char *kn[] = { "rot", "mulcc", "rescale", "sum", "neg", "mulp", "addp", "copy", "boot", "modraise", "rotsum", "mulsum" };
         double total = 0;
         for (auto &kv : prof) total += kv.second.second;
         fprintf(stderr, "[dacapo_amd] step profile (synchronised after every step): %.2f ms in %zu steps\n", total * 1e3, P.steps.size());
@@ -1618,6 +1687,7 @@ void HEVM::run_plan()
         if (op.opcode <= 10) op_counts[op.opcode]++;
     n_keyswitch = P.n_keyswitch, n_ntt = P.n_ntt;
     n_hops = P.n_hops, n_decomp = P.n_decomp, n_fold = P.n_fold;
+    n_relin_groups = P.n_relin_groups, n_relin_products = P.n_relin_products;
     t_bootstrap = 0.0;
     const long ps = (long)c.K * (long)c.N;
     if (plan_graph) { // the plan is a fixed launch sequence: recorded once (normally by preprocess()), replayed as one graph launch
@@ -1640,6 +1710,7 @@ void HEVM::run_plan()
     for (size_t r = 0; r < P.final_val.size() && r < ciphers.size(); r++) {
         const int v = P.final_val[r];
         if (v < 0) continue;
+        if (!P.vals[(size_t)P.vals[(size_t)v].root].buf) continue; // (option ks_lazy_relin: an absorbed product that a non-result register still names)
         reg_base[r] = P.vals[(size_t)P.vals[(size_t)v].root].buf;
         ciphers[r].data = reg_base[r] + (size_t)sel * (size_t)2 * c.K * c.N;
         ciphers[r].poly_stride = ps;

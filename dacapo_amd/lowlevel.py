@@ -77,6 +77,9 @@ def _bind(path):
         L.dc_ct_mul_plain.argtypes = [vp, u64p, lng, u64p, lng, u64p, i32, vp]
         L.dc_ct_mul_relin.argtypes = [vp, u64p, lng, u64p, lng, u64p, lng, u64p, i32, vp]
         L.dc_ct_mul_relin_rescale.argtypes = [vp, u64p, lng, u64p, lng, u64p, lng, u64p, u64p, vp, i32, vp]
+        L.dc_ct_mul.argtypes = [vp, u64p, lng, u64p, lng, u64p, lng, i32, vp]
+        L.dc_ct_relin.argtypes = [vp, u64p, lng, u64p, lng, u64p, i32, vp]
+        L.dc_ct_mul_sum_relin.argtypes = [vp, u64p, lng, vp, vp, vp, i32, lng, u64p, i32, vp]
         L.dc_ct_rotate_hop.argtypes = [vp, u64p, lng, u64p, lng, C.c_uint32, u64p, i32, vp]
         L.dc_ct_rotate_hoisted.argtypes = [vp, vp, lng, u64p, lng, vp, vp, i32, i32, vp]
         L.dc_ct_rotate_sum_hoisted.argtypes = [vp, u64p, lng, vp, lng, vp, vp, vp, vp, i32, i32, vp]
@@ -178,6 +181,14 @@ class Context:
             (self.L.dc_ntt_inverse if inverse else self.L.dc_ntt_forward)(self.h, *args)
         else:
             self.L.dc_ntt_variant(self.h, variant, int(inverse), *args)
+
+    def mul_sum_relin(self, dst: int, dst_stride: int, a_ptrs, b_ptrs, signs, src_stride: int, relin_key: int, ell: int, stream=None):
+        """dc_ct_mul_sum_relin: dst = relin(sum_k signs[k] a_k (x) b_k) with one key switch; a_ptrs / b_ptrs are device pointers (ints)"""
+        n = len(signs)
+        assert len(a_ptrs) == n and len(b_ptrs) == n
+        pa, pb = (C.c_void_p * n)(*a_ptrs), (C.c_void_p * n)(*b_ptrs)
+        sg = (C.c_int32 * n)(*[int(s) for s in signs])
+        self.L.dc_ct_mul_sum_relin(self.h, dst, dst_stride, pa, pb, sg, n, src_stride, relin_key, ell, stream)
 
     def elt_from_step(self, step: int) -> int:
         return int(self.L.dc_galois_elt_from_step(self.h, step))

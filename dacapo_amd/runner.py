@@ -104,6 +104,9 @@ def bind_vm_lib(path):
     L.hevm_last_run_fold_rescale_stats.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)]
     L.hevm_plan_lazy_groups.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32), ctypes.c_int64]
     L.hevm_plan_lazy_groups.restype = ctypes.c_int64
+    L.hevm_plan_relin_groups.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32), ctypes.c_int64]
+    L.hevm_plan_relin_groups.restype = ctypes.c_int64
+    L.hevm_last_run_relin_stats.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
     L.hevm_set_streams.argtypes = [ctypes.c_void_p, ctypes.c_int]
     L.hevm_select_stream.argtypes = [ctypes.c_void_p, ctypes.c_int]
     L.hevm_last_run_bootstrap_seconds.argtypes = [ctypes.c_void_p]
@@ -396,6 +399,27 @@ class HEVM:
         hops, dec = ctypes.c_int64(), ctypes.c_int64()
         self.lw.hevm_last_run_hoist_stats(self.vm, ctypes.byref(hops), ctypes.byref(dec))
         return {"hops": hops.value, "decompositions": dec.value}
+
+    def relin_groups(self):
+        """option ks_lazy_relin: the plan's product sums that one key switch relinearises (hevm_plan_relin_groups) as
+        [(closing_op, [(mul_op, sign), ...]), ...]; the raw return value (0 / -1) when there is no list"""
+        n = self.lw.hevm_plan_relin_groups(self.vm, None, 0)
+        if n <= 0:
+            return int(n)
+        buf = (ctypes.c_int32 * n)()
+        self.lw.hevm_plan_relin_groups(self.vm, buf, n)
+        out, i = [], 0
+        while i < n:
+            k = buf[i]
+            out.append((buf[i + 1], [(buf[i + 2 + 2 * j], buf[i + 3 + 2 * j]) for j in range(k)]))
+            i += 2 + 2 * k
+        return out
+
+    def relin_stats(self):
+        """option ks_lazy_relin: groups and the products in them that the last run() executed (once per stream)"""
+        g, p = ctypes.c_int64(), ctypes.c_int64()
+        self.lw.hevm_last_run_relin_stats(self.vm, ctypes.byref(g), ctypes.byref(p))
+        return {"groups": g.value, "products": p.value}
 
     def fold_rescale_stats(self):
         """option ks_fold_rescale: items (multiply-rescale pairs, once per stream) the last run() executed as one merged step"""

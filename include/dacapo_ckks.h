@@ -96,6 +96,25 @@ void dc_ct_mul_plain(dc_context *ctx, uint64_t *dst, long dst_stride, const uint
 /* Evaluator::multiply + relinearize_inplace   SEAL_HEVM.cpp:315-316 */
 void dc_ct_mul_relin(dc_context *ctx, uint64_t *dst, long dst_stride, const uint64_t *a, long a_stride, const uint64_t *b,
                      long b_stride, const uint64_t *relin_key, int ell, void *stream);
+/* Evaluator::multiply alone: the three-part product, polynomials `dst_stride` apart in dst3 -- d0 = a0 b0, d1 = a0 b1 + a1 b0, d2 = a1 b1
+ * (oracle Oracle.tensor).  dst3 must not overlap a or b. */
+void dc_ct_mul(dc_context *ctx, uint64_t *dst3, long dst_stride, const uint64_t *a, long a_stride, const uint64_t *b, long b_stride, int ell,
+               void *stream);
+/* Evaluator::relinearize_inplace of a three-part ciphertext (polynomials `src_stride` apart): dst = (d0, d1) + KS(d2), dc_keyswitch's path,
+ * so either key mode.  dst may be src3 (in place).  dc_ct_relin(dc_ct_mul(a, b)) equals dc_ct_mul_relin(a, b) limb for limb. */
+void dc_ct_relin(dc_context *ctx, uint64_t *dst, long dst_stride, const uint64_t *src3, long src_stride, const uint64_t *relin_key, int ell,
+                 void *stream);
+/* EXTENSION (not SEAL's rounding for count > 1): dst = relinearize(sum_k signs[k] * as[k] (x) bs[k]) with ONE key-switch sequence -- the
+ * launches of one dc_ct_mul_relin whatever the count.  The three-part sum T = sum_k signs[k] * Oracle.tensor(as[k], bs[k]) is formed in exact
+ * modular arithmetic (poly_add / poly_sub), then dst = (T0, T1) + KS(T2), limb for limb Oracle.keyswitch(T2, relin, T0, T1); count = 1 with
+ * sign +1 is dc_ct_mul_relin exactly.  as / bs: HOST arrays of `count` device pointers to ciphertexts of poly stride `src_stride`; signs: HOST
+ * array of +1 / -1.  1 <= count <= DC_CT_MUL_SUM_MAX; more aborts with a message (split the sum and dc_ct_add the parts).  as[k] may equal bs[k]
+ * (a square), an operand may appear in several terms, dst may be an operand (it is then written through scratch and copied: one more launch).
+ * SEAL-layout contexts only (a grouped-digit context aborts with a message).  Scratch is kept in the context.  The item table is copied
+ * synchronously: the call waits for earlier work on `stream`. */
+#define DC_CT_MUL_SUM_MAX 32
+void dc_ct_mul_sum_relin(dc_context *ctx, uint64_t *dst, long dst_stride, const uint64_t *const *as, const uint64_t *const *bs,
+                         const int32_t *signs, int count, long src_stride, const uint64_t *relin_key, int ell, void *stream);
 /* Evaluator::multiply + relinearize_inplace [+ add_plain + multiply_plain by a constant polynomial] + rescale_to_next, limb for limb;
  * dst at level ell-1.  add_plain: [>= ell][N] NTT form or NULL.  mul_const: HOST array of ell residues (the constant polynomial's value
  * modulo each prime) or NULL.  ell >= 2.  dst may be a or b; a may be b.  SEAL-layout contexts only.

@@ -141,6 +141,14 @@ void hevm_last_run_fold_rescale_stats(void *vm, int64_t *pairs);
  * n_1, op ...]: per group its size and its rotations' instruction indices.  Returns the length of that list (written if cap suffices), 0 without
  * groups, -1 before the first run() and under option "plan" = 0 (the loop executes every rotate on its own).  Test infrastructure: oracle/oracle.py OracleVM.set_lazy_groups replays exactly these groups. */
 int64_t hevm_plan_lazy_groups(void *vm, int32_t *out, int64_t cap);
+/* option "ks_lazy_relin" (SEAL-layout keys, off by default): the groups of ct x ct products that the last run()'s plan relinearises with ONE
+ * key switch each -- maximal trees of addcc / negate over mulcc results that nothing else reads, at one level.  out = [n, closing_op,
+ * (mul_op, sign) x n, ...]: per group its size, the instruction index of the addcc / negate whose result the group computes, and per product
+ * the mulcc's instruction index (ascending) and its sign +1 / -1.  Returns as hevm_plan_lazy_groups does: the length, 0 without groups, -1
+ * before the first run() or under plan = 0. */
+int64_t hevm_plan_relin_groups(void *vm, int32_t *out, int64_t cap);
+/* ... and the counts of the last run(): groups and the products in them, once per stream (0 with the option off or under plan = 0) */
+void hevm_last_run_relin_stats(void *vm, int64_t *groups, int64_t *products);
 /* Throughput mode: run `n` independent ciphertext streams of the same program side by side (shared keys and
  * plaintexts; every step of the batched plan processes all streams in one launch sequence).  Call before load();
  * encrypt / decrypt / decrypt_result / getCtxt then address the stream chosen with hevm_select_stream. */
@@ -168,7 +176,7 @@ void hevm_load_ctxt(void *vm, int64_t reg, const char *path);
 
 /* Run-time options (dacapo_amd/csrc/options.hpp holds the ONE table: names, defaults, meaning).  VM options -- "logn", "primes",
  * "prime_bits", "ks_special", "ks_alpha", "secret_hw", "rot_compose", "plan", "plan_graph", "plan_lanes", "max_batch", "chain_fusion", "host_encoder",
- * "online_encode", "fold_rescale_boot", "zenc_head", "hyb_mfma", "hyb_fuse", "seal_compr", "trace", "step_profile" -- are read when a VM (or kernel-level
+ * "online_encode", "fold_rescale_boot", "ks_lazy_relin", "zenc_head", "hyb_mfma", "hyb_fuse", "seal_compr", "trace", "step_profile" -- are read when a VM (or kernel-level
  * context) is created; launch-shape thresholds -- "small_tile_wgs", "tiny_tile_wgs", "ntt_full_min_limbs", ... -- at every launch.
  * Process-wide, not thread-safe (like the rest of this ABI).  An unknown name aborts with the list of names.  A caller that only knows
  * the reference's 18 symbols sets the same names through the single environment variable DACAPO_HEVM_OPTIONS="name=value,...". */

@@ -233,6 +233,8 @@ rows.append("| `ks_hoist_ab.txt` | hoisted rotations on SEAL-layout keys (option
 rows.append("| `ks_lazy_sum_ab.txt` | lazy sums on SEAL-layout keys (option `ks_lazy_sum` with `ks_hoist`): `run()` of the headline and of its 13-prime lowering under the default options, `ks_hoist`, and `ks_hoist` with `ks_lazy_sum` = 1 and 2: time, groups and members, hops, decompositions, rms against the torch logits | `python tools/legs/ks_lazy_sum_ab.py --out profiles/ks_lazy_sum_ab.txt` |")
 rows.append("| `zenc_head_ab.txt` | the zero-encryption head of `run()` (option `zenc_head`, `HEVM::plan_zero_encrypt`): the head's own duration and its kernels on the parent commit and under both values (kernel traces of plain `bench.py` runs, `tools/summarize/zenc_head.py`), `run()` of the headline on three VMs with the option 0, 1, 0 (0/0 spread beside the difference), the chunk-size sweep 64 / 128 / 192 / 256 on the hooks build, the head's scratch under both values, `bench.py`'s `ms_per_step` on the parent commit and on the branch on one box, and the compile-time VGPR / LDS / scratch figures of the new kernels | `python tools/legs/zenc_head_ab.py --out profiles/zenc_head_ab.txt`; `DACAPO_AMD_HOOKS=1 python tools/legs/zenc_head_ab.py --sweep --out profiles/zenc_head_ab.txt` |")
 rows.append("| `ks_fold_rescale_ab.txt` | a rescale folded into the multiply's key switch (option `ks_fold_rescale`, `dc_ct_mul_relin_rescale`): `dc_ct_mul_relin` + `dc_ct_rescale` against the one call under device events at N = 2^15 / 2, 3, 5, 13 primes and N = 2^16 / 24 primes, `run()` of the headline and of its 13-prime lowering with the option off, on, off (off/off spread beside the difference), pair counts, and the compile-time VGPR / LDS / scratch figures of the new kernels | `python tools/legs/ks_fold_rescale_ab.py --out profiles/ks_fold_rescale_ab.txt` |")
+rows.append("| `ks_lazy_relin_ab.txt` | lazy relinearisation at the kernel-level ABI (`dc_ct_mul_sum_relin`): one call against n x `dc_ct_mul_relin` + (n - 1) x `dc_ct_add` for n = 2, 3, 8 products at N = 2^15, l = 2 and 13: us per sum, mean and spread of the alternating rounds (the call includes its synchronous copy of the term table); `run()` of `suite/Multivariate` on three VMs with option `ks_lazy_relin` 0 / 1 / 0: ms, groups, key switches, rms, on - off beside the off/off spread; `bench.py`'s line against the parent commit's library | `python tools/legs/ks_lazy_relin_ab.py --out profiles/ks_lazy_relin_ab.txt` |")
+rows.append("| `ks_lazy_relin_regs.txt` | compile-time figures, not runs: VGPRs, SGPRs, scratch, occupancy and LDS of `f_irows_tensor_sum_kernel` and `f_frows_sum_final_kernel` beside `f_irows_tensor_c2`'s kernel and `f_frows_final_kernel` modes 4 and 1, every tile geometry; `b_tensor_sum_kernel` beside `b_tensor_kernel` | `hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage -c fused_ks.hip` (and `batch_ops.hip`) |")
 rows.append("| `ks_mac_regs.txt` | compile-time figures, not runs: VGPRs, SGPRs, spills, scratch and LDS of `f_ks_gmac_kernel`, `f_ks_gsum_kernel`, `hyb_mac_kernel` and `hyb_mac_group_kernel` before and after their shared pieces moved to `ks_mac.hpp` / `galois.hpp`, both builds, with `identical` / `differs` per instantiation, and which pieces were left written out because of what they cost | `hipcc -S --cuda-device-only` of parent and branch, `python tools/experiments/asm_compare.py <parent dir> <branch dir> --table '<regex>'` |")
 rows.append("| `fused_tail_share.txt` | compile-time figures, not runs: every kernel of `fused_ks.hip` (and of `hybrid_fused.hip`, `hoist_ks.hip`, which include the touched header) against the parent's listing after the divide-and-round middle (plain / noise), the `a1·b1` loader, the rounding arithmetic and the merged-launch dispatch got one definition each, both builds, the renamed kernels paired by hand; and each shared form that was built and NOT kept (tensor terms, continuations, target loop, `base_folded`) with the VGPR figures that decided it | `hipcc -S --cuda-device-only` of parent and branch, `python tools/experiments/asm_compare.py <parent dir> <branch dir> --rename 'OLD=NEW' [--table '<regex>']` |")
 rows.append(f"| `plan_levels_ab.txt` | slack-aware levelling of the plan and the addend hoisted out of a rescale's folded sum (option `plan_level`): the headline plan under 0 (ASAP), 1 and 2 (the hoist alone) from the trace — steps by kind, waves, waves with more than one step, links, launches, live buffers, pool — then `run()` on three VMs with the option 0, 1, 0 in one process: {first_lines('plan_levels_ab.txt', 'run headline 1 - 0', 1)}; the parent commit's library with `plan_lanes` 1 and 2; `bench.py` on the parent's library and on this one: {first_lines('plan_levels_ab.txt', 'ms_per_step [0-9.]+  value', 3)}; kernel-trace runs of both: {first_lines('plan_levels_ab.txt', 'last run.. ', 2)}; the decision | `python tools/legs/plan_levels_ab.py --out profiles/plan_levels_ab.txt`; `python tools/legs/plan_levels_ab.py --lanes`; `python bench.py --gpus 1 --steps 10 --warmup 3`; `rocprofv3 --kernel-trace --stats -- python3 tools/legs/headline_only.py 3 [--opt plan_level=1]`, `tools/summarize/timeline_gaps.py` |")
