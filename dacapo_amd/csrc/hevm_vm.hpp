@@ -3,6 +3,7 @@
 // SEAL objects replaced by HBM-resident limb arrays and HIP launches.
 #pragma once
 #include "wire_parse.hpp"
+#include <algorithm>
 #include <complex>
 #include <deque>
 #include <map>
@@ -40,7 +41,6 @@ inline hipError_t vm_free(void *p)
     if (p && g_vm_allocs) g_vm_allocs->live.erase(p);
     return hipFree(p);
 }
-
 
 // the wire structs (WireHeader, WireConfigBody, WireOp) and the two files' parsers live in a host-only TU: wire_parse.hpp
 
@@ -146,6 +146,12 @@ class HEVM {
     // ---- batched plan (plan.hpp): built on the first run() of a loaded program -----------------------------
     enum PopKind { P_ROT, P_MULCC, P_RESCALE, P_SUM, P_NEG, P_MULP, P_ADDP, P_COPY, P_BOOT, P_MODRAISE, P_ROTSUM, P_MULSUM };
     static constexpr int kPopKinds = 12;
+    // A step by its kind alone: name in traces; heavy = key switch, rescale or opcode 10: max_batch items to a step where limb-wise kinds take 4096
+    // (step_chunk); launches of one step as the trace's "step launches" and the levelling pass count them (not the ~launches estimate that gates capture)
+    struct KindTraits { const char *name; bool heavy; int launches; };
+    static constexpr KindTraits kKind[kPopKinds] = { { "rot", true, 5 },  { "mulcc", true, 5 }, { "rescale", true, 3 }, { "sum", false, 1 },      { "neg", false, 1 },   { "mulp", false, 1 },
+                                                     { "addp", false, 1 }, { "copy", false, 1 }, { "boot", true, 4 },    { "modraise", false, 1 }, { "rotsum", true, 5 }, { "mulsum", true, 5 } };
+    size_t step_chunk(PopKind k) const { return std::max<size_t>(1, (kKind[k].heavy ? (size_t)max_batch : (size_t)4096) / (size_t)streams); } // pseudo-ops per step
     struct Val {
         int level = 0;
         double scale = 1.0;
@@ -201,8 +207,11 @@ class HEVM {
         // built graph (option plan_graph = 2, capture_plan_dag)
         std::vector<const u64 *> reads, writes;
     };
+    // The device memory a plan allocates for itself (item tables, arenas, the links' first-phase buffers, both lanes' scratch) comes from plan_alloc, which
+    // lists it in `owned`; release_plan frees that list and resets everything but pool and events.  The typed pointers below are read, never freed.
     struct Plan {
         bool ready = false;
+        std::vector<void *> owned;
         std::vector<Val> vals;
         std::vector<Pop> pops;
         std::vector<Step> steps;
@@ -228,7 +237,6 @@ class HEVM {
         int *d_enc_overflow = nullptr;
         size_t enc_arena_bytes = 0, enc_scratch_bytes = 0;
         std::vector<EwItem> h_ew;            // host copy of the elementwise item table (modraise launches its NTTs per item)
-        std::vector<u64 *> handoff_bufs;     // first-phase buffers of fused consumer steps
         size_t n_fused = 0;
         // opcode 10: item table, the divide-and-round items of the zero-encryptions, the zero-encryption arena and scratch
         BootItem *d_boot = nullptr;
@@ -256,6 +264,9 @@ class HEVM {
     bool capture_plan_dag();
     void issue_step(const Step &st, hipStream_t q);
     void drop_plan_graph();
+    void *plan_alloc(size_t bytes);
+    void release_plan();
+    void issue_head(hipStream_t s);
     void issue_plan(hipStream_t s);
     bool use_plan = true;
     bool test_zero_enc = false; // hevm_test_zero_encryption: encryptions of zero are (0, 0) -- INSECURE, parity tests of opcode 10 only
@@ -268,6 +279,13 @@ class HEVM {
     void set_streams(int n);
     void select_stream(int s);
     void build_plan();
+    // leaves of build_plan: they read the finished values, pops and steps and write Plan fields (and, on-line encode, where a plaintext lies)
+    CtView plan_view(int v, int stream) const;
+    const u64 *plain_ptr(int reg) const { return reg >= 0 ? plains.at((size_t)reg).d : nullptr; }
+    std::pair<int, int> push_terms(std::vector<SumSrc> &h_srcs, const Pop &p, int stream) const;
+    void place_online_encode(const std::vector<std::vector<int>> &step_pops);
+    void build_boot_tables(const std::vector<std::pair<int, int>> &boot_pops, int boot_tmax, size_t need_bpt, size_t need_bptx, std::vector<SumSrc> &h_srcs, size_t &need_d, size_t &need_m);
+    void report_plan(const double (&sum_stat)[5], int max_wave, int levels_moved) const;
     void run_plan();
     void boot_item(CtView src, int src_level, double src_scale, hevm_ctxt &dst, int target_level);
     void plan_zero_encrypt(int first, int B, int t, hipStream_t s);

@@ -20,43 +20,125 @@ namespace dacapo {
 
 #define ks_ntts(ell) ks_ntt_count(c, (ell))
 
-template <class T>
-static T *upload(const std::vector<T> &v)
+// every device allocation a plan makes for itself (hevm_vm.hpp Plan::owned): hevm_destroy sees it like any other of the VM's, release_plan returns it
+void *HEVM::plan_alloc(size_t bytes)
 {
-    T *d = nullptr;
-    DC_HIP_CHECK(vm_malloc(&d, std::max<size_t>(v.size(), 1) * sizeof(T)));
+    void *d = nullptr;
+    DC_HIP_CHECK(vm_malloc(&d, bytes));
+    plan.owned.push_back(d);
+    return d;
+}
+
+template <class T>
+static T *upload(HEVM &vm, const std::vector<T> &v)
+{
+    T *d = static_cast<T *>(vm.plan_alloc(std::max<size_t>(v.size(), 1) * sizeof(T)));
     if (!v.empty()) DC_HIP_CHECK(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
     return d;
+}
+
+// The end of a plan: its device memory and its graph go and every field -- tables, counters, sizes -- is a default again, except the two
+// that persist across plans on purpose: the pool's buffers (set_streams frees them) and the fork / join events are reused.
+void HEVM::release_plan()
+{
+    for (void *p : plan.owned) (void)vm_free(p);
+    drop_plan_graph();
+    Plan fresh;
+    fresh.pool = std::move(plan.pool), fresh.events = std::move(plan.events);
+    plan = std::move(fresh);
+}
+
+// the limbs of value v in stream `stream`: its pool (or home) buffer, which a view shares with the value it views
+CtView HEVM::plan_view(int v, int stream) const
+{
+    u64 *b = plan.vals[(size_t)plan.vals[(size_t)v].root].buf;
+    if (!b) {
+        fprintf(stderr, "[dacapo_amd] plan: value %d has no buffer (internal error)\n", v);
+        abort();
+    }
+    const long ps = (long)ctx->K * (long)ctx->N;
+    return CtView{ b + (size_t)stream * (size_t)(2 * ps), ps };
+}
+
+// the terms of an n-ary sum, or of the sum folded into a rescale or an opcode 10, appended to the table all three share: (first, count)
+std::pair<int, int> HEVM::push_terms(std::vector<SumSrc> &h_srcs, const Pop &p, int stream) const
+{
+    const int first = (int)h_srcs.size();
+    for (size_t k = 0; k < p.srcs.size(); k++) h_srcs.push_back(SumSrc{ plan_view(p.srcs[k], stream), plain_ptr(p.src_plain.empty() ? -1 : p.src_plain[k]) });
+    return { first, (int)p.srcs.size() };
+}
+
+// "A's last kernel can compute B's first phase" by kind, level and target (plan.hpp Handoff): a multiply hands to the rescale at its level; a
+// rescale to the multiply or opcode 10 one level down; a rotation hop outside the boot context and the hoisted path to the opcode 10 at its level.
+// a_merged: a multiply step that runs its rescales itself (option ks_fold_rescale) and ends as a rescale does.  Sections 3b (per pop) and 4b.
+static bool link_fits(HEVM::PopKind a_kind, int a_level, int a_target, bool a_merged, HEVM::PopKind b_kind, int b_level)
+{
+    const bool a_rescales = a_kind == HEVM::P_RESCALE || (a_kind == HEVM::P_MULCC && a_merged);
+    return (b_kind == HEVM::P_RESCALE && a_kind == HEVM::P_MULCC && !a_merged && a_level == b_level) ||
+           (b_kind == HEVM::P_BOOT && ((a_rescales && a_level - 1 == b_level) || (a_kind == HEVM::P_ROT && a_target >= 0 && a_level == b_level))) ||
+           (b_kind == HEVM::P_MULCC && a_rescales && a_level - 1 == b_level);
+}
+
+// no operand expression folded into the consumer's first phase (a rescale's own "+ pt" / "* pt" do not count: Handoff::rs_items applies them)
+static bool bare_first_phase(const HEVM::Pop &p)
+{
+    return !(p.rs_sum || p.boot_drop >= 0 || (p.kind != HEVM::P_RESCALE && (p.rs_add >= 0 || p.rs_mul >= 0)));
+}
+
+// The items of an n-ary sum step as groups that share sources (plan.hpp SumGroup).  Greedy: an item joins the open group while at least half
+// of its sources are in the group's union already (candidates: the next 64 items of the step, program order keeps relatives close).  A source
+// an item names twice gets one union entry per occurrence.
+typedef std::pair<int, int> SumKey; // (source value, occurrence)
+static std::vector<SumKey> sum_keys(const HEVM::Pop &p) // the keys of an item, in term order
+{
+    std::vector<SumKey> ks;
+    std::map<int, int> occ;
+    for (int sv : p.srcs) ks.push_back({ sv, occ[sv]++ });
+    return ks;
+}
+struct SumSharing {
+    std::vector<std::vector<int>> groups;    // positions in the step's pop list
+    std::vector<std::vector<SumKey>> unions; // per group: its sources, each once
+    size_t reads_before = 0, reads_after = 0; // ciphertext reads item by item / group by group
+};
+static SumSharing share_sum_sources(const std::vector<HEVM::Pop> &O, const std::vector<int> &pops)
+{
+    SumSharing sh;
+    std::vector<char> used(pops.size(), 0);
+    for (size_t a0 = 0; a0 < pops.size(); a0++) {
+        if (used[a0]) continue;
+        used[a0] = 1;
+        std::vector<int> grp{ (int)a0 };
+        std::vector<SumKey> uni = sum_keys(O[(size_t)pops[a0]]);
+        std::set<SumKey> in_uni(uni.begin(), uni.end());
+        while ((int)grp.size() < kSumGroup) {
+            int best = -1;
+            size_t best_sh = 0;
+            for (size_t b0 = a0 + 1; b0 < pops.size() && b0 < a0 + 64; b0++) {
+                if (used[b0]) continue;
+                const auto kb = sum_keys(O[(size_t)pops[b0]]);
+                size_t n = 0;
+                for (auto &kk : kb) n += in_uni.count(kk);
+                if (n * 2 >= kb.size() && n > best_sh) best = (int)b0, best_sh = n;
+            }
+            if (best < 0) break;
+            used[(size_t)best] = 1, grp.push_back(best);
+            for (auto &kk : sum_keys(O[(size_t)pops[(size_t)best]]))
+                if (in_uni.insert(kk).second) uni.push_back(kk);
+        }
+        for (int m : grp) sh.reads_before += O[(size_t)pops[(size_t)m]].srcs.size();
+        sh.reads_after += uni.size();
+        sh.groups.push_back(grp), sh.unions.push_back(uni);
+    }
+    return sh;
 }
 
 void HEVM::build_plan()
 {
     Context &c = *ctx;
     const size_t N = c.N;
+    release_plan();
     Plan &P = plan;
-    for (u64 *b : P.handoff_bufs) (void)vm_free(b);
-    P.handoff_bufs.clear();
-    for (void *p : { (void *)P.d_enc_items, (void *)P.enc_arena, (void *)P.enc_scratch, (void *)P.d_enc_overflow })
-        if (p) (void)vm_free(p);
-    P.d_enc_items = nullptr, P.enc_arena = nullptr, P.enc_scratch = nullptr, P.d_enc_overflow = nullptr;
-    P.enc_groups.clear(), P.enc_arena_bytes = P.enc_scratch_bytes = 0;
-    if (P.d_cont_other) (void)vm_free(P.d_cont_other), P.d_cont_other = nullptr;
-    if (P.d_mulrs) (void)vm_free(P.d_mulrs), P.d_mulrs = nullptr;
-    if (P.d_mulsum) (void)vm_free(P.d_mulsum), P.d_mulsum = nullptr;
-    if (P.d_mulsum_terms) (void)vm_free(P.d_mulsum_terms), P.d_mulsum_terms = nullptr;
-    for (void *p : { (void *)P.d_ks, (void *)P.d_mul, (void *)P.d_rs, (void *)P.d_ew, (void *)P.d_sum, (void *)P.d_sum_srcs, (void *)P.d_sumg, (void *)P.d_sumg_srcs, (void *)P.d_boot,
-                     (void *)P.d_boot_rs, (void *)P.d_boot_zenc, (void *)P.zenc, (void *)P.boot_ue, (void *)P.boot_tmp, (void *)P.boot_pt[0], (void *)P.boot_ptx[0],
-                     (void *)P.boot_pt[1], (void *)P.boot_ptx[1] })
-        if (p) (void)vm_free(p);
-    P.d_boot = nullptr, P.d_boot_rs = nullptr, P.d_boot_zenc = nullptr, P.zenc = P.boot_ue = P.boot_tmp = nullptr, P.boot_e = nullptr;
-    P.boot_pt[0] = P.boot_pt[1] = P.boot_ptx[0] = P.boot_ptx[1] = nullptr;
-    P.boot_chunks.clear();
-    if (P.graph_exec) (void)hipGraphExecDestroy(P.graph_exec);
-    if (P.graph) (void)hipGraphDestroy(P.graph);
-    P.graph_exec = nullptr, P.graph = nullptr;
-    P.vals.clear(), P.pops.clear(), P.steps.clear();
-    P.n_keyswitch = P.n_ntt = 0;
-    P.n_hops = P.n_decomp = 0, P.n_fold = 0, P.n_relin_groups = P.n_relin_products = 0;
     const size_t nreg = ciphers.size();
     const int S = streams; // independent ciphertext streams executed side by side (items of every step are replicated)
     std::vector<int> cur(nreg, -1);
@@ -80,6 +162,31 @@ void HEVM::build_plan()
         P.pops.push_back(p);
         return P.pops.back();
     };
+    auto same_level = [&](const char *what, int la, int lb) {
+        if (la == lb) return;
+        fprintf(stderr, "[dacapo_amd] %s: level mismatch %d vs %d\n", what, la, lb);
+        abort();
+    };
+    auto chain_left = [&](const char *what, int level_after) {
+        if (level_after >= 1) return;
+        fprintf(stderr, "[dacapo_amd] %s: end of modulus switching chain reached\n", what);
+        abort();
+    };
+    auto new_view = [&](int of, int level, double scale) { // a value that names the buffer of another: no pop of its own, metadata of its own
+        const int nv = new_val(level, scale), root = P.vals[(size_t)of].root;
+        P.vals[(size_t)nv].root = root;
+        P.vals[(size_t)nv].def_pop = P.vals[(size_t)root].def_pop;
+        P.vals[(size_t)of].uses++; // the view keeps the original alive and observable
+        return nv;
+    };
+    auto add_hop = [&](int src, double scale, u32 elt) -> Pop & { // one key-switch hop of a rotate / conj instruction under a Galois key
+        const int level = P.vals[(size_t)src].level;
+        Pop &p = add_pop(P_ROT, level, { src }, new_val(level, scale));
+        p.elt = elt, p.key = keys.galois.at(elt);
+        p.rot = ks_hoist ? 2 : 1, p.target_level = ks_hoist ? -2 : 0; // (hoisted hops: steps of their own, issue_step)
+        P.n_keyswitch++, P.n_ntt += ks_ntts(level);
+        return p;
+    };
     for (size_t i = 0; i < header.arg_length; i++) { // program inputs: written by encrypt() into the home buffers
         const int v = new_val((int)arg_level[i], pow(2.0, (double)arg_scale[i]));
         P.vals[(size_t)v].external = true;
@@ -94,6 +201,7 @@ void HEVM::build_plan()
     // operand has NOW, not the one the memoised hop saw.  memo_base maps such a view back to the value whose hops are memoised.
     std::map<std::pair<int, u32>, int> hop_memo;
     std::map<int, int> memo_base;
+    auto memo_key = [&](int v) { const auto mb = memo_base.find(v); return mb != memo_base.end() ? mb->second : v; };
     for (const WireOp &op : ops) {
         switch (op.opcode) {
         case 1: { // rotate: one key-switch hop per Galois element (direct key or NAF digits)
@@ -107,36 +215,22 @@ void HEVM::build_plan()
                 // (a key switch is deterministic), one key switch fewer.  config 4 under the reference HEaaN runtime's 49 keys: 18.7 % of the hops.
                 memo_final = false;
                 if (rot_compose) {
-                    const auto mb = memo_base.find(v);
-                    auto it = hop_memo.find({ mb != memo_base.end() ? mb->second : v, elt });
+                    auto it = hop_memo.find({ memo_key(v), elt });
                     if (it != hop_memo.end()) {
                         v = it->second;
                         memo_final = true;
                         continue;
                     }
                 }
-                const Val s = P.vals[(size_t)v];
-                const int nv = new_val(s.level, in_scale);
-                Pop &p = add_pop(P_ROT, s.level, { v }, nv);
-                p.elt = elt, p.key = keys.galois.at(elt);
-                p.rot = ks_hoist ? 2 : 1, p.target_level = ks_hoist ? -2 : 0; // (hoisted hops: steps of their own, issue_step)
+                Pop &p = add_hop(v, in_scale, elt);
                 p.op = (int)(&op - ops.data()), p.direct = &elt == &hops.back(); // (the LAST hop of the instruction: the one whose result the program sees)
-                P.n_keyswitch++, P.n_ntt += ks_ntts(s.level);
-                if (rot_compose) {
-                    const auto mb = memo_base.find(v);
-                    hop_memo[{ mb != memo_base.end() ? mb->second : v, elt }] = nv;
-                }
-                v = nv;
+                if (rot_compose) hop_memo[{ memo_key(v), elt }] = p.dst;
+                v = p.dst;
             }
             if (memo_final) { // the last hop came out of the memo: another register may name that value -- dst gets its own view of the buffer
-                const Val s = P.vals[(size_t)v];
-                const int nv = new_val(s.level, in_scale);
-                P.vals[(size_t)nv].root = s.root;
-                P.vals[(size_t)nv].def_pop = P.vals[(size_t)s.root].def_pop;
-                P.vals[(size_t)v].uses++; // the view keeps the memoised value alive and observable
-                const auto mb = memo_base.find(v);
-                memo_base[nv] = mb != memo_base.end() ? mb->second : v;
-                v = nv;
+                const int base = memo_key(v);
+                v = new_view(v, P.vals[(size_t)v].level, in_scale);
+                memo_base[v] = base;
             }
             if (v == cur[op.lhs] && op.dst != op.lhs) { // no hop at all: rotate_vector copies (SEAL_HEVM.cpp:273), so dst gets a value of its
                 const Val s = P.vals[(size_t)v];            // own -- a later scale overwrite on one register (:301,:308) must not reach the other
@@ -158,10 +252,7 @@ void HEVM::build_plan()
         case 3: {
             const int a = need(op.lhs, "rescale");
             const Val s = P.vals[(size_t)a];
-            if (s.level < 2) {
-                fprintf(stderr, "[dacapo_amd] rescale: end of modulus switching chain reached\n");
-                abort();
-            }
+            chain_left("rescale", s.level - 1);
             const int nv = new_val(s.level - 1, s.scale / (double)c.primes[(size_t)s.level - 1]);
             add_pop(P_RESCALE, s.level, { a }, nv);
             P.n_ntt += 2 * s.level;
@@ -173,25 +264,15 @@ void HEVM::build_plan()
             if (down <= 0) break; // dst untouched (SEAL_HEVM.cpp:288)
             const int a = need(op.lhs, "modswitch");
             const Val s = P.vals[(size_t)a];
-            if (s.level - down < 1) {
-                fprintf(stderr, "[dacapo_amd] modswitch: end of modulus switching chain reached\n");
-                abort();
-            }
-            const int nv = new_val(s.level - down, s.scale);
-            P.vals[(size_t)nv].root = s.root;
-            P.vals[(size_t)nv].def_pop = P.vals[(size_t)s.root].def_pop;
-            P.vals[(size_t)a].uses++; // the view keeps the original alive and observable
-            cur[op.dst] = nv;
+            chain_left("modswitch", s.level - down);
+            cur[op.dst] = new_view(a, s.level - down, s.scale);
             break;
         }
         case 5: fprintf(stderr, "This VM does not support native upscale op\n"); abort();
         case 6: {
             const int a = need(op.lhs, "addcc"), b = need(op.rhs, "addcc");
             P.vals[(size_t)a].scale = P.vals[(size_t)b].scale; // SEAL_HEVM.cpp:301
-            if (P.vals[(size_t)a].level != P.vals[(size_t)b].level) {
-                fprintf(stderr, "[dacapo_amd] addcc: level mismatch %d vs %d\n", P.vals[(size_t)a].level, P.vals[(size_t)b].level);
-                abort();
-            }
+            same_level("addcc", P.vals[(size_t)a].level, P.vals[(size_t)b].level);
             const int nv = new_val(P.vals[(size_t)a].level, P.vals[(size_t)b].scale);
             add_pop(P_SUM, P.vals[(size_t)a].level, { a, b }, nv).op = (int)(&op - ops.data());
             cur[op.dst] = nv;
@@ -201,10 +282,7 @@ void HEVM::build_plan()
             const int a = need(op.lhs, "addcp");
             const Plain &pl = plains.at(op.rhs);
             P.vals[(size_t)a].scale = pl.scale; // SEAL_HEVM.cpp:308
-            if (P.vals[(size_t)a].level != pl.level) {
-                fprintf(stderr, "[dacapo_amd] addcp: level mismatch %d vs %d\n", P.vals[(size_t)a].level, pl.level);
-                abort();
-            }
+            same_level("addcp", P.vals[(size_t)a].level, pl.level);
             const int nv = new_val(pl.level, pl.scale);
             add_pop(P_ADDP, pl.level, { a }, nv).plain = op.rhs;
             cur[op.dst] = nv;
@@ -213,10 +291,7 @@ void HEVM::build_plan()
         case 8: {
             const int a = need(op.lhs, "mulcc"), b = need(op.rhs, "mulcc");
             const Val sa = P.vals[(size_t)a], sb = P.vals[(size_t)b];
-            if (sa.level != sb.level) {
-                fprintf(stderr, "[dacapo_amd] mulcc: level mismatch %d vs %d\n", sa.level, sb.level);
-                abort();
-            }
+            same_level("mulcc", sa.level, sb.level);
             const int nv = new_val(sa.level, sa.scale * sb.scale);
             add_pop(P_MULCC, sa.level, { a, b }, nv).op = (int)(&op - ops.data());
             P.n_keyswitch++, P.n_ntt += ks_ntts(sa.level);
@@ -227,10 +302,7 @@ void HEVM::build_plan()
             const int a = need(op.lhs, "mulcp");
             const Val sa = P.vals[(size_t)a];
             const Plain &pl = plains.at(op.rhs);
-            if (sa.level != pl.level) {
-                fprintf(stderr, "[dacapo_amd] mulcp: level mismatch %d vs %d\n", sa.level, pl.level);
-                abort();
-            }
+            same_level("mulcp", sa.level, pl.level);
             const int nv = new_val(sa.level, sa.scale * pl.scale);
             add_pop(P_MULP, sa.level, { a }, nv).plain = op.rhs;
             cur[op.dst] = nv;
@@ -247,18 +319,12 @@ void HEVM::build_plan()
         }
         case kOpConj: { // one key switch with the conjugation key
             const int a = need(op.lhs, "conj");
-            const Val s = P.vals[(size_t)a];
             const u32 elt = (u32)(2 * N - 1);
             if (!keys.galois.count(elt)) {
                 fprintf(stderr, "[dacapo_amd] conj: no Galois key for the conjugation\n");
                 abort();
             }
-            const int nv = new_val(s.level, s.scale);
-            Pop &p = add_pop(P_ROT, s.level, { a }, nv);
-            p.elt = elt, p.key = keys.galois.at(elt);
-            p.rot = ks_hoist ? 2 : 1, p.target_level = ks_hoist ? -2 : 0;
-            P.n_keyswitch++, P.n_ntt += ks_ntts(s.level);
-            cur[op.dst] = nv;
+            cur[op.dst] = add_hop(a, P.vals[(size_t)a].scale, elt).dst;
             break;
         }
         case kOpModRaise: {
@@ -297,12 +363,7 @@ void HEVM::build_plan()
         }
         case kOpSetScale: { // a relabelled view of the same buffer
             const int a = need(op.lhs, "setscale");
-            const Val s = P.vals[(size_t)a];
-            const int nv = new_val(s.level, buffer[op.rhs][0]); // validated by load_program
-            P.vals[(size_t)nv].root = s.root;
-            P.vals[(size_t)nv].def_pop = P.vals[(size_t)s.root].def_pop;
-            P.vals[(size_t)a].uses++;
-            cur[op.dst] = nv;
+            cur[op.dst] = new_view(a, P.vals[(size_t)a].level, buffer[op.rhs][0]); // validated by load_program
             break;
         }
         default: break;
@@ -315,6 +376,13 @@ void HEVM::build_plan()
         for (int s : p.srcs) V[(size_t)s].uses++;
     for (int v : cur)
         if (v >= 0) V[(size_t)v].uses++, V[(size_t)V[(size_t)v].root].pinned = true;
+    // The live pop whose OWN result value v is -- not a view of that result (modswitch, setscale, a memoised hop's), not a program input --,
+    // or -1.  Every fold and link below starts from it and adds the conditions of its own: single use, not pinned, the kind, the level.
+    // (Section 3b's producer lists alone follow a view to the pop behind it: they read def_pop directly.)
+    auto own_pop = [&](int v) -> int {
+        const Val &sv = V[(size_t)v];
+        return (sv.root == v && sv.def_pop >= 0 && !O[(size_t)sv.def_pop].dead && O[(size_t)sv.def_pop].dst == v) ? sv.def_pop : -1;
+    };
 
     // ---- 1b. lazy relinearisation (option ks_lazy_relin; SEAL-layout keys) ---------------------------------------------------------
     // relin(sum_k s_k a_k (x) b_k) is ONE key switch of the summed three-part ciphertext (plan.hpp b_mul_sum_relin) where the program's mulcc
@@ -333,15 +401,11 @@ void HEVM::build_plan()
             if (r < nreg && cur[(size_t)r] >= 0) is_result[(size_t)cur[(size_t)r]] = 1;
         const size_t n = O.size();
         std::vector<int> kind(n, RELIN_OTHER), src0(n, -1), src1(n, -1), readers(n, 0), level(n, 0), result(n, 0);
-        auto own_def = [&](int v) -> int { // pop whose own result (not a view of it) value v is, or -1
-            const Val &sv = V[(size_t)v];
-            return (sv.root == v && sv.def_pop >= 0 && O[(size_t)sv.def_pop].dst == v) ? sv.def_pop : -1;
-        };
-        for (size_t i = 0; i < n; i++) {
+        for (size_t i = 0; i < n; i++) { // (no pop is dead yet)
             const Pop &p = O[i];
             kind[i] = p.kind == P_MULCC ? RELIN_MULCC : (p.kind == P_SUM && p.srcs.size() == 2) ? RELIN_ADDCC : p.kind == P_NEG ? RELIN_NEGATE : RELIN_OTHER;
-            if (kind[i] != RELIN_OTHER) src0[i] = own_def(p.srcs[0]);
-            if (kind[i] == RELIN_MULCC || kind[i] == RELIN_ADDCC) src1[i] = own_def(p.srcs[1]);
+            if (kind[i] != RELIN_OTHER) src0[i] = own_pop(p.srcs[0]);
+            if (kind[i] == RELIN_MULCC || kind[i] == RELIN_ADDCC) src1[i] = own_pop(p.srcs[1]);
             readers[i] = V[(size_t)p.dst].uses - named[(size_t)p.dst], level[i] = p.level, result[i] = is_result[(size_t)p.dst];
         }
         RelinOps in;
@@ -372,9 +436,8 @@ void HEVM::build_plan()
         if (p.kind != P_SUM) continue;
         std::vector<int> flat;
         for (int s : p.srcs) {
-            const Val &sv = V[(size_t)s];
-            const int dp = sv.root == s ? sv.def_pop : -1;
-            if (dp >= 0 && O[(size_t)dp].kind == P_SUM && !O[(size_t)dp].dead && sv.uses == 1 && O[(size_t)dp].dst == s) {
+            const int dp = own_pop(s);
+            if (dp >= 0 && O[(size_t)dp].kind == P_SUM && V[(size_t)s].uses == 1) {
                 flat.insert(flat.end(), O[(size_t)dp].srcs.begin(), O[(size_t)dp].srcs.end());
                 O[(size_t)dp].dead = true;
             } else
@@ -389,9 +452,8 @@ void HEVM::build_plan()
         p.src_plain.assign(p.srcs.size(), -1);
         for (size_t k = 0; k < p.srcs.size(); k++) {
             const int sidx = p.srcs[k];
-            const Val &sv = V[(size_t)sidx];
-            const int dp = sv.root == sidx ? sv.def_pop : -1;
-            if (dp >= 0 && O[(size_t)dp].kind == P_MULP && !O[(size_t)dp].dead && sv.uses == 1 && O[(size_t)dp].dst == sidx) {
+            const int dp = own_pop(sidx);
+            if (dp >= 0 && O[(size_t)dp].kind == P_MULP && V[(size_t)sidx].uses == 1) {
                 p.srcs[k] = O[(size_t)dp].srcs[0];
                 p.src_plain[k] = O[(size_t)dp].plain;
                 O[(size_t)dp].dead = true;
@@ -405,10 +467,8 @@ void HEVM::build_plan()
     for (Pop &p : O) {
         if (p.kind != P_RESCALE || p.dead) continue;
         auto single_def = [&](int v, PopKind k) -> int { // pop defining v if v is a plain (non-view) single-use value made by kind k
-            const Val &sv = V[(size_t)v];
-            const int dp = sv.root == v ? sv.def_pop : -1;
-            if (dp >= 0 && O[(size_t)dp].kind == k && !O[(size_t)dp].dead && sv.uses == 1 && O[(size_t)dp].dst == v && !sv.pinned) return dp;
-            return -1;
+            const int dp = own_pop(v);
+            return (dp >= 0 && O[(size_t)dp].kind == k && V[(size_t)v].uses == 1 && !V[(size_t)v].pinned) ? dp : -1;
         };
         int x = p.srcs[0], dp;
         if ((dp = single_def(x, P_MULP)) >= 0) p.rs_mul = O[(size_t)dp].plain, x = O[(size_t)dp].srcs[0], O[(size_t)dp].dead = true;
@@ -444,8 +504,8 @@ void HEVM::build_plan()
         if (p.kind != P_BOOT || p.dead || !fold_rescale_into_boot) continue;
         const int x = p.srcs[0];
         const Val &sv = V[(size_t)x];
-        const int dp = sv.root == x ? sv.def_pop : -1;
-        if (dp < 0 || O[(size_t)dp].kind != P_RESCALE || O[(size_t)dp].dead || sv.uses != 1 || O[(size_t)dp].dst != x || sv.pinned) continue;
+        const int dp = own_pop(x);
+        if (dp < 0 || O[(size_t)dp].kind != P_RESCALE || sv.uses != 1 || sv.pinned) continue;
         Pop &r = O[(size_t)dp];
         p.srcs = r.srcs, p.src_plain = r.src_plain, p.rs_sum = r.rs_sum, p.rs_add = r.rs_add, p.rs_mul = r.rs_mul;
         p.level = r.level, p.boot_drop = r.level - 1, p.boot_src_scale = sv.scale;
@@ -479,11 +539,11 @@ void HEVM::build_plan()
                     continue;
                 const int sidx = O[ci].srcs[k];
                 const Val &sv = V[(size_t)sidx];
-                const int dp = sv.root == sidx ? sv.def_pop : -1;
+                const int dp = own_pop(sidx);
                 if (dp < 0) continue;
                 const Pop &r = O[(size_t)dp];
                 if (seal_sums && !(r.rot == 2 && r.op >= 0 && ops[(size_t)r.op].opcode == 1)) continue;
-                if (r.kind == P_ROT && !r.dead && r.direct && r.dst == sidx && sv.uses == 1 && !sv.pinned && r.level == O[ci].level) terms.push_back(k);
+                if (r.kind == P_ROT && r.direct && sv.uses == 1 && !sv.pinned && r.level == O[ci].level) terms.push_back(k);
             }
             if (terms.size() < 2) continue;
             // the group takes the place of its LAST member in pop order: every member's source is defined before it, its consumer after it
@@ -554,33 +614,23 @@ void HEVM::build_plan()
         const size_t n = live.size();
         std::vector<int> kind(n), level(n), target(n), cap(n), fixed(n), launches(n), link_prev(n, -1), asap(n), first(n + 1, 0), prod, wave(n);
         const bool links = chain_fusion && chain_fusion_supported();
-        auto live_def = [&](int v, bool own) -> int { // live pop that defines value v (own: v is its result itself, not a view of it), or -1
-            const Val &sv = V[(size_t)v];
-            if (sv.def_pop < 0 || O[(size_t)sv.def_pop].dead || (own && (sv.root != v || O[(size_t)sv.def_pop].dst != v))) return -1;
-            return sv.def_pop;
-        };
         for (size_t k = 0; k < n; k++) {
             const Pop &p = O[(size_t)live[k]];
-            const bool heavy = p.kind == P_ROT || p.kind == P_MULCC || p.kind == P_RESCALE || p.kind == P_BOOT || p.kind == P_ROTSUM || p.kind == P_MULSUM;
             kind[k] = (int)p.kind, level[k] = p.level, target[k] = p.target_level, asap[k] = p.wave;
-            cap[k] = (int)std::max<size_t>(1, (heavy ? (size_t)max_batch : (size_t)4096) / (size_t)S); // (section 4's chunk)
+            cap[k] = (int)step_chunk(p.kind); // (section 4's chunk)
             fixed[k] = p.kind == P_ROTSUM;
-            launches[k] = p.kind == P_ROT || p.kind == P_MULCC || p.kind == P_ROTSUM || p.kind == P_MULSUM ? 5 : p.kind == P_RESCALE ? 3 : p.kind == P_BOOT ? 4 : 1;
-            for (int s : p.srcs) {
-                const int dp = live_def(s, false);
-                if (dp >= 0) prod.push_back(idx[(size_t)dp]);
+            launches[k] = kKind[p.kind].launches;
+            for (int s : p.srcs) { // (the live pop behind the value, also through a view of its result: an order, not a hand-off)
+                const int dp = V[(size_t)s].def_pop;
+                if (dp >= 0 && !O[(size_t)dp].dead) prod.push_back(idx[(size_t)dp]);
             }
             first[k + 1] = (int)prod.size();
             // the producer whose step could hand its result to this operation's first phase (section 4b's rule, operation for operation)
             const bool consumer = p.kind == P_RESCALE || p.kind == P_BOOT || p.kind == P_MULCC;
-            if (!links || !consumer || p.rs_sum || p.boot_drop >= 0 || (p.kind != P_RESCALE && (p.rs_add >= 0 || p.rs_mul >= 0))) continue;
+            if (!links || !consumer || !bare_first_phase(p)) continue;
             for (size_t w = 0; w < (p.kind == P_MULCC ? 2u : 1u) && link_prev[k] < 0; w++) {
-                const int dp = live_def(p.srcs[w], true);
-                if (dp < 0) continue;
-                const Pop &a = O[(size_t)dp];
-                if ((p.kind == P_RESCALE && a.kind == P_MULCC && a.level == p.level) ||
-                    (p.kind == P_BOOT && ((a.kind == P_RESCALE && a.level - 1 == p.level) || (a.kind == P_ROT && a.target_level >= 0 && a.level == p.level))) ||
-                    (p.kind == P_MULCC && a.kind == P_RESCALE && a.level - 1 == p.level))
+                const int dp = own_pop(p.srcs[w]);
+                if (dp >= 0 && link_fits(O[(size_t)dp].kind, O[(size_t)dp].level, O[(size_t)dp].target_level, false, p.kind, p.level))
                     link_prev[k] = idx[(size_t)dp];
             }
         }
@@ -637,11 +687,12 @@ void HEVM::build_plan()
             const Pop &rp = O[ri];
             if (rp.dead || rp.kind != P_RESCALE || rp.rs_sum || rp.srcs.size() != 1) continue;
             const Val &mv = V[(size_t)rp.srcs[0]];
-            if (mv.root != rp.srcs[0] || mv.def_pop < 0 || mv.uses != 1 || mv.pinned) continue;
-            Pop &mp = O[(size_t)mv.def_pop];
-            if (mp.dead || mp.kind != P_MULCC || mp.dst != rp.srcs[0] || mp.level != rp.level || mp.level < 2) continue;
+            const int mi = own_pop(rp.srcs[0]);
+            if (mi < 0 || mv.uses != 1 || mv.pinned) continue;
+            Pop &mp = O[(size_t)mi];
+            if (mp.kind != P_MULCC || mp.level != rp.level || mp.level < 2) continue;
             if (rp.rs_mul >= 0 && !is_constant(rp.rs_mul)) continue;
-            fold_rs_of[mv.def_pop] = (int)ri, mp.target_level = -3;
+            fold_rs_of[mi] = (int)ri, mp.target_level = -3;
         }
     }
     for (int w = 1; w <= max_wave; w++) {
@@ -665,8 +716,7 @@ void HEVM::build_plan()
                 });
             else if (kind == P_ROT && !c.hybrid() && option(OPT_KS_ITEMS_FAST))
                 std::stable_sort(kv.second.begin(), kv.second.end(), [&](int x, int y) { return O[(size_t)x].elt < O[(size_t)y].elt; });
-            const bool heavy = kind == P_ROT || kind == P_MULCC || kind == P_RESCALE || kind == P_BOOT || kind == P_ROTSUM || kind == P_MULSUM;
-            const size_t chunk = std::max<size_t>(1, (heavy ? (size_t)max_batch : (size_t)4096) / (size_t)S);
+            const size_t chunk = step_chunk(kind);
             if (kind == P_ROTSUM) { // whole groups, counted by their rotations
                 for (size_t off = 0; off < kv.second.size();) {
                     size_t end = off, items = 0;
@@ -707,16 +757,10 @@ void HEVM::build_plan()
     // ---- 4b. chain fusion (plan.hpp Handoff): step B's first phase computed by the last kernel of step A -----------------------------
     // A link needs: B reads A's results and nothing else as its first-phase operand, item for item; no operand expression folded
     // into B; for a multiply, the other operand is A's result too (a square) or older than A.
-    P.n_fused = 0;
     std::vector<CtView> h_cont_other;            // filled with stream views in section 6
     std::vector<std::pair<int, int>> cont_other; // (value or -1 for a square, unused) per CONT_MUL item slot, pop order
     std::vector<int> mul_fused_src((size_t)O.size(), -1); // consumer multiply pop -> which operand (0 / 1) comes from the producer
     if (chain_fusion && chain_fusion_supported() && !c.hybrid()) { // (the grouped-digit key switch has no continuation kernels)
-        auto def_step_of = [&](int v) -> int { // step defining value v when v is a plain (non-view) pop result, else -1
-            const Val &sv = V[(size_t)v];
-            if (sv.root != v || sv.def_pop < 0 || O[(size_t)sv.def_pop].dead || O[(size_t)sv.def_pop].dst != v) return -1;
-            return O[(size_t)sv.def_pop].step;
-        };
         auto wave_of_value = [&](int v) -> int { // wave in which v (or the buffer it views) is complete; 0 for program inputs
             const Val &r = V[(size_t)V[(size_t)v].root];
             return r.def_pop >= 0 ? O[(size_t)r.def_pop].wave : 0;
@@ -730,17 +774,13 @@ void HEVM::build_plan()
             std::vector<int> which(bp.size(), 0);
             for (size_t k = 0; k < bp.size() && ok; k++) {
                 const Pop &p = O[(size_t)bp[k]];
-                if (p.rs_sum || p.boot_drop >= 0 || (B.kind != P_RESCALE && (p.rs_add >= 0 || p.rs_mul >= 0))) ok = false;
+                if (!bare_first_phase(p)) ok = false;
                 int found = -1;
                 for (size_t w = 0; w < (B.kind == P_MULCC ? 2u : 1u) && ok && found < 0; w++) {
-                    const int st = def_step_of(p.srcs[w]);
+                    const int dp = own_pop(p.srcs[w]), st = dp >= 0 ? O[(size_t)dp].step : -1; // (the step whose own result the operand is)
                     if (st < 0 || (ai >= 0 && st != ai)) continue;
                     const Step &A = P.steps[(size_t)st];
-                    const bool a_rescales = A.kind == P_RESCALE || (A.kind == P_MULCC && A.fold_rs); // (a merged step ends as a rescale does)
-                    const bool kinds = (B.kind == P_RESCALE && A.kind == P_MULCC && !A.fold_rs && A.level == B.level) ||
-                                       (B.kind == P_BOOT && ((a_rescales && A.level - 1 == B.level) || (A.kind == P_ROT && A.target >= 0 && A.level == B.level))) ||
-                                       (B.kind == P_MULCC && a_rescales && A.level - 1 == B.level);
-                    if (!kinds || A.fused_consumer >= 0 || A.wave >= B.wave) continue;
+                    if (!link_fits(A.kind, A.level, A.target, A.fold_rs, B.kind, B.level) || A.fused_consumer >= 0 || A.wave >= B.wave) continue;
                     if (B.kind == P_MULCC) { // the other operand: the same value, or complete before A starts
                         const int other = p.srcs[1 - w];
                         if (other != p.srcs[w] && wave_of_value(other) >= A.wave) continue;
@@ -801,89 +841,7 @@ void HEVM::build_plan()
     }
     // ---- 4c. on-line encode: every plaintext register is encoded right before the wave that first reads it, into a window whose
     // blocks are recycled once the last reader's wave is over; the item tables below then see ordinary device pointers -----------
-    if (online_encode && !online.items.empty()) {
-        const int NW = max_wave + 2;
-        std::map<int, std::pair<int, int>> use; // plain register -> (first wave, last wave)
-        auto touch = [&](int reg, int w) {
-            if (reg < 0) return;
-            auto it = use.find(reg);
-            if (it == use.end())
-                use[reg] = { w, w };
-            else
-                it->second.first = std::min(it->second.first, w), it->second.second = std::max(it->second.second, w);
-        };
-        for (size_t si = 0; si < P.steps.size(); si++) {
-            const Step &st = P.steps[si];
-            // a fused producer evaluates its consumer's folded "+ pt" / "* pt" one step early (Handoff::rs_items)
-            const int early = st.fused_consumer >= 0 ? st.wave : -1;
-            for (int pi : step_pops[si]) {
-                const Pop &p = O[(size_t)pi];
-                touch(p.plain, p.wave), touch(p.rs_add, p.wave), touch(p.rs_mul, p.wave);
-                for (int pl : p.src_plain) touch(pl, p.wave);
-            }
-            if (early >= 0)
-                for (int pi : step_pops[(size_t)st.fused_consumer]) touch(O[(size_t)pi].rs_add, early), touch(O[(size_t)pi].rs_mul, early);
-        }
-        std::map<std::pair<int, int>, std::vector<int>> groups; // (first wave, level) -> registers
-        for (auto &kv : use) groups[{ kv.second.first, plains.at((size_t)kv.first).level }].push_back(kv.first);
-        struct Block { size_t off, size; int release; };
-        std::vector<Block> live, freeb;
-        size_t high = 0, max_cnt = 0;
-        std::vector<EncItem> h_items;
-        std::vector<std::pair<size_t, size_t>> placed; // per group: (offset, first item)
-        const int chunk = 256;
-        int cur_wave = -1;
-        for (auto &kv : groups) {
-            const int w = kv.first.first, level = kv.first.second;
-            if (w != cur_wave) { // blocks whose readers are done are free again
-                for (size_t i = 0; i < live.size();)
-                    if (live[i].release < w) {
-                        freeb.push_back(live[i]);
-                        live[i] = live.back(), live.pop_back();
-                    } else
-                        i++;
-                cur_wave = w;
-            }
-            for (size_t k0 = 0; k0 < kv.second.size(); k0 += (size_t)chunk) {
-                const size_t cnt = std::min<size_t>((size_t)chunk, kv.second.size() - k0), size = cnt * (size_t)level * N;
-                int release = w;
-                for (size_t k = 0; k < cnt; k++) release = std::max(release, use[kv.second[k0 + k]].second);
-                size_t off = (size_t)-1;
-                for (size_t i = 0; i < freeb.size(); i++)
-                    if (freeb[i].size >= size) { // first fit; the remainder stays free
-                        off = freeb[i].off;
-                        if (freeb[i].size > size)
-                            freeb[i].off += size, freeb[i].size -= size;
-                        else
-                            freeb[i] = freeb.back(), freeb.pop_back();
-                        break;
-                    }
-                if (off == (size_t)-1) off = high, high += size;
-                live.push_back({ off, size, release });
-                P.enc_groups.push_back({ w, level, (int)h_items.size(), (int)cnt, nullptr });
-                placed.push_back({ off, h_items.size() });
-                for (size_t k = 0; k < cnt; k++) h_items.push_back(online.items.at(kv.second[k0 + k]));
-                max_cnt = std::max(max_cnt, cnt);
-            }
-            (void)NW;
-        }
-        DC_HIP_CHECK(vm_malloc(&P.enc_arena, std::max<size_t>(high, 1) * sizeof(u64)));
-        P.enc_arena_bytes = high * sizeof(u64);
-        P.enc_scratch_bytes = max_cnt * N * sizeof(double2);
-        DC_HIP_CHECK(vm_malloc(&P.enc_scratch, std::max<size_t>(P.enc_scratch_bytes, 16)));
-        DC_HIP_CHECK(vm_malloc(&P.d_enc_overflow, sizeof(int)));
-        DC_HIP_CHECK(hipMemset(P.d_enc_overflow, 0, sizeof(int)));
-        P.d_enc_items = upload(h_items);
-        size_t gi = 0;
-        for (auto &kv : groups)
-            for (size_t k0 = 0; k0 < kv.second.size(); k0 += (size_t)chunk, gi++) {
-                Plan::EncGroup &g = P.enc_groups[gi];
-                g.out = P.enc_arena + placed[gi].first;
-                for (int k = 0; k < g.count; k++) plains.at((size_t)kv.second[k0 + (size_t)k]).d = g.out + (size_t)k * (size_t)g.level * N;
-            }
-        for (auto &kv : online.items)
-            if (!use.count(kv.first)) plains.at((size_t)kv.first).d = P.enc_arena; // never read: any valid address
-    }
+    if (online_encode && !online.items.empty()) place_online_encode(step_pops);
     // ---- 5. lifetimes and pool buffers ---------------------------------------------------------------------------------
     for (const Pop &p : O) {
         if (p.dead) continue;
@@ -898,7 +856,6 @@ void HEVM::build_plan()
     typedef std::pair<int, u64 *> Rel; // (last_use, buffer)
     std::priority_queue<Rel, std::vector<Rel>, std::greater<Rel>> busy;
     size_t live = 0;
-    P.max_live = 0;
     std::vector<std::vector<int>> defs(P.steps.size());
     for (size_t v = 0; v < V.size(); v++)
         if (V[v].root == (int)v && V[v].def_step >= 0 && !V[v].external) defs[(size_t)V[v].def_step].push_back((int)v);
@@ -925,21 +882,10 @@ void HEVM::build_plan()
         }
     }
     // ---- 6. device item tables ----------------------------------------------------------------------------------------
-    const long ps = (long)c.K * (long)N;
-    auto view = [&](int v, int sidx) {
-        u64 *b = V[(size_t)V[(size_t)v].root].buf;
-        if (!b) {
-            fprintf(stderr, "[dacapo_amd] plan: value %d has no buffer (internal error)\n", v);
-            abort();
-        }
-        return CtView{ b + (size_t)sidx * buf_elems, ps };
-    };
     size_t need_t = 0, need_d = 0, need_e = 0, need_a = 0, need_m = 0;
     size_t need_bpt = 0, need_bptx = 0;
     int boot_tmax = 0;
     std::vector<std::pair<int, int>> h_boot_pops; // (pop, stream) per boot item; device tables are filled once the arena exists
-    std::vector<double> h_boot_ratio;
-    P.launches = 0;
     for (size_t s = 0; s < P.steps.size(); s++) {
         Step &st = P.steps[s];
         st.count *= S; // items = pseudo-ops x streams
@@ -958,10 +904,10 @@ void HEVM::build_plan()
                 std::vector<KsItem> sources;
                 for (int pi : step_pops[s])
                     for (int q = 0; q < S; q++) {
-                        const CtView sv = view(O[(size_t)pi].srcs[0], q);
+                        const CtView sv = plan_view(O[(size_t)pi].srcs[0], q);
                         if (hoisted && !slot_of.count(sv.p)) sources.push_back(KsItem{ sv, sv, nullptr, 1u, 0 });
                         const u32 slot = (c.hybrid() || hoisted) ? slot_of.emplace(sv.p, (u32)slot_of.size()).first->second : 0u;
-                        h_ks.push_back(KsItem{ sv, view(O[(size_t)pi].dst, q), O[(size_t)pi].key, O[(size_t)pi].elt, slot });
+                        h_ks.push_back(KsItem{ sv, plan_view(O[(size_t)pi].dst, q), O[(size_t)pi].key, O[(size_t)pi].elt, slot });
                     }
                 st.unique = (int)slot_of.size();
                 st.gfirst = (int)h_ks.size(), st.gcount = (int)sources.size();
@@ -978,19 +924,18 @@ void HEVM::build_plan()
             for (int pi : step_pops[s])
                 for (int q = 0; q < S; q++) {
                     const Pop &rp = O[(size_t)pi];
-                    const CtView dst = view(rp.dst, q);
+                    const CtView dst = plan_view(rp.dst, q);
                     groups.push_back(KsItem{ dst, dst, nullptr, (u32)(h_ks.size() - (size_t)st.first), (u32)rp.srcs.size() });
                     // (option ks_lazy_sum: group-major, then by source -- a group's members that read one decomposition are adjacent)
                     std::vector<size_t> order(rp.srcs.size());
                     for (size_t k = 0; k < order.size(); k++) order[k] = k;
                     if (!c.hybrid()) std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return rp.srcs[x] < rp.srcs[y]; });
                     for (size_t k : order) {
-                        const CtView sv = view(rp.srcs[k], q);
+                        const CtView sv = plan_view(rp.srcs[k], q);
                         if (!c.hybrid() && !slot_of.count(sv.p)) sources.push_back(KsItem{ sv, sv, nullptr, 1u, 0 });
                         const u32 slot = slot_of.emplace(sv.p, (u32)slot_of.size()).first->second;
                         const int pl = rp.plains.empty() ? -1 : rp.plains[k];
-                        h_ks.push_back(KsItem{ sv, dst, rp.keys[k], rp.elts[k], slot, pl >= 0 ? plains.at((size_t)pl).d : nullptr,
-                                               pl >= 0 ? plains.at((size_t)pl).dsp : nullptr });
+                        h_ks.push_back(KsItem{ sv, dst, rp.keys[k], rp.elts[k], slot, plain_ptr(pl), pl >= 0 ? plains.at((size_t)pl).dsp : nullptr });
                     }
                 }
             st.unique = (int)slot_of.size();
@@ -1010,9 +955,9 @@ void HEVM::build_plan()
                     for (int q = 0; q < S; q++) {
                         const Pop &mp = O[(size_t)step_pops[s][k]], &rp = O[(size_t)rs[k]];
                         MulRsItem it;
-                        it.a = view(mp.srcs[0], q), it.b = view(mp.srcs[1], q), it.dst = view(rp.dst, q);
-                        if (rp.rs_add >= 0) it.add = plains.at((size_t)rp.rs_add).d;
-                        if (rp.rs_mul >= 0) it.mul = plains.at((size_t)rp.rs_mul).d, it.mul_stride = (long)N;
+                        it.a = plan_view(mp.srcs[0], q), it.b = plan_view(mp.srcs[1], q), it.dst = plan_view(rp.dst, q);
+                        it.add = plain_ptr(rp.rs_add), it.mul = plain_ptr(rp.rs_mul);
+                        if (rp.rs_mul >= 0) it.mul_stride = (long)N;
                         h_mulrs.push_back(it);
                     }
                 P.n_fold += (int64_t)B;
@@ -1021,16 +966,16 @@ void HEVM::build_plan()
             st.first = (int)h_mul.size();
             for (int pi : step_pops[s])
                 for (int q = 0; q < S; q++)
-                    h_mul.push_back(MulItem{ view(O[(size_t)pi].srcs[0], q), view(O[(size_t)pi].srcs[1], q), view(O[(size_t)pi].dst, q) });
+                    h_mul.push_back(MulItem{ plan_view(O[(size_t)pi].srcs[0], q), plan_view(O[(size_t)pi].srcs[1], q), plan_view(O[(size_t)pi].dst, q) });
             break;
         case P_MULSUM: // one item per group and stream; its terms in the group's program order
             st.first = (int)h_mulsum.size();
             for (int pi : step_pops[s])
                 for (int q = 0; q < S; q++) {
                     const Pop &gp = O[(size_t)pi];
-                    h_mulsum.push_back(MulSumItem{ view(gp.dst, q), (int)h_mulsum_terms.size(), (int)gp.signs.size() });
+                    h_mulsum.push_back(MulSumItem{ plan_view(gp.dst, q), (int)h_mulsum_terms.size(), (int)gp.signs.size() });
                     for (size_t k = 0; k < gp.signs.size(); k++)
-                        h_mulsum_terms.push_back(MulTerm{ view(gp.srcs[2 * k], q), view(gp.srcs[2 * k + 1], q), gp.signs[k] });
+                        h_mulsum_terms.push_back(MulTerm{ plan_view(gp.srcs[2 * k], q), plan_view(gp.srcs[2 * k + 1], q), gp.signs[k] });
                     P.n_relin_groups++, P.n_relin_products += (int64_t)gp.signs.size();
                 }
             break;
@@ -1039,16 +984,9 @@ void HEVM::build_plan()
             for (int pi : step_pops[s])
                 for (int q = 0; q < S; q++) {
                     const Pop &rp = O[(size_t)pi];
-                    RsItem it{ view(rp.srcs[0], q), view(rp.dst, q), 0, 0, nullptr, nullptr };
-                    if (rp.rs_sum) {
-                        it.first = (int)h_srcs.size(), it.count = (int)rp.srcs.size();
-                        for (size_t k = 0; k < rp.srcs.size(); k++) {
-                            const int pl = rp.src_plain.empty() ? -1 : rp.src_plain[k];
-                            h_srcs.push_back(SumSrc{ view(rp.srcs[k], q), pl >= 0 ? plains.at((size_t)pl).d : nullptr });
-                        }
-                    }
-                    if (rp.rs_add >= 0) it.add = plains.at((size_t)rp.rs_add).d;
-                    if (rp.rs_mul >= 0) it.mul = plains.at((size_t)rp.rs_mul).d;
+                    RsItem it{ plan_view(rp.srcs[0], q), plan_view(rp.dst, q), 0, 0, nullptr, nullptr };
+                    if (rp.rs_sum) std::tie(it.first, it.count) = push_terms(h_srcs, rp, q);
+                    it.add = plain_ptr(rp.rs_add), it.mul = plain_ptr(rp.rs_mul);
                     h_rs.push_back(it);
                 }
             break;
@@ -1070,75 +1008,37 @@ void HEVM::build_plan()
             }
             for (int pi : step_pops[s])
                 for (int q = 0; q < S; q++) {
-                    h_sum.push_back(SumItem{ view(O[(size_t)pi].dst, q), (int)h_srcs.size(), (int)O[(size_t)pi].srcs.size() });
-                    for (size_t k = 0; k < O[(size_t)pi].srcs.size(); k++) {
-                        const int pl = O[(size_t)pi].src_plain.empty() ? -1 : O[(size_t)pi].src_plain[k];
-                        h_srcs.push_back(SumSrc{ view(O[(size_t)pi].srcs[k], q), pl >= 0 ? plains.at((size_t)pl).d : nullptr });
-                    }
+                    const std::pair<int, int> terms = push_terms(h_srcs, O[(size_t)pi], q);
+                    h_sum.push_back(SumItem{ plan_view(O[(size_t)pi].dst, q), terms.first, terms.second });
                 }
             // The same items as groups that share sources (plan.hpp SumGroup): the output channels of a convolution, the giant steps of a
-            // matrix-vector product name the same rotated ciphertexts.  Greedy: an item joins the open group while at least half of its
-            // sources are in the group's union already (candidates: the next 64 items of the step, program order keeps relatives close).
-            // A source an item names twice gets one union entry per occurrence.  Taken when it saves a fifth of the step's ciphertext reads
-            // and leaves option sum_group_min_wgs workgroups.
+            // matrix-vector product name the same rotated ciphertexts (share_sum_sources finds them).  Taken when it saves a fifth of the
+            // step's ciphertext reads and leaves option sum_group_min_wgs workgroups.
             if (option(OPT_SUM_GROUP_MIN_WGS) >= 0 && step_pops[s].size() > 1) {
                 const std::vector<int> &pops = step_pops[s];
-                auto keys_of = [&](int pi) { // (source value, occurrence) keys of an item, in term order
-                    std::vector<std::pair<int, int>> ks;
-                    std::map<int, int> occ;
-                    for (int sv : O[(size_t)pi].srcs) ks.push_back({ sv, occ[sv]++ });
-                    return ks;
-                };
-                std::vector<std::vector<int>> groups;
-                std::vector<std::vector<std::pair<int, int>>> unions;
-                std::vector<char> used(pops.size(), 0);
-                size_t reads_before = 0, reads_after = 0;
-                for (size_t a0 = 0; a0 < pops.size(); a0++) {
-                    if (used[a0]) continue;
-                    used[a0] = 1;
-                    std::vector<int> grp{ (int)a0 };
-                    std::vector<std::pair<int, int>> uni = keys_of(pops[a0]);
-                    std::set<std::pair<int, int>> in_uni(uni.begin(), uni.end());
-                    while ((int)grp.size() < kSumGroup) {
-                        int best = -1;
-                        size_t best_sh = 0;
-                        for (size_t b0 = a0 + 1; b0 < pops.size() && b0 < a0 + 64; b0++) {
-                            if (used[b0]) continue;
-                            const auto kb = keys_of(pops[b0]);
-                            size_t sh = 0;
-                            for (auto &kk : kb) sh += in_uni.count(kk);
-                            if (sh * 2 >= kb.size() && sh > best_sh) best = (int)b0, best_sh = sh;
-                        }
-                        if (best < 0) break;
-                        used[(size_t)best] = 1, grp.push_back(best);
-                        for (auto &kk : keys_of(pops[(size_t)best]))
-                            if (in_uni.insert(kk).second) uni.push_back(kk);
-                    }
-                    for (int m : grp) reads_before += O[(size_t)pops[(size_t)m]].srcs.size();
-                    reads_after += uni.size();
-                    groups.push_back(grp), unions.push_back(uni);
-                }
+                const SumSharing sh = share_sum_sources(O, pops);
+                const std::vector<std::vector<int>> &groups = sh.groups;
                 const long wgs = (long)(N / 256) * st.level * (long)groups.size() * S;
                 if (option(OPT_TRACE) >= 2)
                     fprintf(stderr, "[dacapo_amd] plan:   sum step at level %d: %zu items, %zu ciphertext reads, %zu as %zu groups\n", st.level, pops.size(),
-                            reads_before, reads_after, groups.size());
-                if (reads_after * 5 <= reads_before * 4 && wgs >= (long)option(OPT_SUM_GROUP_MIN_WGS)) {
+                            sh.reads_before, sh.reads_after, groups.size());
+                if (sh.reads_after * 5 <= sh.reads_before * 4 && wgs >= (long)option(OPT_SUM_GROUP_MIN_WGS)) {
                     st.gfirst = (int)h_sumg.size();
                     for (int q = 0; q < S; q++)
                         for (size_t gi = 0; gi < groups.size(); gi++) {
                             SumGroup sg{};
-                            sg.first = (int)h_sumg_srcs.size(), sg.count = (int)unions[gi].size(), sg.items = (int)groups[gi].size();
+                            sg.first = (int)h_sumg_srcs.size(), sg.count = (int)sh.unions[gi].size(), sg.items = (int)groups[gi].size();
                             std::map<std::pair<int, int>, size_t> pos;
-                            for (auto &kk : unions[gi]) {
+                            for (auto &kk : sh.unions[gi]) {
                                 SumGroupSrc gs{};
-                                gs.v = view(kk.first, q);
+                                gs.v = plan_view(kk.first, q);
                                 pos[kk] = h_sumg_srcs.size();
                                 h_sumg_srcs.push_back(gs);
                             }
                             for (size_t m = 0; m < groups[gi].size(); m++) {
                                 const Pop &p = O[(size_t)pops[(size_t)groups[gi][m]]];
-                                sg.dst[m] = view(p.dst, q);
-                                const auto km = keys_of(pops[(size_t)groups[gi][m]]);
+                                sg.dst[m] = plan_view(p.dst, q);
+                                const auto km = sum_keys(p);
                                 for (size_t k = 0; k < km.size(); k++) {
                                     const int pl = p.src_plain.empty() ? -1 : p.src_plain[k];
                                     h_sumg_srcs[pos[km[k]]].plain[m] = pl >= 0 ? plains.at((size_t)pl).d : sum_add_only();
@@ -1155,18 +1055,14 @@ void HEVM::build_plan()
             [[fallthrough]];
         case P_NEG:
         case P_COPY:
-            st.first = (int)h_ew.size();
-            for (int pi : step_pops[s])
-                for (int q = 0; q < S; q++)
-                    h_ew.push_back(EwItem{ view(O[(size_t)pi].dst, q), view(O[(size_t)pi].srcs[0], q), view(O[(size_t)pi].srcs[0], q) });
-            break;
         case P_MULP:
-        case P_ADDP:
+        case P_ADDP: // (second operand: the plaintext of a mulcp / addcp, else the source again)
             st.first = (int)h_ew.size();
             for (int pi : step_pops[s])
-                for (int q = 0; q < S; q++)
-                    h_ew.push_back(EwItem{ view(O[(size_t)pi].dst, q), view(O[(size_t)pi].srcs[0], q),
-                                           CtView{ plains.at((size_t)O[(size_t)pi].plain).d, 0 } });
+                for (int q = 0; q < S; q++) {
+                    const CtView src = plan_view(O[(size_t)pi].srcs[0], q);
+                    h_ew.push_back(EwItem{ plan_view(O[(size_t)pi].dst, q), src, O[(size_t)pi].plain >= 0 ? CtView{ plains.at((size_t)O[(size_t)pi].plain).d, 0 } : src });
+                }
             break;
         case P_BOOT:
             st.first = (int)h_boot_pops.size();
@@ -1190,7 +1086,6 @@ void HEVM::build_plan()
     // what every step reads and writes, by pool buffer: the dependencies of the explicitly built graph (capture_plan_dag)
     for (size_t s = 0; s < P.steps.size(); s++) {
         Step &st = P.steps[s];
-        st.reads.clear(), st.writes.clear();
         for (int pi : step_pops[s]) {
             const Pop &p = O[(size_t)pi];
             for (int v : p.srcs) st.reads.push_back(V[(size_t)V[(size_t)v].root].buf);
@@ -1206,82 +1101,14 @@ void HEVM::build_plan()
             vec->erase(std::unique(vec->begin(), vec->end()), vec->end());
         }
     }
-    // opcode 10: every item owns a slot of the zero-encryption arena; the zero-encryptions are made in chunks of items with
-    // the same target level at the start of each run (plan_zero_encrypt)
-    if (!h_boot_pops.empty()) {
-        const size_t nb = h_boot_pops.size(), slot = (size_t)2 * boot_tmax * N;
-        DC_HIP_CHECK(vm_malloc(&P.zenc, nb * slot * sizeof(u64)));
-        P.zenc_bytes = nb * slot * sizeof(u64);
-        std::vector<int> order(nb); // boot items sorted by target level (stable): chunks are ranges of the sorted tables
-        for (size_t i = 0; i < nb; i++) order[i] = (int)i;
-        std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
-            return O[(size_t)h_boot_pops[(size_t)a].first].target_level < O[(size_t)h_boot_pops[(size_t)b].first].target_level;
-        });
-        // zenc_head = 1 samples a third of the limbs per item and keeps no product buffer, so its chunks are its own (kZencChunk), not max_batch's
-        const size_t bc = std::min<size_t>(nb, zenc_head ? (size_t)(zenc_chunk_hook > 0 ? zenc_chunk_hook : kZencChunk) : (size_t)std::max(max_batch, 1));
-        const size_t cmax = (size_t)boot_tmax + 1;
-        if (zenc_head) { // u [bc][cmax][N] words, then e0, e1 [bc][2][N] bytes
-            DC_HIP_CHECK(vm_malloc(&P.boot_ue, bc * cmax * N * sizeof(u64) + bc * 2 * N));
-            P.boot_e = reinterpret_cast<signed char *>(P.boot_ue + bc * cmax * N);
-        } else {
-            DC_HIP_CHECK(vm_malloc(&P.boot_ue, bc * 3 * cmax * N * sizeof(u64)));
-            DC_HIP_CHECK(vm_malloc(&P.boot_tmp, bc * 2 * cmax * N * sizeof(u64)));
-        }
-        for (int ln = 0; ln < plan_lanes; ln++) {
-            DC_HIP_CHECK(vm_malloc(&P.boot_pt[ln], std::max<size_t>(need_bpt, 1) * N * sizeof(u64)));
-            DC_HIP_CHECK(vm_malloc(&P.boot_ptx[ln], std::max<size_t>(need_bptx, 1) * N * sizeof(u64)));
-        }
-        std::vector<BootItem> h_boot(nb);
-        std::vector<RsItem> h_brs(zenc_head ? 0 : nb);
-        std::vector<ZencItem> h_bz(zenc_head ? nb : 0);
-        for (size_t k = 0; k < nb;) { // chunks over the sorted order
-            const int t = O[(size_t)h_boot_pops[(size_t)order[k]].first].target_level;
-            size_t e = k;
-            while (e < nb && e - k < bc && O[(size_t)h_boot_pops[(size_t)order[e]].first].target_level == t) e++;
-            P.boot_chunks.push_back({ (int)k, (int)(e - k), t });
-            for (size_t j = k; j < e; j++) { // sorted position j <-> item order[j]; zenc slot = item index
-                const size_t item = (size_t)order[j];
-                u64 *z = P.zenc + item * slot;
-                if (zenc_head)
-                    h_bz[j] = ZencItem{ P.boot_ue + (j - k) * (size_t)(t + 1) * N, CtView{ z, (long)t * (long)N } };
-                else
-                    h_brs[j] = RsItem{ CtView{ P.boot_tmp + (j - k) * 2 * (size_t)(t + 1) * N, (long)(t + 1) * (long)N }, CtView{ z, (long)t * (long)N } };
-            }
-            need_d = std::max(need_d, (e - k) * 2), need_m = std::max(need_m, (e - k) * 2 * (size_t)(zenc_head ? t : t + 1));
-            P.launches += zenc_head ? 6 : 7; // (the transform of a chunk is one launch or two)
-            k = e;
-        }
-        for (size_t item = 0; item < nb; item++) {
-            const Pop &p = O[(size_t)h_boot_pops[item].first];
-            const int q = h_boot_pops[item].second;
-            // scale of what is decrypted: the (possibly folded) rescale's result when there is one, else the source value
-            const double new_scale = V[(size_t)p.dst].scale;
-            BootItem bi{ view(p.srcs[0], q), view(p.dst, q), P.zenc + item * slot, 1.0 };
-            double src_scale;
-            if (p.boot_drop >= 0) { // new_scale = 2^floor(log2(scale after the rescale)) was fixed by the SSA walk
-                src_scale = p.boot_src_scale * (double)c.primes[(size_t)p.boot_drop];
-            } else
-                src_scale = V[(size_t)p.srcs[0]].scale;
-            bi.ratio = new_scale / src_scale;
-            if (p.rs_sum) {
-                bi.first = (int)h_srcs.size(), bi.count = (int)p.srcs.size();
-                for (size_t k = 0; k < p.srcs.size(); k++) {
-                    const int pl = p.src_plain.empty() ? -1 : p.src_plain[k];
-                    h_srcs.push_back(SumSrc{ view(p.srcs[k], q), pl >= 0 ? plains.at((size_t)pl).d : nullptr });
-                }
-            }
-            if (p.rs_add >= 0) bi.add = plains.at((size_t)p.rs_add).d;
-            if (p.rs_mul >= 0) bi.mul = plains.at((size_t)p.rs_mul).d;
-            h_boot[item] = bi;
-        }
-        P.d_boot = upload(h_boot), P.d_boot_rs = upload(h_brs), P.d_boot_zenc = upload(h_bz);
-    }
-    P.d_mulrs = upload(h_mulrs);
-    P.d_mulsum = upload(h_mulsum), P.d_mulsum_terms = upload(h_mulsum_terms);
-    P.d_ks = upload(h_ks), P.d_mul = upload(h_mul), P.d_rs = upload(h_rs), P.d_ew = upload(h_ew), P.d_sum = upload(h_sum);
+    // opcode 10: the zero-encryption arena, its chunks and the item tables (section 6b)
+    if (!h_boot_pops.empty()) build_boot_tables(h_boot_pops, boot_tmax, need_bpt, need_bptx, h_srcs, need_d, need_m);
+    P.d_mulrs = upload(*this, h_mulrs);
+    P.d_mulsum = upload(*this, h_mulsum), P.d_mulsum_terms = upload(*this, h_mulsum_terms);
+    P.d_ks = upload(*this, h_ks), P.d_mul = upload(*this, h_mul), P.d_rs = upload(*this, h_rs), P.d_ew = upload(*this, h_ew), P.d_sum = upload(*this, h_sum);
     P.h_ew = h_ew;
-    P.d_sum_srcs = upload(h_srcs);
-    P.d_sumg = upload(h_sumg), P.d_sumg_srcs = upload(h_sumg_srcs);
+    P.d_sum_srcs = upload(*this, h_srcs);
+    P.d_sumg = upload(*this, h_sumg), P.d_sumg_srcs = upload(*this, h_sumg_srcs);
     // fused links: the consumer's first-phase buffer (owned by the link, so the two steps may sit on different streams / waves)
     // and, for multiplies, the table of the consumers' other operands in item order
     {
@@ -1291,9 +1118,7 @@ void HEVM::build_plan()
             if (A.fused_consumer < 0) continue;
             Step &B = P.steps[(size_t)A.fused_consumer];
             const size_t items = (size_t)B.count, limbs = A.h.cont == CONT_RS ? 2 : (size_t)B.level;
-            u64 *buf = nullptr;
-            DC_HIP_CHECK(vm_malloc(&buf, items * limbs * N * sizeof(u64)));
-            P.handoff_bufs.push_back(buf);
+            u64 *buf = static_cast<u64 *>(plan_alloc(items * limbs * N * sizeof(u64)));
             A.h.out = buf, B.h.in = buf;
             A.h.sk = keys.sk;
             if (A.h.cont == CONT_RS) A.h.rs_items = P.d_rs + B.first;
@@ -1303,25 +1128,17 @@ void HEVM::build_plan()
                     for (int q = 0; q < S; q++) {
                         const Pop &mp = O[(size_t)pi];
                         const int w = mul_fused_src[(size_t)pi], other = mp.srcs[(size_t)(1 - w)];
-                        h_cont_other.push_back(other == mp.srcs[(size_t)w] ? CtView{ nullptr, 0 } : view(other, q));
+                        h_cont_other.push_back(other == mp.srcs[(size_t)w] ? CtView{ nullptr, 0 } : plan_view(other, q));
                     }
             }
         }
-        P.d_cont_other = upload(h_cont_other);
+        P.d_cont_other = upload(*this, h_cont_other);
         for (size_t ai = 0; ai < P.steps.size(); ai++)
             if (P.steps[ai].fused_consumer >= 0 && P.steps[ai].h.cont == CONT_MUL) P.steps[ai].h.other = P.d_cont_other + other_first[ai];
     }
-    auto alloc = [&](size_t limbs) {
-        u64 *d = nullptr;
-        DC_HIP_CHECK(vm_malloc(&d, std::max<size_t>(limbs, 1) * N * sizeof(u64)));
-        return d;
-    };
-    for (int ln = 0; ln < 2; ln++) {
+    auto alloc = [&](size_t limbs) { return static_cast<u64 *>(plan_alloc(std::max<size_t>(limbs, 1) * N * sizeof(u64))); };
+    for (int ln = 0; ln < 2 && ln < plan_lanes; ln++) { // the lanes' batch scratch
         BatchWs &w = P.ws[ln];
-        for (void *p : { (void *)w.target, (void *)w.digits, (void *)w.ext, (void *)w.acc, (void *)w.tmp })
-            if (p) (void)vm_free(p);
-        w = BatchWs{};
-        if (ln >= plan_lanes) continue;
         w.target = alloc(need_t), w.digits = alloc(need_d), w.ext = alloc(need_e);
         w.acc = alloc(need_a), w.tmp = alloc(need_m);
     }
@@ -1339,13 +1156,178 @@ void HEVM::build_plan()
     P.n_keyswitch *= S, P.n_ntt *= S;
     P.ready = true;
     if (plan_graph) capture_plan(); // part of the (untimed) preparation, like the plan itself
-    if (option(OPT_TRACE)) {
-        static const char *kn[] = { "rot", "mulcc", "rescale", "sum", "neg", "mulp", "addp", "copy", "boot", "modraise", "rotsum", "mulsum" };
+    if (option(OPT_TRACE)) report_plan(sum_stat, max_wave, levels_moved);
+}
+
+// ---- 4c. on-line encode (option online_encode): the window placement.  Reads the steps and their pops; writes Plan::enc_* and, for every
+// plaintext register of the program, where its limbs will lie.
+void HEVM::place_online_encode(const std::vector<std::vector<int>> &step_pops)
+{
+    Plan &P = plan;
+    const std::vector<Pop> &O = P.pops;
+    const size_t N = ctx->N;
+    std::map<int, std::pair<int, int>> use; // plain register -> (first wave, last wave)
+    auto touch = [&](int reg, int w) {
+        if (reg < 0) return;
+        auto it = use.emplace(reg, std::make_pair(w, w)).first;
+        it->second.first = std::min(it->second.first, w), it->second.second = std::max(it->second.second, w);
+    };
+    for (size_t si = 0; si < P.steps.size(); si++) {
+        const Step &st = P.steps[si];
+        // a fused producer evaluates its consumer's folded "+ pt" / "* pt" one step early (Handoff::rs_items)
+        const int early = st.fused_consumer >= 0 ? st.wave : -1;
+        for (int pi : step_pops[si]) {
+            const Pop &p = O[(size_t)pi];
+            touch(p.plain, p.wave), touch(p.rs_add, p.wave), touch(p.rs_mul, p.wave);
+            for (int pl : p.src_plain) touch(pl, p.wave);
+        }
+        if (early >= 0)
+            for (int pi : step_pops[(size_t)st.fused_consumer]) touch(O[(size_t)pi].rs_add, early), touch(O[(size_t)pi].rs_mul, early);
+    }
+    std::map<std::pair<int, int>, std::vector<int>> groups; // (first wave, level) -> registers
+    for (auto &kv : use) groups[{ kv.second.first, plains.at((size_t)kv.first).level }].push_back(kv.first);
+    struct Block { size_t off, size; int release; };
+    std::vector<Block> live, freeb;
+    size_t high = 0, max_cnt = 0;
+    std::vector<EncItem> h_items;
+    std::vector<std::pair<size_t, size_t>> placed; // per group: (offset, first item)
+    const int chunk = 256;
+    int cur_wave = -1;
+    for (auto &kv : groups) {
+        const int w = kv.first.first, level = kv.first.second;
+        if (w != cur_wave) { // blocks whose readers are done are free again
+            for (size_t i = 0; i < live.size();)
+                if (live[i].release < w) {
+                    freeb.push_back(live[i]);
+                    live[i] = live.back(), live.pop_back();
+                } else
+                    i++;
+            cur_wave = w;
+        }
+        for (size_t k0 = 0; k0 < kv.second.size(); k0 += (size_t)chunk) {
+            const size_t cnt = std::min<size_t>((size_t)chunk, kv.second.size() - k0), size = cnt * (size_t)level * N;
+            int release = w;
+            for (size_t k = 0; k < cnt; k++) release = std::max(release, use[kv.second[k0 + k]].second);
+            size_t off = (size_t)-1;
+            for (size_t i = 0; i < freeb.size(); i++)
+                if (freeb[i].size >= size) { // first fit; the remainder stays free
+                    off = freeb[i].off;
+                    if (freeb[i].size > size)
+                        freeb[i].off += size, freeb[i].size -= size;
+                    else
+                        freeb[i] = freeb.back(), freeb.pop_back();
+                    break;
+                }
+            if (off == (size_t)-1) off = high, high += size;
+            live.push_back({ off, size, release });
+            P.enc_groups.push_back({ w, level, (int)h_items.size(), (int)cnt, nullptr });
+            placed.push_back({ off, h_items.size() });
+            for (size_t k = 0; k < cnt; k++) h_items.push_back(online.items.at(kv.second[k0 + k]));
+            max_cnt = std::max(max_cnt, cnt);
+        }
+    }
+    P.enc_arena = static_cast<u64 *>(plan_alloc(std::max<size_t>(high, 1) * sizeof(u64)));
+    P.enc_arena_bytes = high * sizeof(u64);
+    P.enc_scratch_bytes = max_cnt * N * sizeof(double2);
+    P.enc_scratch = static_cast<double2 *>(plan_alloc(std::max<size_t>(P.enc_scratch_bytes, 16)));
+    P.d_enc_overflow = static_cast<int *>(plan_alloc(sizeof(int)));
+    DC_HIP_CHECK(hipMemset(P.d_enc_overflow, 0, sizeof(int)));
+    P.d_enc_items = upload(*this, h_items);
+    size_t gi = 0;
+    for (auto &kv : groups)
+        for (size_t k0 = 0; k0 < kv.second.size(); k0 += (size_t)chunk, gi++) {
+            Plan::EncGroup &g = P.enc_groups[gi];
+            g.out = P.enc_arena + placed[gi].first;
+            for (int k = 0; k < g.count; k++) plains.at((size_t)kv.second[k0 + (size_t)k]).d = g.out + (size_t)k * (size_t)g.level * N;
+        }
+    for (auto &kv : online.items)
+        if (!use.count(kv.first)) plains.at((size_t)kv.first).d = P.enc_arena; // never read: any valid address
+}
+
+// ---- 6b. opcode 10: every item ((pop, stream), in step order) owns a slot of the zero-encryption arena; the zero-encryptions are made in chunks
+// of items with the same target level at the start of each run (plan_zero_encrypt).  Appends the items' folded sums to h_srcs and raises the
+// lanes' scratch needs (need_d, need_m: BatchWs digits and tmp, in limbs) for those chunks.
+void HEVM::build_boot_tables(const std::vector<std::pair<int, int>> &h_boot_pops, int boot_tmax, size_t need_bpt, size_t need_bptx, std::vector<SumSrc> &h_srcs, size_t &need_d, size_t &need_m)
+{
+    Plan &P = plan;
+    const std::vector<Pop> &O = P.pops;
+    const std::vector<Val> &V = P.vals;
+    const size_t N = ctx->N;
+    const size_t nb = h_boot_pops.size(), slot = (size_t)2 * boot_tmax * N;
+    auto words = [&](size_t n) { return static_cast<u64 *>(plan_alloc(n * sizeof(u64))); };
+    P.zenc = words(nb * slot);
+    P.zenc_bytes = nb * slot * sizeof(u64);
+    std::vector<int> order(nb); // boot items sorted by target level (stable): chunks are ranges of the sorted tables
+    for (size_t i = 0; i < nb; i++) order[i] = (int)i;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
+        return O[(size_t)h_boot_pops[(size_t)a].first].target_level < O[(size_t)h_boot_pops[(size_t)b].first].target_level;
+    });
+    // zenc_head = 1 samples a third of the limbs per item and keeps no product buffer, so its chunks are its own (kZencChunk), not max_batch's
+    const size_t bc = std::min<size_t>(nb, zenc_head ? (size_t)(zenc_chunk_hook > 0 ? zenc_chunk_hook : kZencChunk) : (size_t)std::max(max_batch, 1));
+    const size_t cmax = (size_t)boot_tmax + 1;
+    if (zenc_head) { // u [bc][cmax][N] words, then e0, e1 [bc][2][N] bytes
+        P.boot_ue = static_cast<u64 *>(plan_alloc(bc * cmax * N * sizeof(u64) + bc * 2 * N));
+        P.boot_e = reinterpret_cast<signed char *>(P.boot_ue + bc * cmax * N);
+    } else {
+        P.boot_ue = words(bc * 3 * cmax * N);
+        P.boot_tmp = words(bc * 2 * cmax * N);
+    }
+    for (int ln = 0; ln < plan_lanes; ln++) {
+        P.boot_pt[ln] = words(std::max<size_t>(need_bpt, 1) * N);
+        P.boot_ptx[ln] = words(std::max<size_t>(need_bptx, 1) * N);
+    }
+    std::vector<BootItem> h_boot(nb);
+    std::vector<RsItem> h_brs(zenc_head ? 0 : nb);
+    std::vector<ZencItem> h_bz(zenc_head ? nb : 0);
+    for (size_t k = 0; k < nb;) { // chunks over the sorted order
+        const int t = O[(size_t)h_boot_pops[(size_t)order[k]].first].target_level;
+        size_t e = k;
+        while (e < nb && e - k < bc && O[(size_t)h_boot_pops[(size_t)order[e]].first].target_level == t) e++;
+        P.boot_chunks.push_back({ (int)k, (int)(e - k), t });
+        for (size_t j = k; j < e; j++) { // sorted position j <-> item order[j]; zenc slot = item index
+            const size_t item = (size_t)order[j];
+            u64 *z = P.zenc + item * slot;
+            if (zenc_head)
+                h_bz[j] = ZencItem{ P.boot_ue + (j - k) * (size_t)(t + 1) * N, CtView{ z, (long)t * (long)N } };
+            else
+                h_brs[j] = RsItem{ CtView{ P.boot_tmp + (j - k) * 2 * (size_t)(t + 1) * N, (long)(t + 1) * (long)N }, CtView{ z, (long)t * (long)N } };
+        }
+        need_d = std::max(need_d, (e - k) * 2), need_m = std::max(need_m, (e - k) * 2 * (size_t)(zenc_head ? t : t + 1));
+        P.launches += zenc_head ? 6 : 7; // (the transform of a chunk is one launch or two)
+        k = e;
+    }
+    for (size_t item = 0; item < nb; item++) {
+        const Pop &p = O[(size_t)h_boot_pops[item].first];
+        const int q = h_boot_pops[item].second;
+        // scale of what is decrypted: the (possibly folded) rescale's result when there is one, else the source value
+        const double new_scale = V[(size_t)p.dst].scale;
+        BootItem bi{ plan_view(p.srcs[0], q), plan_view(p.dst, q), P.zenc + item * slot, 1.0 };
+        double src_scale;
+        if (p.boot_drop >= 0) { // new_scale = 2^floor(log2(scale after the rescale)) was fixed by the SSA walk
+            src_scale = p.boot_src_scale * (double)ctx->primes[(size_t)p.boot_drop];
+        } else
+            src_scale = V[(size_t)p.srcs[0]].scale;
+        bi.ratio = new_scale / src_scale;
+        if (p.rs_sum) std::tie(bi.first, bi.count) = push_terms(h_srcs, p, q);
+        bi.add = plain_ptr(p.rs_add), bi.mul = plain_ptr(p.rs_mul);
+        h_boot[item] = bi;
+    }
+    P.d_boot = upload(*this, h_boot), P.d_boot_rs = upload(*this, h_brs), P.d_boot_zenc = upload(*this, h_bz);
+}
+
+// ---- 7. option trace: the plan as built.  sum_stat: sharing of sources between the items of the n-ary sum steps (section 6).
+void HEVM::report_plan(const double (&sum_stat)[5], int max_wave, int levels_moved) const
+{
+    const Plan &P = plan;
+    const std::vector<Pop> &O = P.pops;
+    const std::vector<Val> &V = P.vals;
+    const size_t buf_elems = (size_t)2 * ctx->K * ctx->N;
+    {
         size_t nsteps[kPopKinds] = { 0 }, nitems[kPopKinds] = { 0 };
         std::map<std::pair<int, int>, std::pair<size_t, size_t>> ks; // (kind, level) -> steps, items
         for (const Step &st : P.steps) {
             nsteps[st.kind]++, nitems[st.kind] += (size_t)st.count;
-            if (st.kind == P_ROT || st.kind == P_MULCC || st.kind == P_RESCALE || st.kind == P_BOOT || st.kind == P_ROTSUM || st.kind == P_MULSUM) {
+            if (kKind[st.kind].heavy) {
                 auto &e = ks[{ (int)st.kind, st.level }];
                 e.first++, e.second += (size_t)st.count;
             }
@@ -1355,13 +1337,13 @@ void HEVM::build_plan()
             for (size_t i = 0; i < P.steps.size() && i < 400; i++) {
                 const Step &st = P.steps[i];
                 if (st.wave != lastw) fprintf(stderr, "\n  wave %d:", st.wave);
-                fprintf(stderr, " [%s l%d x%d%s]", kn[st.kind], st.level, st.count, st.lane ? " aux" : "");
+                fprintf(stderr, " [%s l%d x%d%s]", kKind[st.kind].name, st.level, st.count, st.lane ? " aux" : "");
                 lastw = st.wave;
             }
             fprintf(stderr, "\n");
         }
         for (int k = 0; k < kPopKinds; k++)
-            if (nsteps[k]) fprintf(stderr, "[dacapo_amd] plan:   %-8s %5zu steps %6zu items\n", kn[k], nsteps[k], nitems[k]);
+            if (nsteps[k]) fprintf(stderr, "[dacapo_amd] plan:   %-8s %5zu steps %6zu items\n", kKind[k].name, nsteps[k], nitems[k]);
         {
             size_t gsteps = 0, ggroups = 0, gitems = 0;
             for (const Step &st : P.steps)
@@ -1385,18 +1367,17 @@ void HEVM::build_plan()
                 for (int u : users[(size_t)d]) edges[std::make_tuple((int)O[i].kind, (int)O[(size_t)u].kind, nu, O[(size_t)u].wave - O[i].wave)]++;
             }
             for (auto &kv : edges)
-                fprintf(stderr, "[dacapo_amd] plan edge: %-8s -> %-8s uses %3d wave distance %3d : %d\n", kn[std::get<0>(kv.first)],
-                        std::get<1>(kv.first) < 0 ? "(none)" : kn[std::get<1>(kv.first)], std::get<2>(kv.first), std::get<3>(kv.first), kv.second);
+                fprintf(stderr, "[dacapo_amd] plan edge: %-8s -> %-8s uses %3d wave distance %3d : %d\n", kKind[std::get<0>(kv.first)].name,
+                        std::get<1>(kv.first) < 0 ? "(none)" : kKind[std::get<1>(kv.first)].name, std::get<2>(kv.first), std::get<3>(kv.first), kv.second);
         }
         for (auto &kv : ks)
-            fprintf(stderr, "[dacapo_amd] plan:   %-8s level %2d: %5zu steps %6zu items\n", kn[kv.first.first], kv.first.second,
+            fprintf(stderr, "[dacapo_amd] plan:   %-8s level %2d: %5zu steps %6zu items\n", kKind[kv.first.first].name, kv.first.second,
                     kv.second.first, kv.second.second);
     }
-    if (option(OPT_TRACE))
-        fprintf(stderr, "[dacapo_amd] plan: %zu ops -> %zu pseudo-ops -> %zu steps (%zu on the auxiliary stream, %zu fused into their producer's last kernel) in %d waves, ~%zu launches, %zu live buffers (%.1f GB pool)\n",
-                ops.size(), O.size(), P.steps.size(), (size_t)std::count_if(P.steps.begin(), P.steps.end(), [](const Step &st) { return st.lane == 1; }), P.n_fused,
-                max_wave, P.launches, P.max_live, (double)P.pool.size() * buf_elems * 8 / 1e9);
-    if (option(OPT_TRACE)) { // what option plan_level changes, counted on the plan as built (the head's zero-encryptions are not steps)
+    fprintf(stderr, "[dacapo_amd] plan: %zu ops -> %zu pseudo-ops -> %zu steps (%zu on the auxiliary stream, %zu fused into their producer's last kernel) in %d waves, ~%zu launches, %zu live buffers (%.1f GB pool)\n",
+            ops.size(), O.size(), P.steps.size(), (size_t)std::count_if(P.steps.begin(), P.steps.end(), [](const Step &st) { return st.lane == 1; }), P.n_fused,
+            max_wave, P.launches, P.max_live, (double)P.pool.size() * buf_elems * 8 / 1e9);
+    { // what option plan_level changes, counted on the plan as built (the head's zero-encryptions are not steps)
         size_t multi = 0, launches = 0;
         for (size_t a = 0; a < P.steps.size();) {
             size_t b = a;
@@ -1405,12 +1386,12 @@ void HEVM::build_plan()
             a = b;
         }
         for (const Step &st : P.steps)
-            launches += st.kind == P_ROT || st.kind == P_MULCC || st.kind == P_ROTSUM || st.kind == P_MULSUM ? 5 : st.kind == P_RESCALE ? 3 : st.kind == P_BOOT ? 4 : 1;
+            launches += (size_t)kKind[st.kind].launches;
         fprintf(stderr, "[dacapo_amd] plan levels: plan_level %d moved %d operations: %zu steps in %d waves, %zu waves with more than one step, %zu links, "
                         "%zu step launches (5 per key switch, 3 per rescale, 4 per opcode 10, 1 per limb-wise step, -1 per link), %zu live buffers, "
                         "%zu pool buffers (%.3f GB)\n",
                 plan_level, levels_moved, P.steps.size(), max_wave, multi, P.n_fused, launches - P.n_fused, P.max_live, P.pool.size(),
-                (double)P.pool.size() * buf_elems * (double)S * 8 / 1e9);
+                (double)P.pool.size() * buf_elems * (double)streams * 8 / 1e9);
     }
 }
 
@@ -1456,14 +1437,21 @@ void HEVM::issue_step(const Step &st, hipStream_t q)
     }
 }
 
-void HEVM::issue_plan(hipStream_t s)
+// the head of a run: the zero-encryptions of every opcode-10 item
+void HEVM::issue_head(hipStream_t s)
 {
-    Context &c = *ctx;
     Plan &P = plan;
     if (test_zero_enc) { // TEST HOOK (hevm_test_zero_encryption): Enc(0) := (0, 0), so opcode 10 leaves its re-encoded plaintext in c0
         if (P.zenc) DC_HIP_CHECK(hipMemsetAsync(P.zenc, 0, P.zenc_bytes, s));
     } else
         for (const Plan::BootChunk &bc : P.boot_chunks) plan_zero_encrypt(bc.first, bc.count, bc.target, s);
+}
+
+void HEVM::issue_plan(hipStream_t s)
+{
+    Context &c = *ctx;
+    Plan &P = plan;
+    issue_head(s);
     // option step_profile = 1: synchronise after every step and attribute wall time to (kind, level, batch size) -- a
     // diagnosis mode (every step then pays a full launch round trip, as the steps of a dependent chain do anyway)
     const bool step_profile = option(OPT_STEP_PROFILE) != 0 && !plan_graph;
@@ -1517,7 +1505,6 @@ void HEVM::issue_plan(hipStream_t s)
     }
     bump_epoch(s);
     if (step_profile) {
-        static const char *kn[] = { "rot", "mulcc", "rescale", "sum", "neg", "mulp", "addp", "copy", "boot", "modraise", "rotsum", "mulsum" };
         double total = 0;
         for (auto &kv : prof) total += kv.second.second;
         fprintf(stderr, "[dacapo_amd] step profile (synchronised after every step): %.2f ms in %zu steps\n", total * 1e3, P.steps.size());
@@ -1526,7 +1513,7 @@ void HEVM::issue_plan(hipStream_t s)
         fprintf(stderr, "[dacapo_amd]   %zu waves, %zu of them with more than one step; sum of all steps %.2f ms, sum over waves of the longest step %.2f ms "
                         "(= %.1f %% of the serial time)\n", waves_seen, wide_waves, all_steps * 1e3, crit_path * 1e3, 100.0 * crit_path / all_steps);
         for (auto &kv : prof)
-            fprintf(stderr, "[dacapo_amd]   %-8s level %2d  batch<=%-3d  %5d steps  %8.3f ms  %7.2f us/step\n", kn[std::get<0>(kv.first)],
+            fprintf(stderr, "[dacapo_amd]   %-8s level %2d  batch<=%-3d  %5d steps  %8.3f ms  %7.2f us/step\n", kKind[std::get<0>(kv.first)].name,
                     std::get<1>(kv.first), std::get<2>(kv.first), kv.second.first, kv.second.second * 1e3,
                     kv.second.second * 1e6 / kv.second.first);
     }
@@ -1617,12 +1604,7 @@ bool HEVM::capture_plan_dag()
     };
     // head of the run: the zero-encryptions of every opcode-10 item (the epoch bump -- the next run's randomness -- is the graph's TAIL, behind
     // both lanes, exactly where issue_plan puts it: any step that samples from d_epoch sees the same epoch in all three execution forms)
-    hipGraphNode_t zenc_tail = add_unit([&](hipStream_t s) {
-        if (test_zero_enc) {
-            if (P.zenc) DC_HIP_CHECK(hipMemsetAsync(P.zenc, 0, P.zenc_bytes, s));
-        } else
-            for (const Plan::BootChunk &bc : P.boot_chunks) plan_zero_encrypt(bc.first, bc.count, bc.target, s);
-    }, {});
+    hipGraphNode_t zenc_tail = add_unit([&](hipStream_t s) { issue_head(s); }, {});
     // Every step sits on one of the two scratch lanes, and a lane is a chain (its steps share the batch scratch): a dependency on a step is
     // implied by a dependency on any LATER step of the same lane.  So a step needs at most two edges -- its own lane's tail and the latest
     // step it depends on in the other lane -- and none to the other lane when nothing it touches was touched there since.
@@ -1669,10 +1651,9 @@ bool HEVM::capture_plan_dag()
 
 void HEVM::drop_plan_graph()
 {
-    Plan &P = plan;
-    if (P.graph_exec) (void)hipGraphExecDestroy(P.graph_exec);
-    if (P.graph) (void)hipGraphDestroy(P.graph);
-    P.graph_exec = nullptr, P.graph = nullptr;
+    if (plan.graph_exec) (void)hipGraphExecDestroy(plan.graph_exec);
+    if (plan.graph) (void)hipGraphDestroy(plan.graph);
+    plan.graph_exec = nullptr, plan.graph = nullptr;
 }
 
 void HEVM::run_plan()
