@@ -1364,7 +1364,7 @@ void HEVM::decrypt(int64_t i, double *out)
     // m = c0 + c1 s mod Q has |coefficients| < Q_16 / 2 for anything that decodes to finite doubles at all (an integer beyond 2^959 divided by
     // any admissible scale is not a CKKS message but overflowed noise), and then its centred representative mod Q_16 is the one mod Q_ell.
     // Limbs are independent, so decrypting and inverse-transforming only those 16 changes nothing about them.
-    const int ell = !host_encoder && ct.level > 16 ? 16 : ct.level;
+    const int ell = decode_limbs(ct.level);
     DC_LAUNCH(decrypt_kernel, dim3((unsigned)(N / (2 * kVmThreads)), (unsigned)ell), dim3(kVmThreads), 0, S(), pt,
                        view(ct), keys.sk, N, c.d_mods);
     launch_ntt(c, true, pt, (long)N, ell, nullptr, 0, 0, S());
@@ -1448,6 +1448,275 @@ void HEVM::decrypt(int64_t i, double *out)
         res[n] = r;
     }
     encoder->decode(res, out);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// batched encrypt / decrypt: all streams' inputs and results at once (hevm_vm.hpp IoBatch; io_batch.hip)
+// ---------------------------------------------------------------------------------------------------------
+void HEVM::io_check_streams(const char *what, int first_stream, int count) const
+{
+    if (count < 1) {
+        fprintf(stderr, "[dacapo_amd] %s: count %d is not positive\n", what, count);
+        abort();
+    }
+    if (first_stream < 0 || first_stream >= streams || count > streams - first_stream) {
+        fprintf(stderr, "[dacapo_amd] %s: streams %d..%lld outside 0..%d\n", what, first_stream, (long long)first_stream + count - 1, streams - 1);
+        abort();
+    }
+}
+
+void HEVM::io_reserve(u64 *&block, size_t &have, size_t bytes)
+{
+    if (bytes <= have) return;
+    if (block) (void)vm_free(block); // (nothing of an earlier call is in flight: every batch call ends with a synchronisation)
+    block = nullptr, have = 0;
+    DC_HIP_CHECK(vm_malloc(&block, bytes));
+    have = bytes;
+}
+
+// io.h_tab -> the device, in stream order
+void *HEVM::io_upload_tables(size_t bytes)
+{
+    if (bytes > io.tab_bytes) {
+        if (io.tab) (void)vm_free(io.tab);
+        io.tab = nullptr, io.tab_bytes = 0;
+        DC_HIP_CHECK(vm_malloc(&io.tab, bytes));
+        io.tab_bytes = bytes;
+    }
+    DC_HIP_CHECK(hipMemcpyAsync(io.tab, io.h_tab.data(), bytes, hipMemcpyHostToDevice, S()));
+    return io.tab;
+}
+
+namespace {
+// the call's item tables, laid out one after the other in HEVM::IoBatch::h_tab (16-byte aligned)
+struct IoTabLayout {
+    size_t bytes = 0;
+    size_t add(size_t elem, size_t count)
+    {
+        const size_t off = bytes;
+        bytes = (bytes + elem * count + 15) & ~(size_t)15;
+        return off;
+    }
+};
+int ntt_launches(const Context &c, bool inverse, int limbs) { return ntt_full_supported(c) && ntt_full_pays(inverse, limbs) ? 1 : 2; }
+} // namespace
+
+// `count` calls of encrypt() on streams first_stream ... in ascending order, as one launch sequence per chunk: the device encoder on all
+// inputs (enc_batch: the host encoder's coefficients bit for bit), the zero-encryptions at the argument's level by the identity of
+// plan_zero_encrypt (option zenc_head = 1: only u is transformed; 0: Encryptor::encrypt's sequence, batched -- the same limbs) straight
+// into the streams' register slices, and + plaintext on c0 (io_batch.hip).  Encryption k draws from object enc_counter + k, as the k-th
+// sequential call would.
+void HEVM::encrypt_batch(int64_t arg, const double *vals, int len, int64_t stride, int first_stream, int count, int where)
+{
+    static const char *const me = "hevm_encrypt_batch";
+    if (!keys.pk) {
+        fprintf(stderr, "[dacapo_amd] %s: this VM has no public key\n", me);
+        abort();
+    }
+    io_check_streams(me, first_stream, count);
+    if (len < 1 || stride < (int64_t)len || !vals || (where != 0 && where != 1)) {
+        fprintf(stderr, "[dacapo_amd] %s: needs values, len >= 1, stride >= len and where = 0 (host) or 1 (device): len %d, stride %lld, where %d\n", me,
+                len, (long long)stride, where);
+        abort();
+    }
+    if (arg < 0 || (size_t)arg >= arg_level.size()) {
+        fprintf(stderr, "[dacapo_amd] %s: argument %lld outside the loaded program's %zu\n", me, (long long)arg, arg_level.size());
+        abort();
+    }
+    Context &c = *ctx;
+    const size_t N = c.N, slots = N >> 1, slice = (size_t)2 * c.K * N;
+    const int ell = (int)arg_level[(size_t)arg], cnt = ell + 1;
+    if (ell < 1 || ell > c.max_level()) {
+        fprintf(stderr, "[dacapo_amd] encode: level %d outside 1..%d\n", ell, c.max_level());
+        abort();
+    }
+    const double scale = pow(2.0, (double)(int)arg_scale[(size_t)arg]);
+    io.launches = io.chunks = 0;
+    hevm_ctxt &r = reg((size_t)arg);
+    if (host_encoder) { // comparison mode: the single-stream path, once per stream
+        std::vector<double> host;
+        if (where == 1) {
+            host.resize((size_t)(count - 1) * (size_t)stride + (size_t)len);
+            DC_HIP_CHECK(hipMemcpy(host.data(), vals, host.size() * sizeof(double), hipMemcpyDeviceToHost));
+            vals = host.data();
+        }
+        const int keep = sel;
+        for (int k = 0; k < count; k++) {
+            select_stream(first_stream + k);
+            encrypt(arg, vals + (size_t)k * (size_t)stride, len);
+        }
+        select_stream(keep);
+        io.chunks = count;
+        return;
+    }
+    reg_base[(size_t)arg] = home[(size_t)arg]; // program inputs always live in the register's own block (as encrypt)
+    r.data = reg_base[(size_t)arg] + (size_t)sel * slice;
+    r.poly_stride = (int64_t)c.K * (int64_t)N;
+    ensure_enc_tables();
+    const size_t w = std::min((size_t)len, slots); // src[i % len] for i < N/2 reads no further
+    const bool hook = test_zero_enc, head = zenc_head && !hook;
+    // u64 words of one item: staged values, the encoder's complex vector, the plaintext; then the zero-encryption's own
+    const size_t zenc_words = hook ? 0 : head ? (size_t)cnt * N + N / 4 + 2 * N + (size_t)2 * ell * N : (size_t)7 * cnt * N + 2 * N;
+    const size_t per_item = slots + 2 * N + (size_t)ell * N + zenc_words;
+    const size_t C = (size_t)std::min(io_chunk(per_item * sizeof(u64)), count);
+    io_reserve(io.enc, io.enc_bytes, C * per_item * sizeof(u64));
+    double *stage = reinterpret_cast<double *>(io.enc);                      // [C][N/2]
+    double2 *fft = reinterpret_cast<double2 *>(io.enc + C * slots);          // [C][N]
+    u64 *pt = io.enc + C * slots + C * 2 * N;                                // [C][ell][N]
+    u64 *ue = pt + C * (size_t)ell * N;                                      // head: u [C][cnt][N]; else u, e0, e1 [C][3][cnt][N]
+    signed char *noise = reinterpret_cast<signed char *>(ue + C * (size_t)cnt * N); // head: e0, e1 [C][2][N] bytes
+    u64 *prod = ue + C * (size_t)3 * cnt * N;                                // (zenc_head = 0) pk * u + e [C][2][cnt][N]
+    u64 *digits = head ? ue + C * (size_t)cnt * N + C * (N / 4) : prod + C * (size_t)2 * cnt * N; // [2C][N]
+    u64 *tmp = digits + C * 2 * N;                                           // [2C][ell][N] ([2C][cnt][N] reserved with zenc_head = 0)
+    if (!io.d_overflow) DC_HIP_CHECK(vm_malloc(&io.d_overflow, sizeof(int)));
+    DC_HIP_CHECK(hipMemsetAsync(io.d_overflow, 0, sizeof(int), S()));
+
+    IoTabLayout lay;
+    const size_t o_enc = lay.add(sizeof(EncItem), (size_t)count), o_dst = lay.add(sizeof(CtView), (size_t)count),
+                 o_z = lay.add(head ? sizeof(ZencItem) : sizeof(RsItem), (size_t)count);
+    io.h_tab.assign(lay.bytes, 0);
+    EncItem *h_enc = reinterpret_cast<EncItem *>(io.h_tab.data() + o_enc);
+    CtView *h_dst = reinterpret_cast<CtView *>(io.h_tab.data() + o_dst);
+    for (int k = 0; k < count; k++) {
+        const size_t j = (size_t)k % C; // position in its chunk
+        const CtView dst{ home[(size_t)arg] + (size_t)(first_stream + k) * slice, (long)c.K * (long)N };
+        h_enc[k] = EncItem{ where == 1 ? (size_t)k * (size_t)stride : j * w, (u32)w, 0u, scale / (double)N };
+        h_dst[k] = dst;
+        if (head)
+            reinterpret_cast<ZencItem *>(io.h_tab.data() + o_z)[k] = ZencItem{ ue + j * (size_t)cnt * N, dst };
+        else
+            reinterpret_cast<RsItem *>(io.h_tab.data() + o_z)[k] = RsItem{ CtView{ prod + j * (size_t)2 * cnt * N, (long)cnt * (long)N }, dst };
+    }
+    const unsigned char *d_tab = static_cast<const unsigned char *>(io_upload_tables(lay.bytes));
+    const EncItem *d_enc = reinterpret_cast<const EncItem *>(d_tab + o_enc);
+    const CtView *d_dst = reinterpret_cast<const CtView *>(d_tab + o_dst);
+    const ZencItem *d_zenc = reinterpret_cast<const ZencItem *>(d_tab + o_z);
+    const RsItem *d_rs = reinterpret_cast<const RsItem *>(d_tab + o_z);
+
+    for (int k0 = 0; k0 < count; k0 += (int)C) {
+        const int B = std::min((int)C, count - k0);
+        if (where == 0) // the one copy of the chunk's values: B rows of w doubles, `stride` apart on the host
+            DC_HIP_CHECK(hipMemcpy2DAsync(stage, w * sizeof(double), vals + (size_t)k0 * (size_t)stride, (size_t)stride * sizeof(double),
+                                          w * sizeof(double), (size_t)B, hipMemcpyHostToDevice, S()));
+        enc_batch(c, enc_tables, where == 0 ? stage : vals, d_enc + k0, B, ell, fft, pt, io.d_overflow, S());
+        io.launches += c.logN + 2 + ntt_launches(c, false, B * ell);
+        if (hook) { // TEST HOOK: (plaintext, 0)
+            io_add_plain(c, d_dst + k0, pt, B, ell, true, S());
+            io.launches += 1;
+        } else {
+            const dim3 sgrid((unsigned)(N / (kRngCoefs * kVmThreads)), (unsigned)(3 * B));
+            if (head) {
+                DC_LAUNCH(sample_zenc_batch_kernel, sgrid, dim3(kVmThreads), 0, S(), ue, noise, N, cnt, rng.secret, enc_counter + (u64)k0, c.d_mods,
+                          d_epoch);
+                launch_ntt(c, false, ue, (long)N, cnt * B, nullptr, 0, cnt, S());
+                f_irows_zenc(c, d_zenc + k0, keys.pk, ell, digits, B, S());
+                f_dr_noise_icols_lift_fcols(c, digits, (long)N, tmp, 2 * B, ell, ell, noise, S());
+                f_frows_zenc_final(c, tmp, d_zenc + k0, keys.pk, B, ell, S());
+                io.launches += 4 + ntt_launches(c, false, cnt * B);
+            } else {
+                DC_LAUNCH(sample_enc_batch_kernel, sgrid, dim3(kVmThreads), 0, S(), ue, N, cnt, rng.secret, enc_counter + (u64)k0, c.d_mods, d_epoch);
+                launch_ntt(c, false, ue, (long)N, 3 * cnt * B, nullptr, 0, cnt, S());
+                DC_LAUNCH(pk_encrypt_batch_kernel, dim3((unsigned)(N / (2 * kVmThreads)), (unsigned)cnt, (unsigned)(2 * B)), dim3(kVmThreads), 0, S(),
+                          prod, keys.pk, (long)c.K * (long)N, ue, cnt, N, c.d_mods);
+                BatchWs ws;
+                ws.digits = digits, ws.tmp = tmp;
+                b_rescale(c, ws, d_rs + k0, B, cnt, S()); // divide-and-round by the extra prime, straight into the register slices
+                io.launches += 5 + ntt_launches(c, false, 3 * cnt * B);
+            }
+            io_add_plain(c, d_dst + k0, pt, B, ell, false, S());
+            io.launches += 1;
+        }
+        io.chunks++;
+    }
+    if (!hook) enc_counter += (u64)count;
+    r.level = ell;
+    r.scale = scale;
+    int overflow = 0;
+    DC_HIP_CHECK(hipMemcpyAsync(&overflow, io.d_overflow, sizeof(int), hipMemcpyDeviceToHost, S()));
+    DC_HIP_CHECK(hipStreamSynchronize(S()));
+    if (overflow) {
+        fprintf(stderr, "[dacapo_amd] encode: coefficient does not fit 120 bits (scale too large)\n");
+        abort();
+    }
+}
+
+// `count` calls of decrypt() on register i of streams first_stream ...: c0 + c1 s in the first inverse phase of all items (opcode 10's
+// f_irows_decrypt_items), the rest of the inverse transform, the composition and the special FFT with the item in grid.y (io_batch.hip).
+void HEVM::decrypt_batch(int64_t i, double *out, int64_t stride, int first_stream, int count, int where)
+{
+    static const char *const me = "hevm_decrypt_batch";
+    if (!keys.sk) {
+        fprintf(stderr, "[dacapo_amd] %s: this VM has no secret key\n", me);
+        abort();
+    }
+    io_check_streams(me, first_stream, count);
+    Context &c = *ctx;
+    const size_t N = c.N, slots = N >> 1, slice = (size_t)2 * c.K * N;
+    if (stride < (int64_t)slots || !out || (where != 0 && where != 1)) {
+        fprintf(stderr, "[dacapo_amd] %s: needs an output, stride >= N/2 = %zu and where = 0 (host) or 1 (device): stride %lld, where %d\n", me, slots,
+                (long long)stride, where);
+        abort();
+    }
+    if (i < 0 || (size_t)i >= ciphers.size()) {
+        fprintf(stderr, "[dacapo_amd] %s: register %lld outside the VM's %zu\n", me, (long long)i, ciphers.size());
+        abort();
+    }
+    const hevm_ctxt &ct = reg((size_t)i);
+    if (ct.level < 1) {
+        fprintf(stderr, "[dacapo_amd] %s: empty register %lld\n", me, (long long)i);
+        abort();
+    }
+    io.launches = io.chunks = 0;
+    if (host_encoder) { // comparison mode: the single-stream path, once per stream
+        std::vector<double> host(slots);
+        const int keep = sel;
+        for (int k = 0; k < count; k++) {
+            select_stream(first_stream + k);
+            decrypt(i, where == 1 ? host.data() : out + (size_t)k * (size_t)stride);
+            if (where == 1) DC_HIP_CHECK(hipMemcpy(out + (size_t)k * (size_t)stride, host.data(), slots * sizeof(double), hipMemcpyHostToDevice));
+        }
+        select_stream(keep);
+        io.chunks = count;
+        return;
+    }
+    const int ell = decode_limbs(ct.level);
+    ensure_enc_tables();
+    const CrtTables &tb = crt_tables(ell);
+    const CrtDev cd{ tb.inv, tb.mmod, tb.hmod, tb.hdig, tb.mdbl };
+    const size_t per_item = (size_t)ell * N + 2 * N + slots; // u64 words: the plaintext's limbs, the FFT's complex vector, the slot values
+    const size_t C = (size_t)std::min(io_chunk(per_item * sizeof(u64)), count);
+    io_reserve(io.dec, io.dec_bytes, C * per_item * sizeof(u64));
+    u64 *pt = io.dec;                                                            // [C][ell][N]
+    double2 *v = reinterpret_cast<double2 *>(io.dec + C * (size_t)ell * N);      // [C][N]
+    double *vals = reinterpret_cast<double *>(io.dec + C * (size_t)ell * N + C * 2 * N); // [C][N/2] (where = 0)
+
+    IoTabLayout lay;
+    const size_t o_it = lay.add(sizeof(BootItem), (size_t)count);
+    io.h_tab.assign(lay.bytes, 0);
+    BootItem *h_it = reinterpret_cast<BootItem *>(io.h_tab.data() + o_it);
+    for (int k = 0; k < count; k++) {
+        BootItem bi{};
+        bi.src = bi.dst = CtView{ reg_base[(size_t)i] + (size_t)(first_stream + k) * slice, (long)ct.poly_stride };
+        h_it[k] = bi;
+    }
+    const BootItem *d_it = reinterpret_cast<const BootItem *>(static_cast<const unsigned char *>(io_upload_tables(lay.bytes)) + o_it);
+
+    for (int k0 = 0; k0 < count; k0 += (int)C) {
+        const int B = std::min((int)C, count - k0);
+        f_irows_decrypt_items(c, d_it + k0, nullptr, keys.sk, ell, pt, B, S());
+        launch_ntt_cols_inv(c, pt, (long)N, B * ell, nullptr, 0, ell, S());
+        io_dec_crt(c, v, pt, B, ell, cd, 1.0 / ct.scale, S());
+        if (where == 1) // straight into the caller's device buffer
+            io_dec_fft(c, enc_tables, v, out + (size_t)k0 * (size_t)stride, (long)stride, B, S());
+        else {
+            io_dec_fft(c, enc_tables, v, vals, (long)slots, B, S());
+            DC_HIP_CHECK(hipMemcpy2DAsync(out + (size_t)k0 * (size_t)stride, (size_t)stride * sizeof(double), vals, slots * sizeof(double),
+                                          slots * sizeof(double), (size_t)B, hipMemcpyDeviceToHost, S()));
+        }
+        io.launches += 3 + c.logN + 1;
+        io.chunks++;
+    }
+    DC_HIP_CHECK(hipStreamSynchronize(S()));
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -2127,6 +2396,30 @@ void hevm_load_mem(void *vm, const void *cst, uint64_t cst_len, const void *hevm
 }
 void hevm_set_streams(void *vm, int n) { V(vm)->set_streams(n); }
 void hevm_select_stream(void *vm, int s) { V(vm)->select_stream(s); }
+// all streams' inputs and results at once (HEVM::encrypt_batch / decrypt_batch)
+void hevm_encrypt_batch(void *vm, int64_t arg, const double *vals, int len, int64_t stride, int first_stream, int count, int where)
+{
+    V(vm)->encrypt_batch(arg, vals, len, stride, first_stream, count, where);
+}
+void hevm_decrypt_batch(void *vm, int64_t reg, double *out, int64_t stride, int first_stream, int count, int where)
+{
+    V(vm)->decrypt_batch(reg, out, stride, first_stream, count, where);
+}
+void hevm_decrypt_result_batch(void *vm, int64_t i, double *out, int64_t stride, int first_stream, int count, int where)
+{
+    auto hevm = V(vm);
+    if (i < 0 || (size_t)i >= hevm->res_dst.size()) {
+        fprintf(stderr, "[dacapo_amd] hevm_decrypt_result_batch: result %lld outside the loaded program's %zu\n", (long long)i, hevm->res_dst.size());
+        abort();
+    }
+    hevm->decrypt_batch((int64_t)hevm->res_dst[(size_t)i], out, stride, first_stream, count, where);
+}
+void hevm_last_io_stats(void *vm, int64_t *launches, int64_t *chunks)
+{
+    auto h = V(vm);
+    if (launches) *launches = h->io.launches;
+    if (chunks) *chunks = h->io.chunks;
+}
 double hevm_last_run_bootstrap_seconds(void *vm) { return V(vm)->t_bootstrap; }
 uint64_t hevm_plaintext_bytes(void *vm)
 { // HBM held for the program's plaintexts: the pre-encoded pool, or (on-line encode) the resident constants + the encode window

@@ -18,6 +18,7 @@
 #include "seal_serial.hpp"
 #include "kernels.hpp"
 #include "encoder.hpp"
+#include "io_batch.hpp"
 #include "plan.hpp"
 
 namespace dacapo {
@@ -368,6 +369,35 @@ class HEVM {
     void encrypt_plain(hevm_ctxt &dst, const Plain &pt);
     void encrypt(int64_t i, const double *dat, int len);
     void decrypt(int64_t i, double *out);
+    // limbs a register at `level` is decoded from (decrypt and decrypt_batch: the device CRT composes at most 16, see decrypt)
+    int decode_limbs(int level) const { return !host_encoder && level > 16 ? 16 : level; }
+
+    // ---- batched encrypt / decrypt (hevm_encrypt_batch / hevm_decrypt_batch): `count` streams' inputs or results as ONE launch sequence and
+    // one synchronisation, values in host (where = 0) or device (where = 1) memory.  Limbs and doubles equal `count` calls of encrypt /
+    // decrypt on those streams in ascending order.  The launches per chunk do not depend on the number of items in it (but for the
+    // transform's own form, kernels.hpp launch_ntt: one launch or two by its limb count at N = 2^15).
+    // Scratch is the VM's own (a client VM has no plan to borrow from): one block per direction, allocated on first use and grown when a call
+    // needs more.  Chunk rule: io_chunk(per_item) = min(kIoChunk, max(1, kIoScratchBytes / per_item)) items per pass of the sequence, per_item
+    // being the bytes one item needs at the call's level -- so a block is at most max(kIoScratchBytes, one item): at N = 2^17 with 31
+    // primes an encryption at level 30 needs 126 MiB (limbs of 1 MiB: u over 31 primes, plaintext 30, divide-and-round 62, encoder 2.5, noise
+    // 0.25), 8 items to a chunk, 1 GiB; a decryption 18.5 MiB (16 limbs at most, the FFT's 2, the slots' 0.5).  Chunks reuse the block in stream order.
+    static constexpr int kIoChunk = 32;
+    static constexpr size_t kIoScratchBytes = (size_t)1 << 30;
+    struct IoBatch {
+        u64 *enc = nullptr, *dec = nullptr; // the two scratch blocks
+        size_t enc_bytes = 0, dec_bytes = 0;
+        void *tab = nullptr;                // device item tables of the call in flight
+        size_t tab_bytes = 0;
+        std::vector<unsigned char> h_tab;   // their host image (lives until the next call: the upload is asynchronous)
+        int *d_overflow = nullptr;          // the encoder's "coefficient does not fit" flag
+        int64_t launches = 0, chunks = 0;   // hevm_last_io_stats: kernel launches and chunks of the last batch call
+    } io;
+    int io_chunk(size_t per_item_bytes) const { return (int)std::min<size_t>((size_t)kIoChunk, std::max<size_t>(1, kIoScratchBytes / per_item_bytes)); }
+    void io_check_streams(const char *what, int first_stream, int count) const;
+    void io_reserve(u64 *&block, size_t &have, size_t bytes);
+    void *io_upload_tables(size_t bytes);
+    void encrypt_batch(int64_t arg, const double *vals, int len, int64_t stride, int first_stream, int count, int where);
+    void decrypt_batch(int64_t reg, double *out, int64_t stride, int first_stream, int count, int where);
     void run();
 
     // opcode handlers (SEAL_HEVM.cpp:268-334)

@@ -109,6 +109,17 @@ def bind_vm_lib(path):
     L.hevm_last_run_relin_stats.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
     L.hevm_set_streams.argtypes = [ctypes.c_void_p, ctypes.c_int]
     L.hevm_select_stream.argtypes = [ctypes.c_void_p, ctypes.c_int]
+    # all streams' inputs / results at once; the value pointers are host or device addresses (last argument: 0 / 1)
+    L.hevm_encrypt_batch.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                     ctypes.c_int]
+    L.hevm_encrypt_batch.restype = None
+    for f in (L.hevm_decrypt_batch, L.hevm_decrypt_result_batch):
+        f.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int]
+        f.restype = None
+    L.hevm_last_io_stats.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
+    L.hevm_last_io_stats.restype = None
+    L.dc_device_sync.argtypes = []
+    L.dc_device_sync.restype = None
     L.hevm_last_run_bootstrap_seconds.argtypes = [ctypes.c_void_p]
     L.hevm_last_run_bootstrap_seconds.restype = ctypes.c_double
     L.hevm_plaintext_bytes.argtypes = [ctypes.c_void_p]
@@ -239,6 +250,7 @@ class HEVM:
         self.lw = lw_ = bind_vm_lib(LIB_PATH_GW) if narrow else lw
         self.option = option
         self.slots = None
+        self.streams = 1
         opts = dict(vm_options or {})
         if ks_special != 1 or (ks_alpha or 1) != 1:
             opts.update(ks_special=ks_special, ks_alpha=ks_alpha or ks_special)
@@ -308,6 +320,7 @@ class HEVM:
     def set_streams(self, n):
         """extension: n independent ciphertext streams through the same program (call before load)"""
         self.lw.hevm_set_streams(self.vm, n)
+        self.streams = max(1, int(n))
 
     def select_stream(self, s):
         self.lw.hevm_select_stream(self.vm, s)
@@ -322,6 +335,63 @@ class HEVM:
         data = np.ascontiguousarray(data, dtype=np.float64)
         carr = data.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
         self.lw.encrypt(self.vm, i, carr, len(data))
+
+    @staticmethod
+    def _device_f64(t, ndim):
+        """a device-resident array for the batch calls: anything with data_ptr(), is_cuda, dtype, shape and is_contiguous() -- a contiguous
+        float64 torch ROCm tensor (this module does not import torch)"""
+        if not (hasattr(t, "data_ptr") and getattr(t, "is_cuda", False)):
+            return False
+        if not str(t.dtype).endswith("float64") or len(t.shape) != ndim or not t.is_contiguous():
+            raise ValueError(f"a device array must be contiguous float64 with {ndim} dimensions (got {t.dtype}, shape {tuple(t.shape)})")
+        return True
+
+    def setInputs(self, i, data, first_stream=0):
+        """extension (hevm_encrypt_batch): input i of streams first_stream ... first_stream + count - 1 from data[count, len] in one launch
+        sequence and one synchronisation -- limb for limb what select_stream(s) + setInput(i, data[s - first_stream]) per stream gives,
+        randomness included; the selected stream stays.  data: a float64 ndarray (host path), or a 2-D contiguous float64 torch ROCm
+        tensor (device path: the values never touch the host).  The call runs on the VM's own stream: on the device path dc_device_sync()
+        is called first, which orders it after whatever the caller's streams still have in flight on `data`."""
+        if self._device_f64(data, 2):
+            count, length = int(data.shape[0]), int(data.shape[1])
+            self.lw.dc_device_sync()
+            self.lw.hevm_encrypt_batch(self.vm, i, ctypes.c_void_p(data.data_ptr()), length, length, first_stream, count, 1)
+            return
+        data = np.ascontiguousarray(data, dtype=np.float64)
+        if data.ndim != 2:
+            raise ValueError(f"setInputs takes data[count, len] (got shape {data.shape})")
+        count, length = data.shape
+        self.lw.hevm_encrypt_batch(self.vm, i, data.ctypes.data_as(ctypes.c_void_p), length, length, first_stream, count, 0)
+
+    def getOutputs(self, first_stream=0, count=None, out=None):
+        """extension (hevm_decrypt_result_batch): every result of streams first_stream ... as an ndarray [count, reslen, slots], one launch
+        sequence and one synchronisation per result -- bit for bit the stack of select_stream(s) + getOutput().  count: default every
+        stream from first_stream on (set_streams), or what `out` holds.  out: a float64 torch ROCm tensor of that shape is filled on
+        the device (no host copy) and returned."""
+        if out is not None:
+            if not self._device_f64(out, 3):
+                raise ValueError("out must be a device-resident float64 array")
+            if count is None:
+                count = int(out.shape[0])
+            if tuple(out.shape) != (count, self.reslen, self.slots):
+                raise ValueError(f"out must have shape {(count, self.reslen, self.slots)} (got {tuple(out.shape)})")
+            self.lw.dc_device_sync()
+            for i in range(self.reslen):
+                self.lw.hevm_decrypt_result_batch(self.vm, i, ctypes.c_void_p(out.data_ptr() + i * self.slots * 8), self.reslen * self.slots,
+                                                  first_stream, count, 1)
+            return out
+        count = self.streams - first_stream if count is None else int(count)
+        result = np.zeros((count, self.reslen, self.slots), dtype=np.float64)
+        for i in range(self.reslen):
+            self.lw.hevm_decrypt_result_batch(self.vm, i, ctypes.c_void_p(result.ctypes.data + i * self.slots * 8), self.reslen * self.slots,
+                                              first_stream, count, 0)
+        return result
+
+    def io_stats(self):
+        """kernel launches and chunks of the last setInputs / getOutputs-style batch call (hevm_last_io_stats)"""
+        n, ch = ctypes.c_int64(), ctypes.c_int64()
+        self.lw.hevm_last_io_stats(self.vm, ctypes.byref(n), ctypes.byref(ch))
+        return {"launches": n.value, "chunks": ch.value}
 
     def setDebug(self, enable):
         self.lw.setDebug(self.vm, enable)

@@ -154,6 +154,26 @@ void hevm_last_run_relin_stats(void *vm, int64_t *groups, int64_t *products);
  * encrypt / decrypt / decrypt_result / getCtxt then address the stream chosen with hevm_select_stream. */
 void hevm_set_streams(void *vm, int n);
 void hevm_select_stream(void *vm, int s);
+/* All streams' inputs and results at once: what `count` calls of encrypt / decrypt / decrypt_result on streams first_stream ...
+ * first_stream + count - 1 (ascending, each after hevm_select_stream) give, as ONE launch sequence and ONE synchronisation -- the device
+ * encoder and decoder on all items, the zero-encryptions batched as run()'s are.  where: 0 = vals / out are host memory, 1 = device memory
+ * (no host copy of the values is made; the call runs on the VM's own stream, so the caller orders it after whatever produced the values,
+ * e.g. dc_device_sync()).  The selected stream does not change.
+ * hevm_encrypt_batch: input k is `len` doubles at vals + k * stride (stride >= len >= 1), tiled over the slots as src[i % len] and encoded at
+ * argument `arg`'s level and scale, encrypted into register `arg` of stream first_stream + k.  Limb for limb the sequential calls' result,
+ * randomness included: encryption k is the VM's (encryptions made so far + k)-th.
+ * hevm_decrypt_batch / hevm_decrypt_result_batch: N/2 doubles per stream at out + k * stride (stride >= N/2), bit for bit decrypt's /
+ * decrypt_result's.
+ * Work is cut into chunks of at most 32 streams (fewer where a chunk's scratch would pass 1 GiB); a chunk's launch count does not depend on
+ * the streams in it.  hevm_last_io_stats: kernel launches and chunks of the last batch call.  Option "host_encoder" = 1 (comparison mode)
+ * runs the single-stream path once per stream instead (launches 0, chunks = count).
+ * Like everything here, bad arguments abort with a message: "streams A..B outside 0..S-1", "count C is not positive", "this VM has no
+ * public key" (encrypt; a server VM) / "no secret key" (decrypt), "empty register", an argument, result or register index outside the
+ * program's, len / stride / where out of range. */
+void hevm_encrypt_batch(void *vm, int64_t arg, const double *vals, int len, int64_t stride, int first_stream, int count, int where);
+void hevm_decrypt_batch(void *vm, int64_t reg, double *out, int64_t stride, int first_stream, int count, int where);
+void hevm_decrypt_result_batch(void *vm, int64_t i, double *out, int64_t stride, int first_stream, int count, int where);
+void hevm_last_io_stats(void *vm, int64_t *launches, int64_t *chunks);
 /* wall seconds the last run() spent inside opcode 10 (decrypt / re-encode / encrypt) */
 double hevm_last_run_bootstrap_seconds(void *vm);
 /* HBM bytes held for the loaded program's plaintexts (pre-encoded pool, or constants + encode window with
