@@ -391,13 +391,14 @@ void dc_ct_rotate_hoisted(dc_context *ctx, uint64_t *const *dsts, long dst_strid
 // dst = sum_k [plains[k] .] galois_k(srcs[k]) with ONE division by P (hoist_ks.hip hoist_rotate_sum): equal source pointers share a
 // decomposition, which is why the decompositions need scratch of their own here ([distinct sources][l][N] digits and [..][l*l][N] lifted limbs,
 // kept in the handle like the rest).
-void dc_ct_rotate_sum_hoisted(dc_context *ctx, uint64_t *dst, long dst_stride, const uint64_t *const *srcs, long src_stride,
-                              const uint32_t *galois_elts, const uint64_t *const *galois_keys, const uint64_t *const *plains,
-                              const uint64_t *const *plains_sp, int count, int ell, void *stream)
+// addend: a ciphertext added to the sum exactly by the inner-product launch (the group's src field, hoist_ks.hip f_ks_gsum_kernel ADDEND), or null
+static void rotate_sum_hoisted(dc_context *ctx, const char *who, uint64_t *dst, long dst_stride, const uint64_t *addend, long addend_stride,
+                               const uint64_t *const *srcs, long src_stride, const uint32_t *galois_elts, const uint64_t *const *galois_keys,
+                               const uint64_t *const *plains, const uint64_t *const *plains_sp, int count, int ell, void *stream)
 {
     const size_t B = (size_t)count;
     size_t U = 0;
-    const KsItem *d = hoist_items(ctx, "dc_ct_rotate_sum_hoisted", " (ks_special > 1)", "members", count, ell, 1, S(stream), [&](std::vector<KsItem> &h) {
+    const KsItem *d = hoist_items(ctx, who, " (ks_special > 1)", "members", count, ell, 1, S(stream), [&](std::vector<KsItem> &h) {
         // members source-major (stable: equal sources keep the caller's order); then the group; then the distinct sources
         std::vector<size_t> order(B);
         for (size_t b = 0; b < B; b++) order[b] = b;
@@ -406,19 +407,34 @@ void dc_ct_rotate_sum_hoisted(dc_context *ctx, uint64_t *dst, long dst_stride, c
         for (size_t b : order) {
             const u64 *pl = plains ? plains[b] : nullptr, *psp = plains_sp ? plains_sp[b] : nullptr;
             if ((pl == nullptr) != (psp == nullptr)) {
-                fprintf(stderr, "[dacapo_amd] dc_ct_rotate_sum_hoisted: member %zu has one of plains / plains_sp only\n", b);
+                fprintf(stderr, "[dacapo_amd] %s: member %zu has one of plains / plains_sp only\n", who, b);
                 abort();
             }
             const CtView sv = V(srcs[b], src_stride);
             if (sources.empty() || sources.back().src.p != sv.p) sources.push_back(KsItem{ sv, sv, nullptr, 1u, 0 });
             h.push_back(KsItem{ sv, V(dst, dst_stride), galois_keys[b], galois_elts[b], (u32)(sources.size() - 1), pl, psp });
         }
-        h.push_back(KsItem{ V(dst, dst_stride), V(dst, dst_stride), nullptr, 0u, (u32)B });
+        h.push_back(KsItem{ addend ? V(addend, addend_stride) : V(dst, dst_stride), V(dst, dst_stride), nullptr, 0u, (u32)B });
         h.insert(h.end(), sources.begin(), sources.end());
         return U = sources.size();
     });
     const BatchWs w{ nullptr, ctx->hoist_digits, ctx->hoist_ext, ctx->hoist_acc, ctx->hoist_tmp };
-    hoist_rotate_sum(*ctx->c, w, d, d + B + 1, count, (int)U, d + B, 1, ell, S(stream));
+    hoist_rotate_sum(*ctx->c, w, d, d + B + 1, count, (int)U, d + B, 1, ell, S(stream), addend != nullptr);
+}
+void dc_ct_rotate_sum_hoisted(dc_context *ctx, uint64_t *dst, long dst_stride, const uint64_t *const *srcs, long src_stride,
+                              const uint32_t *galois_elts, const uint64_t *const *galois_keys, const uint64_t *const *plains,
+                              const uint64_t *const *plains_sp, int count, int ell, void *stream)
+{
+    rotate_sum_hoisted(ctx, "dc_ct_rotate_sum_hoisted", dst, dst_stride, nullptr, 0, srcs, src_stride, galois_elts, galois_keys, plains, plains_sp,
+                       count, ell, stream);
+}
+// ... plus `addend`, a ciphertext at level ell that the same launches add exactly (NULL: dc_ct_rotate_sum_hoisted itself)
+void dc_ct_rotate_sum_hoisted_add(dc_context *ctx, uint64_t *dst, long dst_stride, const uint64_t *addend, long addend_stride,
+                                  const uint64_t *const *srcs, long src_stride, const uint32_t *galois_elts, const uint64_t *const *galois_keys,
+                                  const uint64_t *const *plains, const uint64_t *const *plains_sp, int count, int ell, void *stream)
+{
+    rotate_sum_hoisted(ctx, "dc_ct_rotate_sum_hoisted_add", dst, dst_stride, addend, addend_stride, srcs, src_stride, galois_elts, galois_keys,
+                       plains, plains_sp, count, ell, stream);
 }
 void dc_ct_rescale(dc_context *ctx, uint64_t *dst, long dst_stride, const uint64_t *src, long src_stride, int ell, void *stream)
 {

@@ -485,6 +485,30 @@ void HEVM::init_context(int logN, int K, const u64 *primes, int dir_ksp, int dir
                         "three-part ciphertext has no grouped-digit key switch here\n", ksp, alpha);
         abort();
     }
+    ks_flatten = (int)option(OPT_KS_FLATTEN_SUMS);
+    if (ks_flatten) {
+        if (ks_flatten < 2 || ks_flatten > kFlattenMaxHops) {
+            fprintf(stderr, "[dacapo_amd] option ks_flatten_sums = %d: the most hops one flattened stage absorbs is 2 .. %d (2^%d - 1 = %d rotations are "
+                            "what one group of the lazy-sum kernel walks), or 0 = off\n", ks_flatten, kFlattenMaxHops, kFlattenMaxHops, (1 << kFlattenMaxHops) - 1);
+            abort();
+        }
+        if (ksp > 1 || alpha > 1) {
+            fprintf(stderr, "[dacapo_amd] option ks_flatten_sums = %d is for SEAL-layout keys (ks_special = 1); with ks_special = %d, ks_alpha = %d key "
+                            "switching uses grouped digits, whose lazy sums take no addend\n", ks_flatten, ksp, alpha);
+            abort();
+        }
+        if (!ks_hoist || !ks_lazy) {
+            fprintf(stderr, "[dacapo_amd] option ks_flatten_sums = %d needs%s%s%s: a flattened stage is a hoisted lazy sum -- the rotations of one source "
+                            "share its decomposition (ks_hoist) and one division by P (ks_lazy_sum)\n", ks_flatten, ks_hoist ? "" : " ks_hoist = 1",
+                    !ks_hoist && !ks_lazy ? " and" : "", ks_lazy ? "" : " ks_lazy_sum >= 1");
+            abort();
+        }
+        if (option(OPT_ROT_COMPOSE) != 0) {
+            fprintf(stderr, "[dacapo_amd] option ks_flatten_sums = %d does not combine with rot_compose = 1: a memoised hop may serve two rotate "
+                            "instructions, and a flattened stage takes its rotations' hops away\n", ks_flatten);
+            abort();
+        }
+    }
     zenc_head = option(OPT_ZENC_HEAD) != 0;
     // prime_bits = b (45..60; the generic-width build only): the chain CoeffModulus::Create(N, {b, b, ...}) instead of the reference's
     // 60-bit one (SEAL_HEVM.cpp:48-53) -- e.g. 51 for rescale primes of the HEaaN configuration's width
@@ -1774,6 +1798,52 @@ std::vector<u32> HEVM::rotate_hops(int steps) const
     return hops;
 }
 
+// Option ks_flatten_sums: the stages of the loaded program's rotate-and-add chains that one hoisted lazy sum with an addend can run
+// (plan_flatten.hpp), found on the instructions as plan_flatten_main.cpp walks them: registers renamed to the instructions that wrote them, an
+// input register r the value -1 - r, a value observable through a result register only.  every_key: as if every offset had a key (what
+// hevm_flatten_offsets asks); otherwise a stage needs a key for each of its members in this VM's key set.
+std::vector<FlattenGroup> HEVM::flatten_groups(bool every_key) const
+{
+    const size_t nops = ops.size(), nreg = ciphers.size();
+    const int slots = (int)(ctx->N >> 1);
+    std::vector<int> cur(nreg), kind(nops, FLAT_OTHER), src0(nops, 0), src1(nops, 0), offset(nops, 0), readers(nops, 0), result(nops, 0);
+    for (size_t r = 0; r < nreg; r++) cur[r] = -1 - (int)r;
+    for (size_t i = 0; i < nops; i++) {
+        const WireOp &op = ops[i];
+        const bool unary = op.opcode == 1 || op.opcode == 2 || op.opcode == 3 || op.opcode == 4 || op.opcode == 7 || op.opcode == 9 || op.opcode == 10 ||
+                           (op.opcode >= kOpConj && op.opcode <= kOpKeySwitch);
+        const bool binary = op.opcode == 6 || op.opcode == 8;
+        if (!unary && !binary) continue;
+        if (op.opcode == 4 && (int16_t)op.rhs <= 0) continue;                     // a zero modswitch leaves dst untouched
+        if (op.opcode == 1 && (int16_t)op.rhs == 0 && op.dst == op.lhs) continue; // ... and so does a rotation by 0 onto itself
+        if (op.lhs >= nreg || op.dst >= nreg || (binary && op.rhs >= nreg)) continue; // (load_program has checked the operands)
+        auto read = [&](uint16_t r) {
+            const int v = cur[r];
+            if (v >= 0) readers[(size_t)v]++;
+            return v;
+        };
+        src0[i] = read(op.lhs);
+        if (binary) src1[i] = read(op.rhs);
+        if (op.opcode == 1) kind[i] = FLAT_ROTATE, offset[i] = (int16_t)op.rhs;
+        if (op.opcode == 6) kind[i] = FLAT_ADDCC;
+        cur[op.dst] = (int)i;
+    }
+    for (uint64_t r : res_dst)
+        if (r < nreg && cur[(size_t)r] >= 0) result[(size_t)cur[(size_t)r]] = 1;
+    std::vector<int> keyed; // the offsets that have a key, from the Galois elements 3^k
+    if (!every_key) {
+        const u64 m = 2 * (u64)ctx->N;
+        u64 e = 3;
+        for (int k = 1; k < slots; k++, e = (e * 3) & (m - 1))
+            if (keys.galois.count((u32)e)) keyed.push_back(flatten_norm_offset(k, slots));
+        std::sort(keyed.begin(), keyed.end());
+    }
+    FlattenOps in;
+    in.n = (int)nops, in.kind = kind.data(), in.src0 = src0.data(), in.src1 = src1.data(), in.offset = offset.data(), in.readers = readers.data();
+    in.result = result.data();
+    return plan_flatten_groups(in, ks_flatten, slots, every_key ? nullptr : keyed.data(), (int)keyed.size());
+}
+
 // EXTENSION (option rot_compose = 1; off by default: SEAL's rotate_internal only ever composes from the power-of-two keys): a bounded key
 // set serving every offset, the way the reference's HEaaN runtime serves every rotation of a program from its 49 left-rotation keys
 // (HEAAN_HEVM.cpp:58-64,124-126).  A rotation without a direct key becomes the SHORTEST sum of offsets that have one -- two parts if any
@@ -2193,7 +2263,7 @@ void HEVM::execute()
 {
     memset(op_counts, 0, sizeof(op_counts));
     n_keyswitch = n_ntt = 0;
-    n_hops = n_decomp = 0, n_fold = 0, n_relin_groups = n_relin_products = 0;
+    n_hops = n_decomp = 0, n_fold = 0, n_relin_groups = n_relin_products = 0, n_flat_groups = n_flat_members = n_flat_hops = 0;
     t_bootstrap = 0.0;
     int i = (int)((header.hevm_header_size + config.config_body_length) / 8), j = 0;
     for (const WireOp &op : ops) {
@@ -2622,12 +2692,64 @@ int64_t hevm_plan_lazy_groups(void *vm, int32_t *out, int64_t cap)
     if (!h->plan.ready) return -1;
     std::vector<int32_t> flat;
     for (const auto &p : h->plan.pops)
-        if (!p.dead && p.kind == HEVM::P_ROTSUM) {
+        if (!p.dead && p.kind == HEVM::P_ROTSUM && p.addend < 0) { // (a flattened stage is no sum of rotate instructions: hevm_plan_flatten_groups)
             flat.push_back((int32_t)p.ops.size());
             flat.insert(flat.end(), p.ops.begin(), p.ops.end());
         }
     if (out && cap >= (int64_t)flat.size()) memcpy(out, flat.data(), flat.size() * sizeof(int32_t));
     return (int64_t)flat.size();
+}
+
+// option ks_flatten_sums: the distinct composite slot offsets that the loaded program's flattened stages would use at the VM's option value and
+// that have no key in its key set yet -- what a caller hands to hevm_add_rotation_keys before the first run() (and before a server's key
+// directory is written).  Writes up to cap of them, ascending; returns how many there are.  0 with the option off, under plan = 0 or with
+// nothing loaded.
+int hevm_flatten_offsets(void *vm, int64_t *out, int cap)
+{
+    auto h = V(vm);
+    if (!h->ks_flatten || !h->use_plan || h->ops.empty()) return 0; // (plan = 0 runs every rotate on its own)
+    std::set<int> missing;
+    for (const dacapo::FlattenGroup &g : h->flatten_groups(true))
+        for (int o : g.offsets) {
+            const uint32_t elt = dc_galois_elt_from_step(static_cast<dc_context *>(hevm_context(vm)), o);
+            if (elt && !h->keys.galois.count(elt)) missing.insert(o);
+        }
+    int n = 0;
+    for (int o : missing) {
+        if (out && n < cap) out[n] = o;
+        n++;
+    }
+    return n;
+}
+
+// ... the groups the plan of the last run() executed: out = [hops, closing_op, (rot_op, add_op) x hops, members, offset x members, ...] -- per
+// group the instruction indices of the stage's closing addcc and of its hops in chain order, and the members' signed slot offsets (member k - 1
+// <-> the subset of hops whose bits are set in k; the group's source and addend is what the first hop rotates): enough to replay the program
+// without knowing the pass.  Return conventions of hevm_plan_lazy_groups.
+int64_t hevm_plan_flatten_groups(void *vm, int32_t *out, int64_t cap)
+{
+    auto h = V(vm);
+    if (!h->plan.ready) return -1;
+    std::vector<int32_t> flat;
+    for (const auto &p : h->plan.pops)
+        if (!p.dead && p.kind == HEVM::P_ROTSUM && p.addend >= 0) {
+            flat.push_back((int32_t)(p.flat_ops.size() / 2));
+            flat.push_back((int32_t)p.op);
+            flat.insert(flat.end(), p.flat_ops.begin(), p.flat_ops.end());
+            flat.push_back((int32_t)p.flat_offsets.size());
+            flat.insert(flat.end(), p.flat_offsets.begin(), p.flat_offsets.end());
+        }
+    if (out && cap >= (int64_t)flat.size()) memcpy(out, flat.data(), flat.size() * sizeof(int32_t));
+    return (int64_t)flat.size();
+}
+
+// ... and how many the last run() executed: flattened stages, the rotations in them and the hops they absorbed, once per stream; 0 with the
+// option off and in the loop (plan = 0)
+void hevm_last_run_flatten_stats(void *vm, int64_t *groups, int64_t *members, int64_t *hops_absorbed)
+{
+    if (groups) *groups = V(vm)->n_flat_groups;
+    if (members) *members = V(vm)->n_flat_members;
+    if (hops_absorbed) *hops_absorbed = V(vm)->n_flat_hops;
 }
 
 // option ks_lazy_relin: the groups of ct x ct products that the plan of the last run() relinearises with one key switch each.

@@ -20,6 +20,7 @@
 #include "encoder.hpp"
 #include "io_batch.hpp"
 #include "plan.hpp"
+#include "plan_flatten.hpp"
 
 namespace dacapo {
 
@@ -190,6 +191,12 @@ class HEVM {
         // a P_MULSUM (option ks_lazy_relin: dst = relin(sum_k signs[k] srcs[2k] (x) srcs[2k + 1]), plan.hpp b_mul_sum_relin) lists its products: ops[k]
         // the mulcc instruction, op the addcc / negate instruction whose result it computes
         std::vector<int> signs;
+        // option ks_flatten_sums: a hop of a rotate instruction remembers the value the INSTRUCTION rotates (inst_src) and the instruction's first
+        // hop (first_hop: a pop index; the hops of one instruction are adjacent); a P_ROTSUM that stands for a stage of a rotate-and-add chain
+        // (plan_flatten.hpp) adds `addend` exactly in its inner-product launch and lists the stage's hops and its members' slot offsets:
+        // flat_ops = (rotate instruction, addcc instruction) per hop, op = the closing addcc
+        int inst_src = -1, first_hop = -1, addend = -1;
+        std::vector<int> flat_ops, flat_offsets;
         std::vector<int> plains; // P_ROTSUM, option hyb_double_hoist: the plaintext register multiplying rotation k before it joins the sum, or -1
     };
     struct Step {
@@ -202,6 +209,7 @@ class HEVM {
         bool fold_rs = false;               // P_MULCC, option ks_fold_rescale: every item also does the rescale that alone reads it (first: in d_mulrs);
                                             // those rescales are in no step of their own, and the step defines THEIR results
         int gfirst = 0, gcount = 0;         // P_SUM: the step's items as groups that share sources (plan.hpp SumGroup), when it runs that way; P_ROTSUM: its groups (in d_ks; option ks_lazy_sum: the distinct sources' items follow them)
+        bool addend = false;                // P_ROTSUM, option ks_flatten_sums: the groups' src fields are addends (or null), plan.hpp hoist_rotate_sum
         int unique = 0;                     // P_ROT, grouped-digit mode: distinct source ciphertexts among the items (shared decompositions)
                                             // ... and option ks_hoist (target == -2): the same count; d_ks[gfirst .. gfirst + unique) are the sources' items
         // what the step's launches read and write, by pool buffer (a value and its modswitch views share one): the edges of the explicitly
@@ -254,6 +262,7 @@ class HEVM {
         int64_t n_keyswitch = 0, n_ntt = 0;
         int64_t n_hops = 0, n_decomp = 0; // rotation hops and the decompositions computed for them (hevm_last_run_hoist_stats)
         int64_t n_relin_groups = 0, n_relin_products = 0; // P_MULSUM items and their terms (hevm_last_run_relin_stats)
+        int64_t n_flat_groups = 0, n_flat_members = 0, n_flat_hops = 0; // flattened stages, their rotations and the hops they absorbed, once per stream (hevm_last_run_flatten_stats)
         int64_t n_fold = 0;               // items of multiply steps that run with their rescale folded in (hevm_last_run_fold_rescale_stats)
         size_t launches = 0, max_live = 0;
         hipGraph_t graph = nullptr;
@@ -310,6 +319,10 @@ class HEVM {
     // option ks_lazy_relin = 1 (SEAL-layout keys): sums of single-use ct x ct products are relinearised once (plan_exec.hip section 1b;
     // plan_relin.hpp names the groups, plan.hpp b_mul_sum_relin runs them).  Changes the rounding: off by default.
     bool ks_lazy_relin = false;
+    // option ks_flatten_sums = f (2 .. 6; with ks_hoist and ks_lazy_sum): stages of up to f hops of a rotate-and-add chain run as one hoisted lazy
+    // sum with an addend (plan_exec.hip section 1a; plan_flatten.hpp names the groups).  Changes the rounding: off by default.
+    int ks_flatten = 0;
+    std::vector<FlattenGroup> flatten_groups(bool every_key) const; // the loaded program's groups under the key set held (every_key: as if every offset had a key)
     // option zenc_head = 1: the zero-encryptions at the start of a plan's run() transform only u (plan_zero_encrypt).  Every limb equals
     // zenc_head = 0's.  zenc_chunk_hook (hooks build, test_hooks.hip: HEVM_TEST_ZENC_CHUNK): items per chunk of that head instead of kZencChunk, 0 = unset
     bool zenc_head = true;
@@ -339,6 +352,7 @@ class HEVM {
     int64_t n_hops = 0, n_decomp = 0; // hevm_last_run_hoist_stats
     int64_t n_fold = 0;               // hevm_last_run_fold_rescale_stats
     int64_t n_relin_groups = 0, n_relin_products = 0; // hevm_last_run_relin_stats
+    int64_t n_flat_groups = 0, n_flat_members = 0, n_flat_hops = 0; // hevm_last_run_flatten_stats
     double t_bootstrap = 0.0; // host wall time spent inside opcode 10
 
     VmAllocs allocs;   // device memory held by this VM (hevm_destroy)

@@ -130,7 +130,12 @@ static void f_ks_gmac(const Context &c, const u64 *L, const KsItem *items, u64 *
 // na for a member's; wave-uniform) and the pair is folded to canonical words -- which then count as one product -- before a 17th would join:
 // 63 members x l digits pass through one pair.  Every stored limb is canonical and modular sums are exact in any order, so the result does not
 // depend on where the folds fall.  The finish is f_ks_gmac_kernel's.
-template <int K, int LOGE, bool MERGE>
+// ADDEND (dc_ct_rotate_sum_hoisted_add; option ks_flatten_sums): groups[g].src is a ciphertext at the group's level that is added to the sum
+// exactly (p == nullptr: this group has none) -- one more product P . addend_p on accumulator p of every data prime, counted like any other,
+// and nothing on the special prime: a multiple of P changes neither the rounding term nor the quotient's remainder, so every limb is
+// Oracle.add(addend, the sum without it).  The addend is read where it lies (no permutation), before any member; only the last launch of
+// the sequence writes a destination, so it may be a source or the destination.  A flag, so that the forms without it compile as before.
+template <int K, int LOGE, bool MERGE, bool ADDEND = false>
 __global__ __launch_bounds__(kTileThreads) void f_ks_gsum_kernel(const u64 *__restrict__ L, const KsItem *__restrict__ items,
                                                                   const KsItem *__restrict__ groups, u64 *__restrict__ acc, int ell, int Kp,
                                                                   const DModulus *__restrict__ mods, const u64 *__restrict__ itw, int logN,
@@ -155,6 +160,17 @@ __global__ __launch_bounds__(kTileThreads) void f_ks_gsum_kernel(const u64 *__re
 #pragma unroll
     for (int e = 0; e < E; e++) s0[e].clear(), s1[e].clear();
     int ns = 0;
+    if constexpr (ADDEND) {
+        if (m < ell && gr.src.p) {
+            const u64 *d0 = gr.src.limb(0, m, N) + g0, *d1 = gr.src.limb(1, m, N) + g0;
+            room(s0, s1, ns);
+#pragma unroll
+            for (int h = 0; h < E / 2; h++) {
+                const u64x2 v0 = *reinterpret_cast<const u64x2 *>(d0 + 2 * h), v1 = *reinterpret_cast<const u64x2 *>(d1 + 2 * h);
+                s0[2 * h].mac(v0.x, P), s0[2 * h + 1].mac(v0.y, P), s1[2 * h].mac(v1.x, P), s1[2 * h + 1].mac(v1.y, P);
+            }
+        }
+    }
     for (int k = 0; k < cnt; k++) {
         const KsItem it = mem[k];
         u32 gi[E / 2];
@@ -233,13 +249,17 @@ __global__ __launch_bounds__(kTileThreads) void f_ks_gsum_kernel(const u64 *__re
     }
 }
 
-// geometry and merging chosen as f_ks_gmac chooses them, with groups in the place of hops
-static void f_ks_gsum(const Context &c, const u64 *L, const KsItem *items, const KsItem *groups, u64 *acc, int G, int ell, hipStream_t s)
+// geometry and merging chosen as f_ks_gmac chooses them, with groups in the place of hops; addend: the groups' src fields are addends (or null)
+static void f_ks_gsum(const Context &c, const u64 *L, const KsItem *items, const KsItem *groups, u64 *acc, int G, int ell, bool addend, hipStream_t s)
 {
     const KsMacShape sh = ks_mac_shape(c, ell, G);
     ks_mac_dispatch(c.k2, sh, [&](auto k, auto le, auto merge) {
-        DC_LAUNCH((f_ks_gsum_kernel<decltype(k)::value, decltype(le)::value, decltype(merge)::value>), sh.grid, dim3(kTileThreads), 0, s, L, items,
-                  groups, acc, ell, c.K, c.d_mods, c.d_itw, c.logN, c.d_pmod, sh.items_fast);
+        if (addend)
+            DC_LAUNCH((f_ks_gsum_kernel<decltype(k)::value, decltype(le)::value, decltype(merge)::value, true>), sh.grid, dim3(kTileThreads), 0, s, L,
+                      items, groups, acc, ell, c.K, c.d_mods, c.d_itw, c.logN, c.d_pmod, sh.items_fast);
+        else
+            DC_LAUNCH((f_ks_gsum_kernel<decltype(k)::value, decltype(le)::value, decltype(merge)::value>), sh.grid, dim3(kTileThreads), 0, s, L, items,
+                      groups, acc, ell, c.K, c.d_mods, c.d_itw, c.logN, c.d_pmod, sh.items_fast);
     });
 }
 
@@ -302,12 +322,14 @@ void hoist_rotate_hops(Context &c, const BatchWs &w, const KsItem *d_items, cons
 // member count } (a group's members are adjacent; their own dst is unused), d_items[b].slot / d_sources as above, d_items[b].plain / plain_sp the
 // plaintext multiplying member b in the raised basis, or null.  Scratch: w.digits / w.ext as above, w.acc [G][2][l+1][N], w.tmp [G][2][l][N]
 // -- U, G <= B.  A destination may be one of the sources: only the last launch writes, and it reads no source.
+// addend: d_groups[g].src is a ciphertext added to sum g exactly (src.p == nullptr: none), read by the inner-product launch alone -- it may be
+// a source or a destination of the batch; false: the field is not read.
 void hoist_rotate_sum(Context &c, const BatchWs &w, const KsItem *d_items, const KsItem *d_sources, int B, int U, const KsItem *d_groups, int G,
-                      int ell, hipStream_t s)
+                      int ell, hipStream_t s, bool addend)
 {
     hoist_check(c, "hoist_rotate_sum", B, U, G, ell);
     hoist_decompose(c, w, d_sources, U, ell, s);
-    f_ks_gsum(c, w.ext, d_items, d_groups, w.acc, G, ell, s);
+    f_ks_gsum(c, w.ext, d_items, d_groups, w.acc, G, ell, addend, s);
     hoist_moddown(c, w, d_groups, G, ell, s);
 }
 

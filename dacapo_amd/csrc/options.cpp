@@ -42,6 +42,7 @@ static const OptDef kDefs[OPT_COUNT] = {
     { "ks_lazy_sum", 0 },
     { "ks_fold_rescale", 0 },
     { "ks_lazy_relin", 0 },
+    { "ks_flatten_sums", 0 },
     { "zenc_head", 1 },
     { "seal_compr", 0 },
     { "trace", 0 },

@@ -147,9 +147,11 @@ void b_mul_sum_relin(Context &c, const BatchWs &w, const MulSumItem *d_items, co
 void hoist_rotate_hops(Context &c, const BatchWs &w, const KsItem *d_items, const KsItem *d_sources, int B, int U, int ell, hipStream_t s);
 // lazy sums on the same decompositions (option ks_lazy_sum, dc_ct_rotate_sum_hoisted): G sums of B members, ONE division by P per sum (oracle
 // orc_rotate_acc_hybrid per member, Oracle.lazy_mul_plain / lazy_add, one orc_moddown_hybrid per group).  d_groups[g] as for hyb_rotate_sum:
-// dst, elt = first member, slot = member count; a member's plain / plain_sp ([level][N] / [1][N]) multiply it in the raised basis, or null
+// dst, elt = first member, slot = member count; a member's plain / plain_sp ([level][N] / [1][N]) multiply it in the raised basis, or null.
+// addend (dc_ct_rotate_sum_hoisted_add, option ks_flatten_sums): d_groups[g].src is a ciphertext at level ell added to sum g exactly, with no
+// launch of its own (src.p == nullptr: that group has none); it may be a source or a destination of the batch
 void hoist_rotate_sum(Context &c, const BatchWs &w, const KsItem *d_items, const KsItem *d_sources, int B, int U, const KsItem *d_groups, int G,
-                      int ell, hipStream_t s);
+                      int ell, hipStream_t s, bool addend = false);
 bool chain_fusion_supported(); // the continuation kernels exist for the default launch sequences only
 // grouped-digit hybrid key switching (hybrid_ks.hip; Context::hybrid()): b_rotate_hops / b_mul_relin / keyswitch route here
 void hyb_rotate_hops(Context &c, const BatchWs &w, const KsItem *d_items, int B, int ell, hipStream_t s, int unique = 0);

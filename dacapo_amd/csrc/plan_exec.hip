@@ -13,6 +13,7 @@
 #include <tuple>
 
 #include "hevm_vm.hpp"
+#include "plan_flatten.hpp"
 #include "plan_levels.hpp"
 #include "plan_relin.hpp"
 
@@ -209,6 +210,7 @@ void HEVM::build_plan()
             const double in_scale = P.vals[(size_t)v].scale; // (rotate_vector keeps the scale: every hop's result carries the operand's)
             bool memo_final = false;
             const std::vector<u32> hops = rotate_hops((int16_t)op.rhs);
+            const int inst_src = v, first_hop = (int)P.pops.size(); // (option ks_flatten_sums: what the instruction rotates, where its hops start)
             for (const u32 &elt : hops) {
                 // option rot_compose (a bounded key set): composed rotations of one value mostly start with the same small offset -- the parts
                 // come in ascending order -- so the hop (value, Galois element) is computed once and its result named again: the same limbs
@@ -224,6 +226,7 @@ void HEVM::build_plan()
                 }
                 Pop &p = add_hop(v, in_scale, elt);
                 p.op = (int)(&op - ops.data()), p.direct = &elt == &hops.back(); // (the LAST hop of the instruction: the one whose result the program sees)
+                p.inst_src = inst_src, p.first_hop = first_hop;
                 if (rot_compose) hop_memo[{ memo_key(v), elt }] = p.dst;
                 v = p.dst;
             }
@@ -384,6 +387,63 @@ void HEVM::build_plan()
         return (sv.root == v && sv.def_pop >= 0 && !O[(size_t)sv.def_pop].dead && O[(size_t)sv.def_pop].dst == v) ? sv.def_pop : -1;
     };
 
+    // ---- 1a. flattened rotate-and-add chains (option ks_flatten_sums; SEAL-layout keys, with ks_hoist and ks_lazy_sum) ----------------------
+    // A stage of h hops y' = y + rotate(y, o) is ONE hoisted lazy sum with an addend: y + sum over the 2^h - 1 subset sums of rotate(y, .),
+    // one decomposition and one division by P where the program runs h dependent key switches (plan_flatten.hpp finds the stages on the
+    // loaded instructions, flatten_groups; a stage whose composite offsets lack a key stays as written).  A group becomes ONE pop where the
+    // stage's closing addcc stood: it defines that instruction's value, whose level and scale the walk above computed as the default run does;
+    // the stage's other pops -- every hop of its rotations, its other adds -- go away and their values are never materialised.  Groups are
+    // closed: a P_ROTSUM is no term of section 2's n-ary sums and no member of section 2b's groups.  A different rounding than the program's
+    // hops (one mod-down instead of h): off by default, and the groups are exported (hevm_plan_flatten_groups) for the oracle's replay.
+    if (ks_flatten && !c.hybrid()) {
+        std::map<int, int> rot_pop, sum_pop; // instruction -> the pop of its last hop / of its addcc
+        for (size_t i = 0; i < O.size(); i++) {
+            if (O[i].kind == P_ROT && O[i].direct && O[i].op >= 0) rot_pop[O[i].op] = (int)i;
+            if (O[i].kind == P_SUM && O[i].op >= 0) sum_pop[O[i].op] = (int)i;
+        }
+        const int slots = (int)(N >> 1);
+        for (const FlattenGroup &g : flatten_groups(false)) {
+            const size_t h = g.rot_ops.size();
+            std::vector<int> rp(h), ap(h);
+            for (size_t k = 0; k < h; k++) {
+                const auto r = rot_pop.find(g.rot_ops[k]), a = sum_pop.find(g.add_ops[k]);
+                if (r == rot_pop.end() || a == sum_pop.end()) {
+                    fprintf(stderr, "[dacapo_amd] plan: hop %d / %d of a flattened stage has no pseudo-op (internal error)\n", g.rot_ops[k], g.add_ops[k]);
+                    abort();
+                }
+                rp[k] = r->second, ap[k] = a->second;
+            }
+            const int source = O[(size_t)rp[0]].inst_src;
+            const Pop &first_add = O[(size_t)ap[0]];
+            if (first_add.srcs.size() != 2 || (first_add.srcs[0] != source && first_add.srcs[1] != source)) {
+                fprintf(stderr, "[dacapo_amd] plan: the flattened stage closing at instruction %d does not start from one value (internal error)\n", g.closing_op);
+                abort();
+            }
+            Pop grp;
+            grp.kind = P_ROTSUM, grp.level = O[(size_t)ap[h - 1]].level, grp.dst = O[(size_t)ap[h - 1]].dst, grp.op = g.closing_op, grp.addend = source;
+            for (size_t k = 0; k < h; k++) grp.flat_ops.push_back(g.rot_ops[k]), grp.flat_ops.push_back(g.add_ops[k]);
+            grp.flat_offsets = g.offsets;
+            for (int o : g.offsets) {
+                u64 e = (u64)(o < 0 ? slots + o : o), elt = 1, g3 = 3;
+                for (; e; e >>= 1, g3 = (g3 * g3) & (2 * N - 1))
+                    if (e & 1) elt = (elt * g3) & (2 * N - 1);
+                grp.srcs.push_back(source), grp.elts.push_back((u32)elt), grp.keys.push_back(keys.galois.at((u32)elt)), grp.plains.push_back(-1);
+            }
+            auto drop = [&](int pi) { // (no pop defines or reads this value any more)
+                O[(size_t)pi].dead = true;
+                V[(size_t)O[(size_t)pi].dst].uses = 0, V[(size_t)O[(size_t)pi].dst].def_pop = -1;
+                if (O[(size_t)pi].kind == P_ROT) P.n_keyswitch--, P.n_ntt -= ks_ntts(O[(size_t)pi].level);
+            };
+            for (size_t k = 0; k < h; k++) {
+                for (int pi = O[(size_t)rp[k]].first_hop; pi <= rp[k]; pi++) drop(pi);
+                if (k + 1 < h) drop(ap[k]);
+            }
+            V[(size_t)source].uses -= 1; // (the first hop's rotation and addcc read it; now the group does)
+            O[(size_t)ap[h - 1]] = grp;
+            P.n_keyswitch++, P.n_ntt += ks_ntts(grp.level); // one decomposition, one inner-product launch, one mod-down
+        }
+    }
+
     // ---- 1b. lazy relinearisation (option ks_lazy_relin; SEAL-layout keys) ---------------------------------------------------------
     // relin(sum_k s_k a_k (x) b_k) is ONE key switch of the summed three-part ciphertext (plan.hpp b_mul_sum_relin) where the program's mulcc
     // instructions run one each.  plan_relin.hpp finds the groups -- maximal trees of addcc / negate over mulcc results that nothing else reads,
@@ -433,7 +493,7 @@ void HEVM::build_plan()
 
     // ---- 2. fold ct+ct chains into n-ary sums (only through intermediates nothing else observes) ------------------
     for (Pop &p : O) {
-        if (p.kind != P_SUM) continue;
+        if (p.kind != P_SUM || p.dead) continue; // (a dropped add -- an interior node of section 1a / 1b -- folds nothing: its operand may be live)
         std::vector<int> flat;
         for (int s : p.srcs) {
             const int dp = own_pop(s);
@@ -925,7 +985,10 @@ void HEVM::build_plan()
                 for (int q = 0; q < S; q++) {
                     const Pop &rp = O[(size_t)pi];
                     const CtView dst = plan_view(rp.dst, q);
-                    groups.push_back(KsItem{ dst, dst, nullptr, (u32)(h_ks.size() - (size_t)st.first), (u32)rp.srcs.size() });
+                    // (option ks_flatten_sums: the group's src is its addend, null without one -- read only by a step that has addends)
+                    const CtView add = rp.addend >= 0 ? plan_view(rp.addend, q) : c.hybrid() ? dst : CtView{ nullptr, 0 };
+                    if (rp.addend >= 0) st.addend = true, P.n_flat_groups++, P.n_flat_members += (int64_t)rp.srcs.size(), P.n_flat_hops += (int64_t)rp.flat_ops.size() / 2;
+                    groups.push_back(KsItem{ add, dst, nullptr, (u32)(h_ks.size() - (size_t)st.first), (u32)rp.srcs.size() });
                     // (option ks_lazy_sum: group-major, then by source -- a group's members that read one decomposition are adjacent)
                     std::vector<size_t> order(rp.srcs.size());
                     for (size_t k = 0; k < order.size(); k++) order[k] = k;
@@ -1410,7 +1473,8 @@ void HEVM::issue_step(const Step &st, hipStream_t q)
         b_rotate_hops(st.target < 0 ? *bctx : c, w, P.d_ks + st.first, st.count, st.level, q, st.h, st.unique); break;
     case P_ROTSUM:
         if (!c.hybrid()) { // option ks_lazy_sum: st.gcount sums of st.count members over st.unique decompositions
-            hoist_rotate_sum(c, w, P.d_ks + st.first, P.d_ks + st.gfirst + st.gcount, st.count, st.unique, P.d_ks + st.gfirst, st.gcount, st.level, q);
+            hoist_rotate_sum(c, w, P.d_ks + st.first, P.d_ks + st.gfirst + st.gcount, st.count, st.unique, P.d_ks + st.gfirst, st.gcount, st.level, q,
+                             st.addend);
             break;
         }
         hyb_rotate_sum(c, w, P.d_ks + st.first, st.count, P.d_ks + st.gfirst, st.gcount, st.level, q, st.unique); break;
@@ -1669,6 +1733,7 @@ void HEVM::run_plan()
     n_keyswitch = P.n_keyswitch, n_ntt = P.n_ntt;
     n_hops = P.n_hops, n_decomp = P.n_decomp, n_fold = P.n_fold;
     n_relin_groups = P.n_relin_groups, n_relin_products = P.n_relin_products;
+    n_flat_groups = P.n_flat_groups, n_flat_members = P.n_flat_members, n_flat_hops = P.n_flat_hops;
     t_bootstrap = 0.0;
     const long ps = (long)c.K * (long)c.N;
     if (plan_graph) { // the plan is a fixed launch sequence: recorded once (normally by preprocess()), replayed as one graph launch

@@ -83,6 +83,7 @@ def _bind(path):
         L.dc_ct_rotate_hop.argtypes = [vp, u64p, lng, u64p, lng, C.c_uint32, u64p, i32, vp]
         L.dc_ct_rotate_hoisted.argtypes = [vp, vp, lng, u64p, lng, vp, vp, i32, i32, vp]
         L.dc_ct_rotate_sum_hoisted.argtypes = [vp, u64p, lng, vp, lng, vp, vp, vp, vp, i32, i32, vp]
+        L.dc_ct_rotate_sum_hoisted_add.argtypes = [vp, u64p, lng, u64p, lng, vp, lng, vp, vp, vp, vp, i32, i32, vp]
         L.dc_ct_rescale.argtypes = [vp, u64p, lng, u64p, lng, i32, vp]
         L.dc_ct_modswitch.argtypes = [vp, u64p, lng, u64p, lng, i32, i32, vp]
         L.dc_keyswitch.argtypes = [vp, u64p, lng, u64p, u64p, u64p, u64p, i32, vp]
@@ -189,6 +190,17 @@ class Context:
         pa, pb = (C.c_void_p * n)(*a_ptrs), (C.c_void_p * n)(*b_ptrs)
         sg = (C.c_int32 * n)(*[int(s) for s in signs])
         self.L.dc_ct_mul_sum_relin(self.h, dst, dst_stride, pa, pb, sg, n, src_stride, relin_key, ell, stream)
+
+    def rotate_sum_add(self, dst: int, dst_stride: int, addend, addend_stride: int, src_ptrs, src_stride: int, elts, key_ptrs, ell: int,
+                       plains=None, plains_sp=None, stream=None):
+        """dc_ct_rotate_sum_hoisted_add: dst = addend + sum_k [plains[k] .] galois_{elts[k]}(srcs[k]) with one division by P; every pointer is
+        a device pointer (int), addend may be None, a source or dst; plains / plains_sp: per member a pointer or None, or None altogether"""
+        n = len(elts)
+        assert len(src_ptrs) == n and len(key_ptrs) == n
+        ps, pk, ge = (C.c_void_p * n)(*src_ptrs), (C.c_void_p * n)(*key_ptrs), (C.c_uint32 * n)(*[int(e) for e in elts])
+        pl = (C.c_void_p * n)(*plains) if plains is not None else None
+        sp = (C.c_void_p * n)(*plains_sp) if plains_sp is not None else None
+        self.L.dc_ct_rotate_sum_hoisted_add(self.h, dst, dst_stride, addend, addend_stride, ps, src_stride, ge, pk, pl, sp, n, ell, stream)
 
     def elt_from_step(self, step: int) -> int:
         return int(self.L.dc_galois_elt_from_step(self.h, step))

@@ -107,6 +107,12 @@ def bind_vm_lib(path):
     L.hevm_plan_relin_groups.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32), ctypes.c_int64]
     L.hevm_plan_relin_groups.restype = ctypes.c_int64
     L.hevm_last_run_relin_stats.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
+    L.hevm_flatten_offsets.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_int]
+    L.hevm_flatten_offsets.restype = ctypes.c_int
+    L.hevm_plan_flatten_groups.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32), ctypes.c_int64]
+    L.hevm_plan_flatten_groups.restype = ctypes.c_int64
+    L.hevm_last_run_flatten_stats.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_int64)] * 3
+    L.hevm_last_run_flatten_stats.restype = None
     L.hevm_set_streams.argtypes = [ctypes.c_void_p, ctypes.c_int]
     L.hevm_select_stream.argtypes = [ctypes.c_void_p, ctypes.c_int]
     # all streams' inputs / results at once; the value pointers are host or device addresses (last argument: 0 / 1)
@@ -490,6 +496,40 @@ class HEVM:
         g, p = ctypes.c_int64(), ctypes.c_int64()
         self.lw.hevm_last_run_relin_stats(self.vm, ctypes.byref(g), ctypes.byref(p))
         return {"groups": g.value, "products": p.value}
+
+    def flatten_offsets(self):
+        """option ks_flatten_sums, after load(): the composite slot offsets the program's flattened stages would use and that have no key
+        yet (hevm_flatten_offsets), ascending -- what addRotationKeys takes"""
+        n = self.lw.hevm_flatten_offsets(self.vm, None, 0)
+        if n <= 0:
+            return []
+        buf = (ctypes.c_int64 * n)()
+        self.lw.hevm_flatten_offsets(self.vm, buf, n)
+        return [int(x) for x in buf]
+
+    def flatten_groups(self):
+        """option ks_flatten_sums: the stages of rotate-and-add chains the plan runs as one hoisted lazy sum each (hevm_plan_flatten_groups)
+        as [(closing_op, [(rot_op, add_op), ...], [member offset, ...]), ...]; the raw return value (0 / -1) when there is no list"""
+        n = self.lw.hevm_plan_flatten_groups(self.vm, None, 0)
+        if n <= 0:
+            return int(n)
+        buf = (ctypes.c_int32 * n)()
+        self.lw.hevm_plan_flatten_groups(self.vm, buf, n)
+        out, i = [], 0
+        while i < n:
+            h, closing = buf[i], buf[i + 1]
+            hops = [(buf[i + 2 + 2 * j], buf[i + 3 + 2 * j]) for j in range(h)]
+            i += 2 + 2 * h
+            m = buf[i]
+            out.append((closing, hops, list(buf[i + 1 : i + 1 + m])))
+            i += 1 + m
+        return out
+
+    def flatten_stats(self):
+        """option ks_flatten_sums: flattened stages, the rotations in them and the hops they absorbed in the last run() (once per stream)"""
+        g, m, h = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        self.lw.hevm_last_run_flatten_stats(self.vm, ctypes.byref(g), ctypes.byref(m), ctypes.byref(h))
+        return {"groups": g.value, "members": m.value, "hops_absorbed": h.value}
 
     def fold_rescale_stats(self):
         """option ks_fold_rescale: items (multiply-rescale pairs, once per stream) the last run() executed as one merged step"""

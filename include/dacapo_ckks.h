@@ -147,6 +147,15 @@ void dc_ct_rotate_hoisted(dc_context *ctx, uint64_t *const *dsts, long dst_strid
 void dc_ct_rotate_sum_hoisted(dc_context *ctx, uint64_t *dst, long dst_stride, const uint64_t *const *srcs, long src_stride,
                               const uint32_t *galois_elts, const uint64_t *const *galois_keys, const uint64_t *const *plains,
                               const uint64_t *const *plains_sp, int count, int ell, void *stream);
+/* EXTENSION: dc_ct_rotate_sum_hoisted plus one addend -- dst = addend + sum_k [plains[k] .] galois_k(srcs[k]), the addend (a ciphertext of ell
+ * limbs, NTT form) added EXACTLY and with no launch of its own: it enters the raised accumulators of the data primes as P . addend, which the
+ * one division by P returns unchanged, so every limb equals Oracle.add(addend, the sum without it).  addend may be one of the sources, may be
+ * dst, or NULL (then the call is dc_ct_rotate_sum_hoisted).  Everything else as there.  y + rot(y, a) + rot(y, b) + rot(y, a + b) -- two hops
+ * of a rotate-and-add chain -- is one such call with three members (option ks_flatten_sums). */
+void dc_ct_rotate_sum_hoisted_add(dc_context *ctx, uint64_t *dst, long dst_stride, const uint64_t *addend, long addend_stride,
+                                  const uint64_t *const *srcs, long src_stride, const uint32_t *galois_elts,
+                                  const uint64_t *const *galois_keys, const uint64_t *const *plains, const uint64_t *const *plains_sp,
+                                  int count, int ell, void *stream);
 /* Evaluator::rescale_to_next: level ell -> ell-1   SEAL_HEVM.cpp:283 */
 void dc_ct_rescale(dc_context *ctx, uint64_t *dst, long dst_stride, const uint64_t *src, long src_stride, int ell,
                    void *stream);

@@ -149,6 +149,23 @@ int64_t hevm_plan_lazy_groups(void *vm, int32_t *out, int64_t cap);
 int64_t hevm_plan_relin_groups(void *vm, int32_t *out, int64_t cap);
 /* ... and the counts of the last run(): groups and the products in them, once per stream (0 with the option off or under plan = 0) */
 void hevm_last_run_relin_stats(void *vm, int64_t *groups, int64_t *products);
+/* option "ks_flatten_sums" = f (SEAL-layout keys, with "ks_hoist" = 1 and "ks_lazy_sum" >= 1; 0 = off, the default; 2 .. 6 = the most hops one
+ * stage absorbs): a chain y' = y + rotate(y, o) -- the log-step slot sums of a model -- runs stage by stage as ONE hoisted lazy sum with an
+ * addend, y + sum over the 2^h - 1 subset sums of a stage's offsets of rotate(y, .): one decomposition and one division by P where the
+ * program runs h dependent key switches (not the program's rounding).  A stage runs as written when a subset sum is
+ * 0 modulo the slot count or a member's offset has no Galois key: the VM never generates a key on its own.
+ * hevm_flatten_offsets: after load(), the distinct composite slot offsets the loaded program's stages would use at the VM's option value
+ * and that have no key yet, ascending -- writes up to cap of them and returns how many there are; a caller that holds the secret key hands
+ * them to hevm_add_rotation_keys (a server's key directory is written after that call).  0 with the option off or under plan = 0.
+ * hevm_plan_flatten_groups: the stages the last run()'s plan flattened, out = [hops, closing_op, (rot_op, add_op) x hops, members,
+ * offset x members, ...]: per group the instruction indices of its closing addcc and of its hops in chain order, and its members' signed slot
+ * offsets (member k - 1 <-> the hops whose bits are set in k, k = 1 .. 2^hops - 1); the group's source, which is also its addend, is the
+ * value the first hop rotates.  Returns as hevm_plan_lazy_groups does, which does not list these groups.
+ * hevm_last_run_flatten_stats: groups, the rotations in them and the hops they absorbed in the last run(), once per stream (0 with the
+ * option off or under plan = 0).  hevm_last_run_stats counts a flattened stage as ONE key switch with one key switch's transforms. */
+int hevm_flatten_offsets(void *vm, int64_t *out, int cap);
+int64_t hevm_plan_flatten_groups(void *vm, int32_t *out, int64_t cap);
+void hevm_last_run_flatten_stats(void *vm, int64_t *groups, int64_t *members, int64_t *hops_absorbed);
 /* Throughput mode: run `n` independent ciphertext streams of the same program side by side (shared keys and
  * plaintexts; every step of the batched plan processes all streams in one launch sequence).  Call before load();
  * encrypt / decrypt / decrypt_result / getCtxt then address the stream chosen with hevm_select_stream. */
@@ -196,7 +213,7 @@ void hevm_load_ctxt(void *vm, int64_t reg, const char *path);
 
 /* Run-time options (dacapo_amd/csrc/options.hpp holds the ONE table: names, defaults, meaning).  VM options -- "logn", "primes",
  * "prime_bits", "ks_special", "ks_alpha", "secret_hw", "rot_compose", "plan", "plan_graph", "plan_lanes", "max_batch", "chain_fusion", "host_encoder",
- * "online_encode", "fold_rescale_boot", "ks_lazy_relin", "zenc_head", "hyb_mfma", "hyb_fuse", "seal_compr", "trace", "step_profile" -- are read when a VM (or kernel-level
+ * "online_encode", "fold_rescale_boot", "ks_lazy_relin", "ks_flatten_sums", "zenc_head", "hyb_mfma", "hyb_fuse", "seal_compr", "trace", "step_profile" -- are read when a VM (or kernel-level
  * context) is created; launch-shape thresholds -- "small_tile_wgs", "tiny_tile_wgs", "ntt_full_min_limbs", ... -- at every launch.
  * Process-wide, not thread-safe (like the rest of this ABI).  An unknown name aborts with the list of names.  A caller that only knows
  * the reference's 18 symbols sets the same names through the single environment variable DACAPO_HEVM_OPTIONS="name=value,...". */

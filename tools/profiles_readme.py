@@ -240,6 +240,7 @@ rows.append("| `fused_tail_share.txt` | compile-time figures, not runs: every ke
 rows.append(f"| `plan_levels_ab.txt` | slack-aware levelling of the plan and the addend hoisted out of a rescale's folded sum (option `plan_level`): the headline plan under 0 (ASAP), 1 and 2 (the hoist alone) from the trace — steps by kind, waves, waves with more than one step, links, launches, live buffers, pool — then `run()` on three VMs with the option 0, 1, 0 in one process: {first_lines('plan_levels_ab.txt', 'run headline 1 - 0', 1)}; the parent commit's library with `plan_lanes` 1 and 2; `bench.py` on the parent's library and on this one: {first_lines('plan_levels_ab.txt', 'ms_per_step [0-9.]+  value', 3)}; kernel-trace runs of both: {first_lines('plan_levels_ab.txt', 'last run.. ', 2)}; the decision | `python tools/legs/plan_levels_ab.py --out profiles/plan_levels_ab.txt`; `python tools/legs/plan_levels_ab.py --lanes`; `python bench.py --gpus 1 --steps 10 --warmup 3`; `rocprofv3 --kernel-trace --stats -- python3 tools/legs/headline_only.py 3 [--opt plan_level=1]`, `tools/summarize/timeline_gaps.py` |")
 rows.append(f"| `plan_builder_refactor.txt` | the plan builder's refactor (one owner for a plan's device memory, each rule once, four leaf blocks out of `build_plan`), parent commit against branch: the plan traces of the headline program and of a convolution-shaped program under ten option sets, byte for byte: {first_lines('plan_builder_refactor.txt', '^every plan|DIFFERENCES', 1)}; every kernel's listing, both builds: {first_lines('plan_builder_refactor.txt', 'kernels in 30 listings', 1)}; `bench.py` with the parent's library and the branch's alternating on one box: {first_lines('plan_builder_refactor.txt', '^parent mean', 1)}; load and first `run()` times; test counts; line counts | `python tools/legs/plan_identity.py PARENT_LIB BRANCH_LIB --out …`; `python tools/experiments/asm_compare.py PARENT_DIR BRANCH_DIR`; `DACAPO_AMD_LIB=… python bench.py --gpus 1 --steps 40 --warmup 5 --no-cpu-baseline` |")
 rows.append(f"| `io_batch_ab.txt` | all streams' inputs and results at once (`hevm_encrypt_batch`, `hevm_decrypt_result_batch`) against the sequential calls, 8 streams of the headline fixture at N = 2^15 / 14 primes, one process, forms alternating, from host and from device memory, with `hevm_last_io_stats`: {first_lines('io_batch_ab.txt', 'one setInputs, host', 1)} | `python tools/legs/io_batch_ab.py --out profiles/io_batch_ab.txt` |")
+rows.append("| `ks_flatten_ab.txt` | flattened rotate-and-add chains (option `ks_flatten_sums`, `dc_ct_rotate_sum_hoisted_add`): `run()` of the headline on alternating VMs, option off / on / off with `ks_hoist` = 1 and `ks_lazy_sum` = 2 in every arm, f = 2, 3, 4, 6 at 1 and 8 streams, a default-options VM beside them: ms per run with the off/off spread, the plan's report (pseudo-ops, steps, waves, launches), key switches, groups / members / hops absorbed, composite keys added and their HBM, rms against the torch logits; the benchmark line of the parent commit's tree and library on the same box; a kernel trace of one VM at the best f and of one with the option off (`f_ks_gsum_kernel` against the hop kernels it replaced) | `python tools/legs/ks_flatten_ab.py --out profiles/ks_flatten_ab.txt`; `rocprofv3 --kernel-trace --stats -- python tools/legs/ks_flatten_ab.py --trace-f F` |")
 print("\n".join(r for r in rows if r))
 print()
 print("## Round 5 (everything `r05_*`; one `gpurun` call of `tools/collect_profiles.sh r05` on the committed build -- the JSON files that `bench.py` reads carry "
