@@ -22,6 +22,9 @@ already executes, plus four extension opcodes (hevm_asm.OP_ENCODE_COMPLEX / OP_C
 With sse=True the main secret may be dense (SEAL's uniform ternary) or of moderate weight: only ModRaise runs under s', so I stays as narrow as
 s' makes it, and `KEYSWITCH 1` right after ModRaise brings the raised ciphertext back to s for the rest.
 
+With real_msg=True (the half form; BootstrapEmitter) only the first of CoeffToSlot's two ciphertexts is computed: a message with real slots
+has p_(N-j) = -p_j, so EvalMod runs once, SlotToCoeff applies A0 to y_lo with coefficient 0 halved, and z' + conj(z') restores the rest.
+
 Levels: 3 + 1 (CoeffToSlot) + 5 + r (EvalMod) + 3 (SlotToCoeff): `boot_levels`.  `simulate` interprets a program (all opcodes, the four extensions
 included) on cleartext slot vectors with the exact scale semantics of the VM -- the reference semantics of the extension opcodes and
 the CPU check of the whole construction (tests/test_ckks_boot.py).
@@ -186,12 +189,21 @@ class Ct:
 
 
 class BootstrapEmitter:
-    """Emits the bootstrap of one ciphertext into `b`.  Plaintext registers of the matrices are shared by all bootstraps of a program."""
+    """Emits the bootstrap of one ciphertext into `b`.  Plaintext registers of the matrices are shared by all bootstraps of a program.
+
+    real_msg=True emits the HALF form, defined for REAL messages only (every slot real: what `encrypt` takes and opcodes 1-10 keep).  A
+    polynomial p with real slots is invariant under X -> X^-1, so p_(N-j) = -p_j and p_(N/2) = 0: CoeffToSlot, EvalMod and SlotToCoeff
+    run on coefficients 0 .. N/2-1 alone (one chain instead of two), and the upper half comes back from the conjugation that ends
+    SlotToCoeff.  On a message with complex slots the half form returns the message whose polynomial agrees with the input's on the
+    first N/2 coefficients -- not the input (lower_bootstraps refuses such programs)."""
 
     def __init__(self, b: ha.Builder, logN: int, num_primes: int, target_level: int, r: int = 5, taylor_terms: int = 16, k_range: float = 16.0,
                  msg_bits: int = 0, diag_bits: int | None = None, out_bits: int = 40, groups: int = 3, cts_bits: int = 60, ks: int = 1, primes=None,
-                 sse: bool = False):
+                 sse: bool = False, real_msg: bool = False):
         """sse: sparse-secret encapsulation -- ModRaise is wrapped in KEYSWITCH 0 / KEYSWITCH 1 (the VM needs option boot_secret_hw).
+        real_msg: the half form (class docstring).  Same levels, kappa, label and input scale as the full form; the one matrix it changes
+        (SlotToCoeff's first, with the weight 1/2 on slot 0) has a plaintext cache key of its own ("stc0r"; "stcLr" when groups == 1), and
+        every other matrix is the full form's under the full form's key, so one program may hold bootstraps of both forms.
         primes: the VM's chain when it is not CoeffModulus::Create(N, {60 x num_primes}) -- round 4: any chain of 45..60-bit primes, in
         particular a HEaaN-style mixed one (mixed_prime_chain).  Every scale below is tracked with the exact primes; the handful of places
         that used to say "60" now read the width of the prime they mean (self.qb)."""
@@ -200,7 +212,7 @@ class BootstrapEmitter:
         assert len(self.primes) == num_primes
         self.top = num_primes - ks  # ks special primes at the end of the chain (1 in SEAL's scheme; more with grouped-digit key switching)
         diag_bits = (self.qb(self.top) - 5) if diag_bits is None else diag_bits  # matrix / coefficient plaintexts: 55 bits next to 60-bit primes
-        self.target, self.r, self.terms, self.k_range, self.sse = target_level, r, taylor_terms, k_range, sse
+        self.target, self.r, self.terms, self.k_range, self.sse, self.real_msg = target_level, r, taylor_terms, k_range, sse, real_msg
         self.msg_bits, self.diag_bits, self.out_bits, self.groups, self.cts_bits = msg_bits, diag_bits, out_bits, groups, cts_bits
         assert taylor_terms in (8, 16), "the polynomial in theta^2 is evaluated as a complete binary tree"
         # round 3: one more level than round 2 -- CoeffToSlot now ends with two rescales (see `bootstrap`)
@@ -294,7 +306,9 @@ class BootstrapEmitter:
                     f = dft_factor(m, logN, herm=False)
                     g = f if g is None else f.after(g)
                 stc.append(g)
-            self._mats = {"cts": cts, "cts_hi_first": cts[0].times_diag_right(np.conj(Dp)), "stc": stc, "Dp": Dp}
+            self._mats = {"cts": cts, "stc": stc, "Dp": Dp}
+            if not self.real_msg:                               # the half form never transforms the upper coefficients
+                self._mats["cts_hi_first"] = cts[0].times_diag_right(np.conj(Dp))
         return self._mats
 
     def linear(self, x: Ct, mat: DiagMatrix, key: str, bits: int | None = None, baby_cache: dict | None = None, rescale: bool = True) -> Ct:
@@ -417,9 +431,11 @@ class BootstrapEmitter:
         ct = self._op(OP_MULCP, ct, self.top, ct.s * 2.0**boost, reg)
         # CoeffToSlot: lo = A0^H z, hi = A0^H conj(D) z.  boost and the plaintext scales are chosen so that (x - 1/4) / kp enters
         # EvalMod at a true scale of ~2^60 (every power of w then sits at ~2^60 too): 2^(boost + sum cbits) N q0 / (4 primes * kp) = 2^60
+        if self.real_msg:                                       # the half form: the `lo` chain alone (see _real_tail)
+            return self._real_tail(ct, cbits, q0, delta)
         shared: dict = {}                                       # both transforms rotate the same ciphertext by the same baby steps
         last = self.groups - 1
-        lo = self.linear(ct, M["cts"][0], "cts0", cbits[0], shared, rescale=last != 0)
+        lo =self.linear(ct, M["cts"][0], "cts0", cbits[0], shared, rescale=last != 0)
         hi = self.linear(ct, M["cts_hi_first"], "cts0h", cbits[0], shared, rescale=last != 0)
         for gi in range(1, self.groups):
             lo = self.linear(lo, M["cts"][gi], f"cts{gi}", cbits[gi], rescale=gi != last)
@@ -447,6 +463,41 @@ class BootstrapEmitter:
         zlo = self.linear(ylo, M["stcL"], "stcL", rescale=False)
         zhi = self.linear(yhi, M["stcLh"], "stcLh", rescale=False)
         z = self.rescale(self.rescale(self.add(zlo, zhi)))
+        assert z.level == self.target, (z.level, self.target)
+        label = 2.0**self.out_bits * (delta / delta_nom)
+        out = self.set_scale(z, label)
+        return out.v, label
+
+    def _real_tail(self, ct: Ct, cbits, q0: float, delta: float) -> tuple:
+        """CoeffToSlot .. SlotToCoeff of the half form (real_msg), from the boosted raised ciphertext on.  With
+        lo'(X) = t_0 / 2 + sum_{0 < j < N/2} t_j X^j:  lo'(X) + lo'(X^-1) = p(X) for every p invariant under X -> X^-1, since
+        X^-j = -X^(N-j) supplies p_(N-j) = -p_j and coefficient N/2 comes out 0.  The ciphertext-level conj IS that automorphism, so only
+        the `lo` chain runs: one EvalMod, one SlotToCoeff chain, and w + conj(w) at the end.  I (not symmetric) needs no upper half
+        either: it is removed coefficient by coefficient before anything is recombined."""
+        M, last = self.matrices(), self.groups - 1
+        lo = ct
+        for gi in range(self.groups):
+            lo = self.linear(lo, M["cts"][gi], f"cts{gi}", cbits[gi], rescale=gi != last)
+        v = self.add(lo, self.conj(lo))                          # 2 Re u = N t  (coefficients 0 .. N/2-1, bit-reversed)
+        v = self.rescale(self.rescale(v))
+        v = Ct(v.v, v.level, v.s * self.N * q0)
+        y = self.eval_sine(v)
+        half0 = np.ones(self.n)
+        half0[0] = 0.5                                           # coefficient 0 sits in slot brev(0) = 0; conj would count it twice
+        if "stc0r" not in M and self.groups > 1:
+            M["stc0r"] = M["stc"][0].times_diag_right(half0)
+        for gi in range(self.groups - 1):
+            y = self.linear(y, M["stc0r"] if gi == 0 else M["stc"][gi], "stc0r" if gi == 0 else f"stc{gi}")
+        q_last, q_fin = float(self.primes[y.level - 1]), float(self.primes[y.level - 2])
+        s_after = y.s * 2.0**self.diag_bits / (q_last * q_fin)
+        delta_nom = 2.0**self.boot_in_bits
+        kappa = 2.0**self.out_bits * q0 / (s_after * 2.0 * math.pi * delta_nom)   # as in the full form: the plaintexts are per program
+        if "stcL" not in M:
+            M["stcL"] = M["stc"][-1].scaled(kappa)
+        if self.groups == 1 and "stcLr" not in M:
+            M["stcLr"] = M["stcL"].times_diag_right(half0)
+        w = self.linear(y, M["stcLr"], "stcLr", rescale=False) if self.groups == 1 else self.linear(y, M["stcL"], "stcL", rescale=False)
+        z = self.rescale(self.rescale(self.add(w, self.conj(w))))
         assert z.level == self.target, (z.level, self.target)
         label = 2.0**self.out_bits * (delta / delta_nom)
         out = self.set_scale(z, label)
@@ -583,14 +634,15 @@ def simulate(hevm: bytes, cst: bytes, inputs, logN: int, primes, secret_weight: 
 
 
 # ---- a bootstrap on its own (tools/legs/boot_demo.py, bench.py, tests) ------------------------------------------------------------------
-def single_bootstrap_program(logN: int, target: int = 3, r: int = 5, msg_bits: int = 0, ks: int = 1, primes=None, sse: bool = False):
+def single_bootstrap_program(logN: int, target: int = 3, r: int = 5, msg_bits: int = 0, ks: int = 1, primes=None, sse: bool = False,
+                             real_msg: bool = False):
     """(num_primes, cst, hevm, rotation offsets, emitter) of the program `one ciphertext at 1 prime, scale 2^40 -> bootstrap -> output`;
     ks = number of special primes of the chain (the VM must be created with ks_special = ks); primes: the VM's chain when it is not the
-    all-60-bit one (target + boot_levels(r) + ks of them)"""
+    all-60-bit one (target + boot_levels(r) + ks of them); real_msg: the half form for real messages (BootstrapEmitter)"""
     K = target + boot_levels(r) + ks
     b = ha.Builder(slots=1 << (logN - 1), init_level=1, shadow=False)
     x = b.input(None, level=1, scale_bits=40)
-    em = BootstrapEmitter(b, logN, K, target, r=r, msg_bits=msg_bits, ks=ks, primes=primes, sse=sse)
+    em = BootstrapEmitter(b, logN, K, target, r=r, msg_bits=msg_bits, ks=ks, primes=primes, sse=sse, real_msg=real_msg)
     y, _ = em.bootstrap(x, 2.0**40)
     b.output(y)
     cst, hv, _ = b.assemble()
@@ -604,19 +656,27 @@ def rotation_offsets(hevm: bytes):
 
 # ---- compiled programs: opcode 10 -> real bootstrapping ------------------------------------------------------------------------------
 def lower_bootstraps(hevm: bytes, cst: bytes, logN: int, num_primes: int, msg_bits: int = 4, r: int = 5, ks: int = 1, primes=None,
-                     sse: bool = False):
+                     sse: bool = False, real_msg: bool = False):
     """Rewrites a program (e.g. one emitted by the reference's compiler) so that every opcode 10 -- `bootstrap`, a decrypt / re-encrypt
     stand-in in the SEAL runtime (SEAL_HEVM.cpp:324-334), the real thing in the HEaaN runtime (HEAAN_HEVM.cpp:386-399) -- becomes the
     real bootstrapping sequence of this module.  Everything else is re-emitted unchanged (same instructions, same constants, registers
     re-allocated).  All opcode 10 of the program must restore the same number of primes t, and the chain must hold num_primes =
     t + boot_levels(r) + ks primes (ks special ones).  sse: every bootstrap's ModRaise runs under the ephemeral sparse secret (opcode 20
-    around it; the VM needs option boot_secret_hw).  Returns (hevm', cst')."""
+    around it; the VM needs option boot_secret_hw).  real_msg: every bootstrap is the half form (BootstrapEmitter), which is only defined
+    for real messages: a source program that itself holds a complex encode (opcode 16) or a conjugation (opcode 17) is refused with
+    ValueError (the compiler's programs and Builder's public calls never emit either).  Returns (hevm', cst')."""
     h = ha.unpack_hevm(hevm)
+    if real_msg:
+        for k, (opc, _, _, _) in enumerate(h["ops"].tolist()):
+            if opc in (OP_ENCODE_COMPLEX, OP_CONJ):
+                raise ValueError(f"real_msg=True: instruction {k} of the source program is opcode {opc} "
+                                 f"({'complex encode' if opc == OP_ENCODE_COMPLEX else 'conj'}): its messages need not be real, "
+                                 "and the half bootstrap is only defined for real ones")
     consts = ha.unpack_cst(cst)
     slots = 1 << (logN - 1)
     qbits = [int(q).bit_length() for q in primes] if primes is not None else [60] * num_primes
     b = ha.Builder(slots=slots, init_level=int(h["init_level"]), shadow=False,
-                   real_boot=dict(num_primes=num_primes, msg_bits=msg_bits, r=r, ks=ks, primes=primes, sse=sse))
+                   real_boot=dict(num_primes=num_primes, msg_bits=msg_bits, r=r, ks=ks, primes=primes, sse=sse, real_msg=real_msg))
     b.constants = [np.asarray(c, dtype=np.float64) for c in consts]
     b._const_index = {c.tobytes(): i for i, c in enumerate(b.constants)}
     cur = {}

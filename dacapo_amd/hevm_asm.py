@@ -218,7 +218,8 @@ class Builder:
         self.boot_level = init_level if boot_level is None else boot_level
         # real_boot = dict(num_primes=K, r=5, msg_bits=7): `bootstrap` emits REAL CKKS bootstrapping (dacapo_amd/ckks_boot.py: ModRaise,
         # CoeffToSlot, EvalMod, SlotToCoeff over extension opcodes 16-19) instead of opcode 10, the SEAL VM's decrypt / re-encrypt stand-in;
-        # sse=True: ModRaise runs under the ephemeral sparse secret (opcode 20 around it; the VM needs option boot_secret_hw)
+        # sse=True: ModRaise runs under the ephemeral sparse secret (opcode 20 around it; the VM needs option boot_secret_hw);
+        # real_msg=True: the half bootstrap for real messages (one EvalMod instead of two; ckks_boot.BootstrapEmitter)
         self.real_boot, self._boot_emitter, self._scale_mirror = real_boot, None, None
         self._memo: dict = {}  # lazy policy: (kind, value id, arg) -> value, so a shared operand is rescaled/bootstrapped once
         self.values: list[Value] = []
@@ -338,7 +339,7 @@ class Builder:
         if self._boot_emitter is None:
             self._boot_emitter = ckks_boot.BootstrapEmitter(self, logN, rb["num_primes"], t, r=rb.get("r", 5), msg_bits=rb.get("msg_bits", 0),
                                                             out_bits=self.waterline, ks=rb.get("ks", 1), primes=rb.get("primes"),
-                                                            sse=rb.get("sse", False))
+                                                            sse=rb.get("sse", False), real_msg=rb.get("real_msg", False))
             self._scale_mirror = ckks_boot.ScaleMirror(self, self._boot_emitter.primes)
         em = self._boot_emitter
         assert t == em.target, "every real bootstrap of a program restores the same number of primes"

@@ -400,6 +400,9 @@ def main():
                     help="K > 0: every bootstrap is REAL CKKS bootstrapping (dacapo_amd/ckks_boot.py) on a chain of K primes "
                          "(K = boot-level + 17 with the default r = 5) instead of opcode 10")
     ap.add_argument("--msg-bits", type=int, default=7, help="--real-boot-primes: bound 2^msg_bits on the magnitude of a bootstrapped value")
+    ap.add_argument("--real-msg", action="store_true",
+                    help="--real-boot-primes: the half bootstrap for real messages (ckks_boot.BootstrapEmitter(real_msg=True)); recorded as "
+                         "real_boot.real_msg in <out>.json")
     ap.add_argument("--hint-need", type=int, default=None,
                     help="honour the model script's hc.bootstrap hints: bootstrap there unless the value still has this many primes to spend "
                          "(default: hints are dropped and the lazy policy bootstraps wherever a value runs out)")
@@ -426,7 +429,7 @@ def main():
     b = hevm_asm.Builder(slots=slots, waterline=a.waterline, init_level=a.init_level, policy="lazy", boot_level=a.boot_level, rotate_reserve=a.rotate_reserve, carry_scale=a.carry_scale,
                          rescale_bits=a.rescale_bits, headroom=a.headroom,
                          shadow=not a.no_shadow,
-                         real_boot=dict(num_primes=a.real_boot_primes, msg_bits=a.msg_bits) if a.real_boot_primes else None)
+                         real_boot=dict(num_primes=a.real_boot_primes, msg_bits=a.msg_bits, real_msg=a.real_msg) if a.real_boot_primes else None)
     b.hint_need = a.hint_need
     stub_torchvision()
     sys.path.insert(0, str(REF / "python/poly"))

@@ -11,6 +11,7 @@ many special primes (dacapo_amd/csrc/hybrid_ks.hip), which is what makes a 31-le
 --sse <main weight>:<ephemeral weight> (e.g. 192:32, or 0:32 for SEAL's dense uniform ternary secret): sparse-secret encapsulation -- the keys
 are generated under a main secret of that weight and every ModRaise runs under an ephemeral sparse secret (options secret_hw / boot_secret_hw,
 opcode 20 around ModRaise); without it the whole key set is generated under a weight-64 secret.
+--real-msg: every bootstrap is the half form for real messages (ckks_boot.lower_bootstraps(real_msg=True): one EvalMod instead of two).
 With fixture resnet20_nt16 (the same model traced at the reference script's own nt = 2^16 slots, examples/benchmarks/ResNet.py:50) and
 logN 17 this is the HEaaN runtime's ring (HEAAN_HEVM.cpp:55-56): ~100 GB of one-prime-per-digit Galois keys, sized for one MI355X."""
 import json
@@ -41,6 +42,9 @@ if "--sse" in sys.argv:
     sse_weights = tuple(int(w) for w in sys.argv[i + 1].split(":"))
     assert len(sse_weights) == 2 and sse_weights[1] > 0, "--sse <main weight>:<ephemeral weight>"
     del sys.argv[i:i + 2]
+real_msg = "--real-msg" in sys.argv
+if real_msg:
+    sys.argv.remove("--real-msg")
 sys.argv = runner.apply_cli_options(sys.argv)  # --opt name=value (csrc/options.hpp)
 
 direct = int(sys.argv[1]) if len(sys.argv) > 1 else 1
@@ -71,7 +75,8 @@ elif chain == "mixed_app":
 else:
     primes = None
 t0 = time.time()
-fx["hevm"], fx["cst"] = cb.lower_bootstraps(fx["hevm"], fx["cst"], logN, KB, msg_bits=msg_bits, ks=ks, primes=primes, sse=sse_weights is not None)
+fx["hevm"], fx["cst"] = cb.lower_bootstraps(fx["hevm"], fx["cst"], logN, KB, msg_bits=msg_bits, ks=ks, primes=primes, sse=sse_weights is not None,
+                                            real_msg=real_msg)
 print(f"opcode 10 -> real bootstrapping: {time.time()-t0:.1f} s", flush=True)
 h = ha.unpack_hevm(fx["hevm"])
 ops = h["ops"]
@@ -137,7 +142,8 @@ def one_run(extra_vm_options):
     out = hevm.getOutput()[0]
     st = hevm.stats()
     key_limbs = hevm.key_digits * 2 * KB
-    res = {"chain": "60-bit" if primes is None else ("mixed: 60-bit base and special primes, 51-bit rescale primes" if chain == "mixed" else
+    res = {"real_msg": real_msg, "bootstrap_s": st["bootstrap_s"], "plaintext_bytes": hevm.plaintextBytes(),
+           "chain": "60-bit" if primes is None else ("mixed: 60-bit base and special primes, 51-bit rescale primes" if chain == "mixed" else
                                                     "mixed_app: 51-bit rescale primes for the program's levels, 60-bit base, bootstrapping and special primes"),
            "prime_bits": [int(q).bit_length() for q in primes] if primes else None,
            "log2_QP": sum(int(q).bit_length() for q in (primes or cb.seal_prime_chain(logN, KB))),
