@@ -1798,38 +1798,18 @@ std::vector<u32> HEVM::rotate_hops(int steps) const
     return hops;
 }
 
-// Option ks_flatten_sums: the stages of the loaded program's rotate-and-add chains that one hoisted lazy sum with an addend can run
-// (plan_flatten.hpp), found on the instructions as plan_flatten_main.cpp walks them: registers renamed to the instructions that wrote them, an
-// input register r the value -1 - r, a value observable through a result register only.  every_key: as if every offset had a key (what
-// hevm_flatten_offsets asks); otherwise a stage needs a key for each of its members in this VM's key set.
-std::vector<FlattenGroup> HEVM::flatten_groups(bool every_key) const
+// The dataflow of the loaded program under the result registers it has NOW (plan_flow.hpp): walked where it is used, never kept.
+PlanFlow HEVM::program_flow() const
 {
-    const size_t nops = ops.size(), nreg = ciphers.size();
+    return plan_flow(ops.data(), ops.size(), ciphers.size(), res_dst.data(), res_dst.size(), arg_level.data(), arg_level.size());
+}
+
+// Option ks_flatten_sums: the stages of the loaded program's rotate-and-add chains that one hoisted lazy sum with an addend can run
+// (plan_flatten.hpp), found on the program's flow.  every_key: as if every offset had a key (what hevm_flatten_offsets asks); otherwise a
+// stage needs a key for each of its members in this VM's key set.
+std::vector<FlattenGroup> HEVM::flatten_groups(const PlanFlow &flow, bool every_key) const
+{
     const int slots = (int)(ctx->N >> 1);
-    std::vector<int> cur(nreg), kind(nops, FLAT_OTHER), src0(nops, 0), src1(nops, 0), offset(nops, 0), readers(nops, 0), result(nops, 0);
-    for (size_t r = 0; r < nreg; r++) cur[r] = -1 - (int)r;
-    for (size_t i = 0; i < nops; i++) {
-        const WireOp &op = ops[i];
-        const bool unary = op.opcode == 1 || op.opcode == 2 || op.opcode == 3 || op.opcode == 4 || op.opcode == 7 || op.opcode == 9 || op.opcode == 10 ||
-                           (op.opcode >= kOpConj && op.opcode <= kOpKeySwitch);
-        const bool binary = op.opcode == 6 || op.opcode == 8;
-        if (!unary && !binary) continue;
-        if (op.opcode == 4 && (int16_t)op.rhs <= 0) continue;                     // a zero modswitch leaves dst untouched
-        if (op.opcode == 1 && (int16_t)op.rhs == 0 && op.dst == op.lhs) continue; // ... and so does a rotation by 0 onto itself
-        if (op.lhs >= nreg || op.dst >= nreg || (binary && op.rhs >= nreg)) continue; // (load_program has checked the operands)
-        auto read = [&](uint16_t r) {
-            const int v = cur[r];
-            if (v >= 0) readers[(size_t)v]++;
-            return v;
-        };
-        src0[i] = read(op.lhs);
-        if (binary) src1[i] = read(op.rhs);
-        if (op.opcode == 1) kind[i] = FLAT_ROTATE, offset[i] = (int16_t)op.rhs;
-        if (op.opcode == 6) kind[i] = FLAT_ADDCC;
-        cur[op.dst] = (int)i;
-    }
-    for (uint64_t r : res_dst)
-        if (r < nreg && cur[(size_t)r] >= 0) result[(size_t)cur[(size_t)r]] = 1;
     std::vector<int> keyed; // the offsets that have a key, from the Galois elements 3^k
     if (!every_key) {
         const u64 m = 2 * (u64)ctx->N;
@@ -1838,10 +1818,7 @@ std::vector<FlattenGroup> HEVM::flatten_groups(bool every_key) const
             if (keys.galois.count((u32)e)) keyed.push_back(flatten_norm_offset(k, slots));
         std::sort(keyed.begin(), keyed.end());
     }
-    FlattenOps in;
-    in.n = (int)nops, in.kind = kind.data(), in.src0 = src0.data(), in.src1 = src1.data(), in.offset = offset.data(), in.readers = readers.data();
-    in.result = result.data();
-    return plan_flatten_groups(in, ks_flatten, slots, every_key ? nullptr : keyed.data(), (int)keyed.size());
+    return flow_flatten_groups(flow, ops.data(), ks_flatten, slots, every_key ? nullptr : keyed.data(), (int)keyed.size());
 }
 
 // EXTENSION (option rot_compose = 1; off by default: SEAL's rotate_internal only ever composes from the power-of-two keys): a bounded key
@@ -2709,7 +2686,7 @@ int hevm_flatten_offsets(void *vm, int64_t *out, int cap)
     auto h = V(vm);
     if (!h->ks_flatten || !h->use_plan || h->ops.empty()) return 0; // (plan = 0 runs every rotate on its own)
     std::set<int> missing;
-    for (const dacapo::FlattenGroup &g : h->flatten_groups(true))
+    for (const dacapo::FlattenGroup &g : h->flatten_groups(h->program_flow(), true))
         for (int o : g.offsets) {
             const uint32_t elt = dc_galois_elt_from_step(static_cast<dc_context *>(hevm_context(vm)), o);
             if (elt && !h->keys.galois.count(elt)) missing.insert(o);

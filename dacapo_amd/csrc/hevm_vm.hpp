@@ -20,7 +20,7 @@
 #include "encoder.hpp"
 #include "io_batch.hpp"
 #include "plan.hpp"
-#include "plan_flatten.hpp"
+#include "plan_flow.hpp"
 
 namespace dacapo {
 
@@ -322,7 +322,8 @@ class HEVM {
     // option ks_flatten_sums = f (2 .. 6; with ks_hoist and ks_lazy_sum): stages of up to f hops of a rotate-and-add chain run as one hoisted lazy
     // sum with an addend (plan_exec.hip section 1a; plan_flatten.hpp names the groups).  Changes the rounding: off by default.
     int ks_flatten = 0;
-    std::vector<FlattenGroup> flatten_groups(bool every_key) const; // the loaded program's groups under the key set held (every_key: as if every offset had a key)
+    PlanFlow program_flow() const; // the loaded program's dataflow under the result registers of this moment (plan_flow.hpp)
+    std::vector<FlattenGroup> flatten_groups(const PlanFlow &flow, bool every_key) const; // the program's groups under the key set held (every_key: as if every offset had a key)
     // option zenc_head = 1: the zero-encryptions at the start of a plan's run() transform only u (plan_zero_encrypt).  Every limb equals
     // zenc_head = 0's.  zenc_chunk_hook (hooks build, test_hooks.hip: HEVM_TEST_ZENC_CHUNK): items per chunk of that head instead of kZencChunk, 0 = unset
     bool zenc_head = true;

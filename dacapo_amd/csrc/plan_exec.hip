@@ -13,9 +13,8 @@
 #include <tuple>
 
 #include "hevm_vm.hpp"
-#include "plan_flatten.hpp"
+#include "plan_flow.hpp"
 #include "plan_levels.hpp"
-#include "plan_relin.hpp"
 
 namespace dacapo {
 
@@ -387,6 +386,26 @@ void HEVM::build_plan()
         return (sv.root == v && sv.def_pop >= 0 && !O[(size_t)sv.def_pop].dead && O[(size_t)sv.def_pop].dst == v) ? sv.def_pop : -1;
     };
 
+    // Sections 1a and 1b group INSTRUCTIONS (plan_flow.hpp walks the loaded program once for both) and apply the groups to the pops that stand
+    // for them: the last hop of a rotate, the one pop of an addcc, a negate or a mulcc.  A group names only instructions whose pop is live.
+    const PlanFlow flow = program_flow();
+    std::vector<int> pop_of(ops.size(), -1);
+    for (size_t i = 0; i < O.size(); i++)
+        if (O[i].op >= 0 && (O[i].kind != P_ROT || O[i].direct)) pop_of[(size_t)O[i].op] = (int)i;
+    auto inst_pop = [&](int op, PopKind kind) {
+        const int pi = pop_of[(size_t)op];
+        if (pi < 0 || O[(size_t)pi].dead || O[(size_t)pi].kind != kind) {
+            fprintf(stderr, "[dacapo_amd] plan: instruction %d of a group has no pseudo-op of its kind (internal error)\n", op);
+            abort();
+        }
+        return pi;
+    };
+    auto drop = [&](int pi) { // (no pop defines or reads this value any more)
+        O[(size_t)pi].dead = true;
+        V[(size_t)O[(size_t)pi].dst].uses = 0, V[(size_t)O[(size_t)pi].dst].def_pop = -1;
+        if (O[(size_t)pi].kind == P_ROT) P.n_keyswitch--, P.n_ntt -= ks_ntts(O[(size_t)pi].level);
+    };
+
     // ---- 1a. flattened rotate-and-add chains (option ks_flatten_sums; SEAL-layout keys, with ks_hoist and ks_lazy_sum) ----------------------
     // A stage of h hops y' = y + rotate(y, o) is ONE hoisted lazy sum with an addend: y + sum over the 2^h - 1 subset sums of rotate(y, .),
     // one decomposition and one division by P where the program runs h dependent key switches (plan_flatten.hpp finds the stages on the
@@ -396,23 +415,11 @@ void HEVM::build_plan()
     // closed: a P_ROTSUM is no term of section 2's n-ary sums and no member of section 2b's groups.  A different rounding than the program's
     // hops (one mod-down instead of h): off by default, and the groups are exported (hevm_plan_flatten_groups) for the oracle's replay.
     if (ks_flatten && !c.hybrid()) {
-        std::map<int, int> rot_pop, sum_pop; // instruction -> the pop of its last hop / of its addcc
-        for (size_t i = 0; i < O.size(); i++) {
-            if (O[i].kind == P_ROT && O[i].direct && O[i].op >= 0) rot_pop[O[i].op] = (int)i;
-            if (O[i].kind == P_SUM && O[i].op >= 0) sum_pop[O[i].op] = (int)i;
-        }
         const int slots = (int)(N >> 1);
-        for (const FlattenGroup &g : flatten_groups(false)) {
+        for (const FlattenGroup &g : flatten_groups(flow, false)) {
             const size_t h = g.rot_ops.size();
             std::vector<int> rp(h), ap(h);
-            for (size_t k = 0; k < h; k++) {
-                const auto r = rot_pop.find(g.rot_ops[k]), a = sum_pop.find(g.add_ops[k]);
-                if (r == rot_pop.end() || a == sum_pop.end()) {
-                    fprintf(stderr, "[dacapo_amd] plan: hop %d / %d of a flattened stage has no pseudo-op (internal error)\n", g.rot_ops[k], g.add_ops[k]);
-                    abort();
-                }
-                rp[k] = r->second, ap[k] = a->second;
-            }
+            for (size_t k = 0; k < h; k++) rp[k] = inst_pop(g.rot_ops[k], P_ROT), ap[k] = inst_pop(g.add_ops[k], P_SUM);
             const int source = O[(size_t)rp[0]].inst_src;
             const Pop &first_add = O[(size_t)ap[0]];
             if (first_add.srcs.size() != 2 || (first_add.srcs[0] != source && first_add.srcs[1] != source)) {
@@ -429,11 +436,6 @@ void HEVM::build_plan()
                     if (e & 1) elt = (elt * g3) & (2 * N - 1);
                 grp.srcs.push_back(source), grp.elts.push_back((u32)elt), grp.keys.push_back(keys.galois.at((u32)elt)), grp.plains.push_back(-1);
             }
-            auto drop = [&](int pi) { // (no pop defines or reads this value any more)
-                O[(size_t)pi].dead = true;
-                V[(size_t)O[(size_t)pi].dst].uses = 0, V[(size_t)O[(size_t)pi].dst].def_pop = -1;
-                if (O[(size_t)pi].kind == P_ROT) P.n_keyswitch--, P.n_ntt -= ks_ntts(O[(size_t)pi].level);
-            };
             for (size_t k = 0; k < h; k++) {
                 for (int pi = O[(size_t)rp[k]].first_hop; pi <= rp[k]; pi++) drop(pi);
                 if (k + 1 < h) drop(ap[k]);
@@ -447,45 +449,32 @@ void HEVM::build_plan()
     // ---- 1b. lazy relinearisation (option ks_lazy_relin; SEAL-layout keys) ---------------------------------------------------------
     // relin(sum_k s_k a_k (x) b_k) is ONE key switch of the summed three-part ciphertext (plan.hpp b_mul_sum_relin) where the program's mulcc
     // instructions run one each.  plan_relin.hpp finds the groups -- maximal trees of addcc / negate over mulcc results that nothing else reads,
-    // at one level -- on the pops as the walk above left them, before any other folding.  A group becomes ONE pop where its closing addcc /
-    // negate stood: it defines that instruction's value, whose scale the walk has already computed in program order exactly as the default run
-    // does; the tree's other pops go away and their values are never materialised.  A value counts as read by the program's end only through a
-    // RESULT register: a register that merely still names an absorbed product when the program ends is not refreshed by such a run.  That is a
-    // different rounding than n mulcc instructions (one mod-down instead of n): off by default, and the groups are exported
-    // (hevm_plan_relin_groups) for the oracle's replay.
+    // at one level -- on the loaded instructions, as section 1a does, before any other folding (an add of a flattened stage has a rotation for
+    // an operand, so it is no node of such a tree).  A group becomes ONE pop where its closing addcc / negate stood: it defines that
+    // instruction's value, whose scale the walk has already computed in program order exactly as the default run does; the tree's other pops go
+    // away and their values are never materialised.  A value counts as read by the program's end only through a RESULT register: a register
+    // that merely still names an absorbed product when the program ends is not refreshed by such a run.  That is a different rounding than n
+    // mulcc instructions (one mod-down instead of n): off by default, and the groups are exported (hevm_plan_relin_groups) for the oracle's
+    // replay.
     if (ks_lazy_relin && !c.hybrid()) {
-        std::vector<int> named(V.size(), 0), is_result(V.size(), 0);
-        for (int v : cur)
-            if (v >= 0) named[(size_t)v]++;
-        for (uint64_t r : res_dst)
-            if (r < nreg && cur[(size_t)r] >= 0) is_result[(size_t)cur[(size_t)r]] = 1;
-        const size_t n = O.size();
-        std::vector<int> kind(n, RELIN_OTHER), src0(n, -1), src1(n, -1), readers(n, 0), level(n, 0), result(n, 0);
-        for (size_t i = 0; i < n; i++) { // (no pop is dead yet)
-            const Pop &p = O[i];
-            kind[i] = p.kind == P_MULCC ? RELIN_MULCC : (p.kind == P_SUM && p.srcs.size() == 2) ? RELIN_ADDCC : p.kind == P_NEG ? RELIN_NEGATE : RELIN_OTHER;
-            if (kind[i] != RELIN_OTHER) src0[i] = own_pop(p.srcs[0]);
-            if (kind[i] == RELIN_MULCC || kind[i] == RELIN_ADDCC) src1[i] = own_pop(p.srcs[1]);
-            readers[i] = V[(size_t)p.dst].uses - named[(size_t)p.dst], level[i] = p.level, result[i] = is_result[(size_t)p.dst];
-        }
-        RelinOps in;
-        in.n = (int)n, in.kind = kind.data(), in.src0 = src0.data(), in.src1 = src1.data(), in.readers = readers.data(), in.level = level.data();
-        in.result = result.data();
-        for (const RelinGroup &g : plan_relin_groups(in, kMulSumMax)) {
+        auto node_pop = [&](int op) { return inst_pop(op, ops[(size_t)op].opcode == 6 ? P_SUM : P_NEG); }; // an addcc or a negate of a tree
+        for (const RelinGroup &g : flow_relin_groups(flow, ops.data(), kMulSumMax)) {
+            const int closing = node_pop(g.closing_op);
             Pop grp;
-            grp.kind = P_MULSUM, grp.level = O[(size_t)g.members[0].mul_op].level, grp.dst = O[(size_t)g.closing_op].dst, grp.op = O[(size_t)g.closing_op].op;
+            grp.kind = P_MULSUM, grp.level = O[(size_t)inst_pop(g.members[0].mul_op, P_MULCC)].level, grp.dst = O[(size_t)closing].dst, grp.op = g.closing_op;
             for (const RelinMember &m : g.members) {
-                const Pop &mp = O[(size_t)m.mul_op];
-                grp.srcs.push_back(mp.srcs[0]), grp.srcs.push_back(mp.srcs[1]), grp.signs.push_back(m.sign), grp.ops.push_back(mp.op);
+                const Pop &mp = O[(size_t)inst_pop(m.mul_op, P_MULCC)];
+                if (mp.level != flow.level[(size_t)m.mul_op]) { // (the flow's level rule per opcode and the walk's above: two statements of one semantics)
+                    fprintf(stderr, "[dacapo_amd] plan: product %d sits at %d primes in the plan and at %d in the program's flow (internal error)\n", m.mul_op,
+                            mp.level, flow.level[(size_t)m.mul_op]);
+                    abort();
+                }
+                grp.srcs.push_back(mp.srcs[0]), grp.srcs.push_back(mp.srcs[1]), grp.signs.push_back(m.sign), grp.ops.push_back(m.mul_op);
             }
-            auto drop = [&](int pi) { // (no pop defines or reads this value any more)
-                O[(size_t)pi].dead = true;
-                V[(size_t)O[(size_t)pi].dst].uses = 0, V[(size_t)O[(size_t)pi].dst].def_pop = -1;
-            };
-            for (const RelinMember &m : g.members) drop(m.mul_op);
-            for (int pi : g.interior)
-                if (pi != g.closing_op) drop(pi);
-            O[(size_t)g.closing_op] = grp;
+            for (const RelinMember &m : g.members) drop(inst_pop(m.mul_op, P_MULCC));
+            for (int op : g.interior)
+                if (op != g.closing_op) drop(node_pop(op));
+            O[(size_t)closing] = grp;
             const int64_t fewer = (int64_t)g.members.size() - 1;
             P.n_keyswitch -= fewer, P.n_ntt -= fewer * ks_ntts(grp.level);
         }

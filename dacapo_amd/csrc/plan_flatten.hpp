@@ -19,8 +19,8 @@
 // register that is no result and still names an absorbed interior value (a stage's rotations, its adds but the closing one) when the program
 // ends is not refreshed by a run that applies the groups.
 //
-// The interface is plain arrays over the ops in program order, so the pass is built and tested without a GPU (plan_flatten_main.cpp,
-// tests/test_plan_flatten.py).
+// The interface is plain arrays over the ops in program order, so the pass is built and tested without a GPU (plan_groups_main.cpp,
+// tests/test_plan_flatten.py); plan_flow.hpp fills them from a loaded program.
 #pragma once
 #include <vector>
 

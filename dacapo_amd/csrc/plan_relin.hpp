@@ -12,7 +12,7 @@
 // an option.
 //
 // The interface is plain arrays over the ops in program order (a topological order), so the pass is built and tested without a GPU
-// (plan_relin_main.cpp, tests/test_plan_relin.py).
+// (plan_groups_main.cpp, tests/test_plan_relin.py); plan_flow.hpp fills them from a loaded program.
 #pragma once
 #include <vector>
 
@@ -23,8 +23,8 @@ enum RelinKind : int { RELIN_OTHER = 0, RELIN_MULCC = 1, RELIN_ADDCC = 2, RELIN_
 struct RelinOps {
     int n = 0;
     const int *kind = nullptr;    // RelinKind
-    const int *src0 = nullptr;    // op that produced the first operand, -1: none of the list (a program input)
-    const int *src1 = nullptr;    // ... the second operand (addcc, mulcc), -1 otherwise
+    const int *src0 = nullptr;    // op that produced the first operand, negative: none of the list (a program input)
+    const int *src1 = nullptr;    // ... the second operand (addcc, mulcc), negative otherwise
     const int *readers = nullptr; // operand slots of later ops that read this op's result
     const int *level = nullptr;   // primes of the op's result
     const int *result = nullptr;  // non-zero: the result is observable when the program ends

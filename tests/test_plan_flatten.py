@@ -1,7 +1,8 @@
 """The flattening pass of rotate-and-add chains (dacapo_amd/csrc/plan_flatten.cpp; option ks_flatten_sums) on its own, without a GPU.
 
-`make -C dacapo_amd/csrc plan_flatten_asan` builds the pass -- host-only C++, plain arrays in, groups out -- with a small driver
-(plan_flatten_main.cpp) under AddressSanitizer + UBSan.  The driver reads a .hevm program and prints the groups: stages of a chain
+`make -C dacapo_amd/csrc plan_groups_asan` builds the pass -- host-only C++, plain arrays in, groups out --, the library's walk of a program
+(plan_flow.cpp) and a small driver (plan_groups_main.cpp) under AddressSanitizer + UBSan.  `plan_groups_asan flatten` reads a .hevm program,
+walks it as the library does and prints the groups: stages of a chain
 y' = y + rotate(y, o) that one hoisted lazy sum with an addend computes (2^h - 1 rotations of the stage's first y, plus that y).
 
   * the committed programs at f = 2, 3, 6: the driver's groups equal those of `flatten_groups` below, a restatement of the rules written here
@@ -22,7 +23,7 @@ from dacapo_amd import hevm_asm as ha
 ROOT = Path(__file__).resolve().parent.parent
 CSRC = ROOT / "dacapo_amd" / "csrc"
 GOLDEN = ROOT / "tests" / "golden"
-DRIVER = CSRC / "build_asan" / "plan_flatten_asan"
+DRIVER = CSRC / "build_asan" / "plan_groups_asan"
 
 ROT, NEG, RESCALE, MODSWITCH, ADDCC, ADDCP, MULCC, MULCP, BOOT = 1, 2, 3, 4, 6, 7, 8, 9, 10
 UNARY = {ROT, NEG, RESCALE, MODSWITCH, ADDCP, MULCP, BOOT, 17, 18, 19, 20}
@@ -106,7 +107,7 @@ def totals(groups):
 def driver():
     if shutil.which("g++") is None or shutil.which("make") is None:
         pytest.skip("no g++ / make")
-    r = subprocess.run(["make", "-C", str(CSRC), "plan_flatten_asan"], capture_output=True, text=True)
+    r = subprocess.run(["make", "-C", str(CSRC), "plan_groups_asan"], capture_output=True, text=True)
     if r.returncode != 0 and ("asan" in r.stderr.lower() or "sanitize" in r.stderr.lower()) and "error:" not in r.stderr:
         pytest.skip("this toolchain has no AddressSanitizer runtime: " + r.stderr[-300:])
     assert r.returncode == 0, r.stderr[-2000:]
@@ -115,7 +116,7 @@ def driver():
 
 def groups_of(driver, hevm_path, f, slots, keyed=None):
     """(rotate instructions, groups as flatten_groups gives them) as the driver prints them; stderr must be empty"""
-    cmd = [str(driver), str(hevm_path), str(f), str(slots)] + ([",".join(str(o) for o in sorted(keyed))] if keyed is not None else [])
+    cmd = [str(driver), "flatten", str(hevm_path), str(f), str(slots)] + ([",".join(str(o) for o in sorted(keyed))] if keyed is not None else [])
     r = subprocess.run(cmd, capture_output=True, text=True)
     assert r.returncode == 0 and r.stderr == "", (r.returncode, r.stderr[-2000:])
     lines = r.stdout.splitlines()
@@ -297,5 +298,5 @@ def test_the_driver_refuses_what_it_cannot_run(driver, tmp_path):
     ops, y = chain([1, 2])
     path = program(tmp_path, ops, results=[y])
     for args in (["1", "2048"], ["7", "2048"], ["2", "1000"]):
-        r = subprocess.run([str(driver), str(path)] + args, capture_output=True, text=True)
+        r = subprocess.run([str(driver), "flatten", str(path)] + args, capture_output=True, text=True)
         assert r.returncode == 2 and "F is 2 .. 6" in r.stderr

@@ -1,7 +1,8 @@
 """The grouping pass of lazy relinearisation (dacapo_amd/csrc/plan_relin.cpp) on its own, without a GPU.
 
-`make -C dacapo_amd/csrc plan_relin_asan` builds the pass -- host-only C++, plain arrays in, groups out -- with a small driver
-(plan_relin_main.cpp) under AddressSanitizer + UBSan.  The driver reads a .hevm program and prints the groups: maximal trees of addcc / negate
+`make -C dacapo_amd/csrc plan_groups_asan` builds the pass -- host-only C++, plain arrays in, groups out --, the library's walk of a program
+(plan_flow.cpp) and a small driver (plan_groups_main.cpp) under AddressSanitizer + UBSan.  `plan_groups_asan relin` reads a .hevm program,
+walks it as the library does and prints the groups: maximal trees of addcc / negate
 over single-use mulcc results at one level, which one key switch can relinearise (dc_ct_mul_sum_relin).
 
   * the committed programs: suite/Multivariate has three groups of three products, HarrisCornerDetection and SobelFilter one group of two,
@@ -21,7 +22,7 @@ from dacapo_amd import hevm_asm as ha
 ROOT = Path(__file__).resolve().parent.parent
 CSRC = ROOT / "dacapo_amd" / "csrc"
 GOLDEN = ROOT / "tests" / "golden"
-DRIVER = CSRC / "build_asan" / "plan_relin_asan"
+DRIVER = CSRC / "build_asan" / "plan_groups_asan"
 
 ROT, NEG, RESCALE, MODSWITCH, ADDCC, MULCC = 1, 2, 3, 4, 6, 8
 
@@ -30,7 +31,7 @@ ROT, NEG, RESCALE, MODSWITCH, ADDCC, MULCC = 1, 2, 3, 4, 6, 8
 def driver():
     if shutil.which("g++") is None or shutil.which("make") is None:
         pytest.skip("no g++ / make")
-    r = subprocess.run(["make", "-C", str(CSRC), "plan_relin_asan"], capture_output=True, text=True)
+    r = subprocess.run(["make", "-C", str(CSRC), "plan_groups_asan"], capture_output=True, text=True)
     if r.returncode != 0 and ("asan" in r.stderr.lower() or "sanitize" in r.stderr.lower()) and "error:" not in r.stderr:
         pytest.skip("this toolchain has no AddressSanitizer runtime: " + r.stderr[-300:])
     assert r.returncode == 0, r.stderr[-2000:]
@@ -39,7 +40,7 @@ def driver():
 
 def groups_of(driver, hevm_path, cap=None):
     """[(closing op, level, [(mul op, sign), ...]), ...] as the driver prints them; stderr must be empty"""
-    r = subprocess.run([str(driver), str(hevm_path)] + ([str(cap)] if cap is not None else []), capture_output=True, text=True)
+    r = subprocess.run([str(driver), "relin", str(hevm_path)] + ([str(cap)] if cap is not None else []), capture_output=True, text=True)
     assert r.returncode == 0 and r.stderr == "", (r.returncode, r.stderr[-2000:])
     lines = r.stdout.splitlines()
     head = lines[0].split()
@@ -105,6 +106,15 @@ def test_a_product_with_two_readers_stays_a_mulcc(driver, tmp_path):
     assert n == 4 and groups == [(3, 5, [(1, 1), (2, 1)])]
 
 
+def test_a_rotation_by_zero_onto_its_own_register_changes_nothing(driver, tmp_path):
+    """p = x y; rotate p by 0 onto its own register; q = z w; p + q: the rotation leaves the register's value alone (the plan adds no hop), so
+    the two products are one group.  By 0 into ANOTHER register it is a copy, a reader of p: no group."""
+    ops = [(MULCC, 10, 0, 1), (ROT, 10, 10, 0), (MULCC, 11, 2, 3), (ADDCC, 12, 10, 11)]
+    assert groups_of(driver, program(tmp_path, ops, results=[12])) == (2, [(3, 5, [(0, 1), (2, 1)])])
+    ops = [(MULCC, 10, 0, 1), (ROT, 13, 10, 0), (MULCC, 11, 2, 3), (ADDCC, 12, 13, 11)]
+    assert groups_of(driver, program(tmp_path, ops, results=[12])) == (2, [])
+
+
 def test_a_product_that_is_a_result_stays_a_mulcc(driver, tmp_path):
     ops = [(MULCC, 10, 0, 1), (MULCC, 11, 2, 3), (ADDCC, 12, 10, 11)]
     assert groups_of(driver, program(tmp_path, ops, results=[12]))[1] == [(2, 5, [(0, 1), (1, 1)])]
@@ -157,5 +167,5 @@ def test_a_tree_above_the_cap_is_split(driver, tmp_path):
     path = program(tmp_path, ops, results=[30])
     assert [len(g[2]) for g in groups_of(driver, path)[1]] == [6]
     assert groups_of(driver, path, cap=4)[1] == [(4, 5, [(0, 1), (1, 1), (3, 1)]), (9, 5, [(5, 1), (6, 1), (8, 1)])]
-    r = subprocess.run([str(driver), str(path), "1"], capture_output=True, text=True)
+    r = subprocess.run([str(driver), "relin", str(path), "1"], capture_output=True, text=True)
     assert r.returncode == 2 and "at least 2" in r.stderr
