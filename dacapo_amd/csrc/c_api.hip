@@ -1,12 +1,14 @@
 // Kernel-level C ABI (include/dacapo_ckks.h): thin extern "C" shims over the launchers.
 #include "../../include/dacapo_ckks.h"
 
+#include <stddef.h>
 #include <string.h>
 
 #include <algorithm>
 #include <vector>
 
 #include "kernels.hpp"
+#include "noise_stats.hpp"
 #include "plan.hpp"
 
 using namespace dacapo;
@@ -120,7 +122,7 @@ void dc_context_destroy(dc_context *ctx)
     if (ctx && ctx->item_ring) (void)hipFree(ctx->item_ring);
     if (ctx)
         for (void *p : { ctx->hoist_items, (void *)ctx->hoist_acc, (void *)ctx->hoist_tmp, (void *)ctx->hoist_digits, (void *)ctx->hoist_ext, (void *)ctx->fold_consts,
-                         (void *)ctx->fold_tmp, ctx->mulsum_table })
+                         (void *)ctx->fold_tmp, ctx->mulsum_table, (void *)ctx->noise_buf })
             if (p) (void)hipFree(p);
     if (ctx && ctx->owned) delete ctx->c;
     delete ctx;
@@ -466,6 +468,40 @@ void dc_poly_mul(dc_context *ctx, uint64_t *dst, const uint64_t *a, const uint64
 void dc_poly_add(dc_context *ctx, uint64_t *dst, const uint64_t *a, const uint64_t *b, int ell, void *stream)
 {
     launch_ew(*ctx->c, EwOp::Add, V(dst, 0), V(a, 0), V(b, 0), 1, 1, ell, S(stream));
+}
+
+// Error statistics of D = m got - want per polynomial (noise_stats.hip): the launches do not depend on `count`; the records are copied to the
+// host and the call waits for them.
+void dc_poly_error_stats(dc_context *ctx, const uint64_t *got, long got_stride, const uint64_t *want, long want_stride, int ell, int count,
+                         int lift_prime, dc_error_stats *out_host, void *stream)
+{
+    static_assert(sizeof(dc_error_stats) == sizeof(NoiseStats) && offsetof(dc_error_stats, max_abs_lo) == offsetof(NoiseStats, max_lo) &&
+                      offsetof(dc_error_stats, inconsistent) == offsetof(NoiseStats, inconsistent),
+                  "dc_error_stats is the device record");
+    Context &c = *ctx->c;
+    hipStream_t s = S(stream);
+    const long need = (long)ell * (long)c.N;
+    if (count < 1 || count > 65535 || ell < 1 || ell > c.K || lift_prime < -1 || lift_prime >= c.K) {
+        fprintf(stderr, "[dacapo_amd] dc_poly_error_stats: %d polynomials of %d limbs, lift_prime %d (1..65535 polynomials, 1..%d limbs, lift_prime -1 "
+                        "or a prime index up to %d)\n", count, ell, lift_prime, c.K, c.K - 1);
+        abort();
+    }
+    auto bad = [&](const uint64_t *p, long stride) { return ((uintptr_t)p & 15) != 0 || (stride & 1) != 0 || (count > 1 && stride < need); };
+    if (!got || !out_host || bad(got, got_stride) || (want && bad(want, want_stride))) {
+        fprintf(stderr, "[dacapo_amd] dc_poly_error_stats: needs polynomials and an output, 16-byte aligned, at even strides of at least ell * N = %ld "
+                        "words (strides %ld, %ld)\n", need, got_stride, want_stride);
+        abort();
+    }
+    const size_t bytes = noise_scratch_words(c, ell, count) * sizeof(u64);
+    if (bytes > ctx->noise_cap) { // (growing waits for the device: hipFree)
+        if (ctx->noise_buf) DC_HIP_CHECK(hipFree(ctx->noise_buf));
+        ctx->noise_buf = nullptr, ctx->noise_cap = 0;
+        DC_HIP_CHECK(hipMalloc(&ctx->noise_buf, bytes));
+        ctx->noise_cap = bytes;
+    }
+    const NoiseStats *total = noise_error_stats(c, ctx->noise_buf, got, got_stride, want, want_stride, ell, count, lift_prime, s);
+    DC_HIP_CHECK(hipMemcpyAsync(out_host, total, (size_t)count * sizeof(NoiseStats), hipMemcpyDeviceToHost, s));
+    DC_HIP_CHECK(hipStreamSynchronize(s));
 }
 
 uint32_t dc_galois_elt_from_step(const dc_context *ctx, int step)

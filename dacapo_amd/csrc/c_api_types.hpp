@@ -20,4 +20,7 @@ struct dc_context {
     // dc_ct_mul_sum_relin: the item and its term table (a destination that aliases an operand goes through fold_tmp)
     void *mulsum_table = nullptr;
     size_t mulsum_cap = 0;
+    // dc_poly_error_stats: the difference polynomials and the reduction's records (noise_stats.hpp noise_scratch_words), grown on demand
+    dacapo::u64 *noise_buf = nullptr;
+    size_t noise_cap = 0;
 };

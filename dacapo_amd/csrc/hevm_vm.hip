@@ -1743,6 +1743,45 @@ void HEVM::decrypt_batch(int64_t i, double *out, int64_t stride, int first_strea
     DC_HIP_CHECK(hipStreamSynchronize(S()));
 }
 
+// c0 + c1 s of register i of streams first_stream ..., all limbs of the register's level, NTT form, into device memory: decrypt's first step
+// for every stream in one launch (io_batch.hip io_phase_kernel), limb for limb the oracle's orc_decrypt.  Returns the level.
+int HEVM::phase_batch(int64_t i, u64 *out, int64_t stride, int first_stream, int count)
+{
+    static const char *const me = "hevm_phase_batch";
+    if (!keys.sk) {
+        fprintf(stderr, "[dacapo_amd] %s: this VM has no secret key\n", me);
+        abort();
+    }
+    io_check_streams(me, first_stream, count);
+    Context &c = *ctx;
+    const size_t N = c.N, slice = (size_t)2 * c.K * N;
+    if (i < 0 || (size_t)i >= ciphers.size()) {
+        fprintf(stderr, "[dacapo_amd] %s: register %lld outside the VM's %zu\n", me, (long long)i, ciphers.size());
+        abort();
+    }
+    const hevm_ctxt &ct = reg((size_t)i);
+    if (ct.level < 1) {
+        fprintf(stderr, "[dacapo_amd] %s: empty register %lld\n", me, (long long)i);
+        abort();
+    }
+    const int ell = ct.level;
+    if (!out || ((uintptr_t)out & 15) != 0 || (stride & 1) != 0 || stride < (int64_t)ell * (int64_t)N) {
+        fprintf(stderr, "[dacapo_amd] %s: needs a 16-byte aligned device output and an even stride >= level * N = %lld words: stride %lld\n", me,
+                (long long)ell * (long long)N, (long long)stride);
+        abort();
+    }
+    IoTabLayout lay;
+    const size_t o_src = lay.add(sizeof(CtView), (size_t)count);
+    io.h_tab.assign(lay.bytes, 0);
+    CtView *h_src = reinterpret_cast<CtView *>(io.h_tab.data() + o_src);
+    for (int k = 0; k < count; k++) h_src[k] = CtView{ reg_base[(size_t)i] + (size_t)(first_stream + k) * slice, (long)ct.poly_stride };
+    const CtView *d_src = reinterpret_cast<const CtView *>(static_cast<const unsigned char *>(io_upload_tables(lay.bytes)) + o_src);
+    io_phase(c, out, (long)stride, d_src, keys.sk, count, ell, S());
+    io.launches = io.chunks = 1;
+    DC_HIP_CHECK(hipStreamSynchronize(S()));
+    return ell;
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // opcode handlers (SEAL_HEVM.cpp:268-334) and dispatch (:336-401)
 // ---------------------------------------------------------------------------------------------------------
@@ -2460,6 +2499,10 @@ void hevm_decrypt_result_batch(void *vm, int64_t i, double *out, int64_t stride,
         abort();
     }
     hevm->decrypt_batch((int64_t)hevm->res_dst[(size_t)i], out, stride, first_stream, count, where);
+}
+int hevm_phase_batch(void *vm, int64_t reg, uint64_t *out_dev, int64_t stride, int first_stream, int count)
+{
+    return V(vm)->phase_batch(reg, out_dev, stride, first_stream, count);
 }
 void hevm_last_io_stats(void *vm, int64_t *launches, int64_t *chunks)
 {

@@ -413,6 +413,7 @@ class HEVM {
     void *io_upload_tables(size_t bytes);
     void encrypt_batch(int64_t arg, const double *vals, int len, int64_t stride, int first_stream, int count, int where);
     void decrypt_batch(int64_t reg, double *out, int64_t stride, int first_stream, int count, int where);
+    int phase_batch(int64_t reg, u64 *out_dev, int64_t stride, int first_stream, int count);
     void run();
 
     // opcode handlers (SEAL_HEVM.cpp:268-334)

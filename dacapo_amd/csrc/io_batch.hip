@@ -32,6 +32,29 @@ void io_add_plain(const Context &c, const CtView *d_dst, const u64 *pt, int B, i
               c.N, c.d_mods, set ? 1 : 0);
 }
 
+// ---- phase: c0 + c1 s of B register slices (decrypt_kernel of hevm_vm.hip with the item in grid.z) ---------------------------------------
+// grid = (N/512, ell, B).  src[b] is a register slice; out [B] polynomials [ell][N], out_stride words apart.
+__global__ __launch_bounds__(kIoThreads) void io_phase_kernel(u64 *__restrict__ out, long out_stride, const CtView *__restrict__ src,
+                                                               const u64 *__restrict__ sk, size_t N, const DModulus *__restrict__ mods)
+{
+    const int i = blockIdx.y, b = blockIdx.z;
+    const DModulus M = mods[i];
+    const CtView ct = src[b];
+    const size_t k = ((size_t)blockIdx.x * kIoThreads + threadIdx.x) * 2;
+    const u64x2 c0 = *reinterpret_cast<const u64x2 *>(ct.limb(0, i, N) + k), c1 = *reinterpret_cast<const u64x2 *>(ct.limb(1, i, N) + k),
+                s = *reinterpret_cast<const u64x2 *>(sk + (size_t)i * N + k);
+    u64x2 r;
+#pragma unroll
+    for (int t = 0; t < 2; t++) r[t] = addmod(c0[t], mulmod(c1[t], s[t], M), M.q);
+    *reinterpret_cast<u64x2 *>(out + (long)b * out_stride + (long)i * (long)N + (long)k) = r;
+}
+
+void io_phase(const Context &c, u64 *out, long out_stride, const CtView *d_src, const u64 *sk, int B, int ell, hipStream_t s)
+{
+    DC_LAUNCH(io_phase_kernel, dim3((unsigned)(c.N / (2 * kIoThreads)), (unsigned)ell, (unsigned)B), dim3(kIoThreads), 0, s, out, out_stride, d_src,
+              sk, c.N, c.d_mods);
+}
+
 // ---- decrypt: compose, centre, divide by the scale (dec_crt_kernel of hevm_vm.hip with the item in grid.y) --------------------------------
 // grid = (N/256, B).  (Compiled like that kernel: the composition's sum of products is contracted the same way.)
 __global__ __launch_bounds__(kIoThreads) void io_dec_crt_kernel(double2 *__restrict__ v, const u64 *__restrict__ coef, int ell, size_t N,

@@ -90,6 +90,8 @@ def _bind(path):
         L.dc_galois_ntt.argtypes = [vp, u64p, lng, u64p, lng, C.c_uint32, i32, i32, vp]
         L.dc_poly_mul.argtypes = [vp, u64p, u64p, u64p, i32, vp]
         L.dc_poly_add.argtypes = [vp, u64p, u64p, u64p, i32, vp]
+        L.dc_poly_error_stats.argtypes = [vp, u64p, lng, u64p, lng, i32, i32, i32, vp, vp]
+        L.dc_poly_error_stats.restype = None
         L.dc_galois_elt_from_step.restype = C.c_uint32
         L.dc_galois_elt_from_step.argtypes = [vp, i32]
         from .runner import bind_options
@@ -138,7 +140,39 @@ def read_device(ptr: int, shape, dtype=np.uint64) -> np.ndarray:
     return out
 
 
+class ErrorStats(C.Structure):
+    """dc_error_stats (include/dacapo_ckks.h): the statistics of one polynomial's D = m got - want"""
+    _fields_ = [("sum_sq", C.c_double), ("sum", C.c_double), ("max_abs_lo", C.c_uint64), ("max_abs_hi", C.c_uint64),
+                ("inconsistent", C.c_int64)]
+
+    @property
+    def max_abs(self) -> int:
+        return (int(self.max_abs_hi) << 64) | int(self.max_abs_lo)
+
+
+def _ptr(x):
+    """a device address: a DeviceBuffer, an int or None"""
+    return x.ptr if isinstance(x, DeviceBuffer) else x
+
+
 class Context:
+    @classmethod
+    def of_vm(cls, hevm):
+        """the kernel-level context behind a runner.HEVM (hevm_context): borrowed, never destroyed from here"""
+        from . import LIB_PATH_GW
+
+        self = cls.__new__(cls)
+        self.L = L = lib(LIB_PATH_GW) if hevm.lw._name == str(LIB_PATH_GW) else lib()
+        self.h, self._borrowed = hevm.ctx_handle, True
+        self.key_digits, self.max_level = hevm.key_digits, hevm.max_level
+        self.logN, self.N, self.K = hevm.logN, hevm.N, hevm.K
+        out = np.zeros(self.K, dtype=np.uint64)
+        L.dc_context_primes(self.h, out.ctypes.data)
+        self.primes = [int(x) for x in out]
+        L.dc_context_roots(self.h, out.ctypes.data)
+        self.roots = [int(x) for x in out]
+        return self
+
     def __init__(self, logN=15, num_primes=14, bit_size=60, primes=None, special=1, alpha=None):
         """special / alpha: the grouped-digit key-switching extension (dc_context_create_hybrid); 1 / 1 is SEAL's scheme"""
         narrow = bit_size != 60 or (primes is not None and any(int(p).bit_length() != 60 for p in primes))
@@ -166,7 +200,8 @@ class Context:
 
     def __del__(self):
         try:
-            self.L.dc_context_destroy(self.h)
+            if not getattr(self, "_borrowed", False):
+                self.L.dc_context_destroy(self.h)
         except Exception:
             pass
 
@@ -201,6 +236,28 @@ class Context:
         pl = (C.c_void_p * n)(*plains) if plains is not None else None
         sp = (C.c_void_p * n)(*plains_sp) if plains_sp is not None else None
         self.L.dc_ct_rotate_sum_hoisted_add(self.h, dst, dst_stride, addend, addend_stride, ps, src_stride, ge, pk, pl, sp, n, ell, stream)
+
+    def poly_mul(self, dst, a, b, ell: int, stream=None):
+        """dc_poly_mul: dst = a . b limb-wise over `ell` limbs (NTT form); DeviceBuffers or device addresses"""
+        self.L.dc_poly_mul(self.h, _ptr(dst), _ptr(a), _ptr(b), ell, stream)
+
+    def poly_add(self, dst, a, b, ell: int, stream=None):
+        """dc_poly_add: dst = a + b limb-wise over `ell` limbs"""
+        self.L.dc_poly_add(self.h, _ptr(dst), _ptr(a), _ptr(b), ell, stream)
+
+    def galois_ntt(self, dst, dst_stride: int, src, src_stride: int, elt: int, polys: int, ell: int, stream=None):
+        """dc_galois_ntt: dst[p] = galois_elt(src[p]) for `polys` polynomials of `ell` limbs at the given strides (NTT form)"""
+        self.L.dc_galois_ntt(self.h, _ptr(dst), dst_stride, _ptr(src), src_stride, elt, polys, ell, stream)
+
+    def error_stats(self, got, want, ell: int, count: int, lift_prime: int = -1, got_stride=None, want_stride=None, stream=None):
+        """dc_poly_error_stats: per polynomial the statistics of D = m got - want as exact centred integers (m = 1, or prime `lift_prime`):
+        a list of `count` ErrorStats.  got / want: DeviceBuffers or device addresses of `count` polynomials [ell][N] in NTT form, strides in
+        words (default ell * N); want None = 0."""
+        out = (ErrorStats * count)()
+        dense = ell * self.N
+        self.L.dc_poly_error_stats(self.h, _ptr(got), dense if got_stride is None else got_stride, _ptr(want),
+                                   dense if want_stride is None else want_stride, ell, count, lift_prime, C.addressof(out), stream)
+        return list(out)
 
     def elt_from_step(self, step: int) -> int:
         return int(self.L.dc_galois_elt_from_step(self.h, step))

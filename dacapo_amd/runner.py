@@ -122,6 +122,9 @@ def bind_vm_lib(path):
     for f in (L.hevm_decrypt_batch, L.hevm_decrypt_result_batch):
         f.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int]
         f.restype = None
+    # c0 + c1 s of a register of all streams into device memory (dacapo_amd/noise.py); returns the register's level
+    L.hevm_phase_batch.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int]
+    L.hevm_phase_batch.restype = ctypes.c_int
     L.hevm_last_io_stats.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
     L.hevm_last_io_stats.restype = None
     L.dc_device_sync.argtypes = []

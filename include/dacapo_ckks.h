@@ -174,6 +174,27 @@ void dc_galois_ntt(dc_context *ctx, uint64_t *dst, long dst_stride, const uint64
 void dc_poly_mul(dc_context *ctx, uint64_t *dst, const uint64_t *a, const uint64_t *b, int ell, void *stream);
 void dc_poly_add(dc_context *ctx, uint64_t *dst, const uint64_t *a, const uint64_t *b, int ell, void *stream);
 
+/* EXTENSION (measurement, not an operation of the scheme): how far `got` is from `want`, as exact integers.  got / want hold `count`
+ * polynomials [ell][N] in NTT form, got_stride / want_stride words apart (even, >= ell * N; the pointers 16-byte aligned); want == NULL
+ * stands for 0.  D = m got - want over limbs 0 .. ell-1, with m = 1 when lift_prime is -1 and m = q_{lift_prime} (taken modulo every limb)
+ * otherwise -- the rescale case: got the result at ell primes, want the operand's first ell limbs, lift_prime >= ell the dropped prime, so
+ * that D / m is the rounding error.  lift_prime < ell is allowed too: m is 0 modulo that limb, so got's limb there is not read into D and D
+ * is -want on it -- a rescale's result padded with one zero limb against the WHOLE operand, which is how a rescale to one prime is
+ * measured (q_1 . out - in exceeds q_0 / 2, but not q_0 q_1 / 2).  Every coefficient of D is lifted to the centred integer it stands for in
+ * (-M/2, M/2], M = q_0 at ell = 1 and q_0 q_1 otherwise (|D| must stay below M/2: the further limbs are only checked against that value
+ * and disagreements counted in `inconsistent`).  One record per polynomial is written to out_host[count] (HOST memory); the call
+ * synchronises `stream`.  Launches: the difference, the batched inverse transform, lift-and-reduce, finish -- the same number whatever
+ * `count` is; no atomics, so equal inputs give equal bits on every run.  Scratch is kept in the context.
+ * noise, in the unit of the reference compiler's noiseTable, is (N/2) mean_j (D_j / m)^2 = sum_sq / 2. */
+typedef struct {
+    double sum_sq;                   /* sum_j (D_j / m)^2 */
+    double sum;                      /* sum_j  D_j / m    */
+    uint64_t max_abs_lo, max_abs_hi; /* max_j |D_j|, exact, 128 bits */
+    int64_t inconsistent;            /* coefficients whose further limbs contradict the value lifted from the first two */
+} dc_error_stats;
+void dc_poly_error_stats(dc_context *ctx, const uint64_t *got, long got_stride, const uint64_t *want, long want_stride, int ell, int count,
+                         int lift_prime, dc_error_stats *out_host, void *stream);
+
 /* GaloisTool::get_elt_from_step (host): step > 0 rotates left; 0 = conjugation; returns 0 if |step| >= N/2 */
 uint32_t dc_galois_elt_from_step(const dc_context *ctx, int step);
 

@@ -190,6 +190,12 @@ void hevm_select_stream(void *vm, int s);
 void hevm_encrypt_batch(void *vm, int64_t arg, const double *vals, int len, int64_t stride, int first_stream, int count, int where);
 void hevm_decrypt_batch(void *vm, int64_t reg, double *out, int64_t stride, int first_stream, int count, int where);
 void hevm_decrypt_result_batch(void *vm, int64_t i, double *out, int64_t stride, int first_stream, int count, int where);
+/* The phase of cipher register `reg`, all streams at once: out_dev + b * stride = c0 + c1 s of stream first_stream + b over all limbs of the
+ * register's level, [level][N], NTT form, in DEVICE memory (16-byte aligned; stride even, >= level * N words) -- the polynomial decrypt
+ * transforms and decodes, limb for limb, before any of that.  One launch for all streams, one synchronisation; returns the register's
+ * level.  What noise measurements compare exactly (dacapo_amd/noise.py, dc_poly_error_stats); it reveals what decrypt reveals.  Aborts as
+ * hevm_decrypt_batch does: "this VM has no secret key", streams out of range, an empty register. */
+int hevm_phase_batch(void *vm, int64_t reg, uint64_t *out_dev, int64_t stride, int first_stream, int count);
 void hevm_last_io_stats(void *vm, int64_t *launches, int64_t *chunks);
 /* wall seconds the last run() spent inside opcode 10 (decrypt / re-encode / encrypt) */
 double hevm_last_run_bootstrap_seconds(void *vm);

@@ -213,6 +213,25 @@ def hop_levels(name, labels=("`hyb_fuse` = 2", "`hyb_fuse` = 1", "`hyb_fuse` = 0
     return "; ".join(f"{f}: {v} µs" for f, v in zip(labels, out))
 
 
+def noise_row():
+    d = J("noise_table.json")
+    if not d:
+        return None
+    def cell(e):
+        s = f"{e['measured']:.3e}"
+        if e.get("measured_over_closed_form"):
+            s += f" (× {e['measured_over_closed_form']:.2f} of the closed form"
+            s += f", × {e['measured_over_reference']:.2f} of the reference's entry)" if e.get("measured_over_reference") else ")"
+        return s
+    parts = []
+    for name, row in d["rows"].items():
+        pick = [row[i] for i in (0, 1, len(row) - 1)]
+        parts.append(f"`{name}` at " + " / ".join(str(e["primes"]) for e in pick) + " primes: " + " / ".join(cell(e) for e in pick))
+    return (f"| `noise_table.json`, `profiled_SEAL_MI355X.json` | the noise each op adds, measured on the device (`dacapo_amd/noise.py`: phases of {d['samples']} encryptions per entry, exact "
+            f"error statistics; (N/2) · mean e², integer units, N = {d['polynomialDegree']}, {d['primes']} primes), per entry beside the closed form and the reference's `noiseTable` entry — "
+            + "; ".join(parts) + "; the profile carries the three rows as its `noiseTable` next to a fresh latency table | `python tools/legs/profile_backend.py --noise --out profiles/profiled_SEAL_MI355X.json` |")
+
+
 print("# profiles/ — rocprofv3 evidence (MI355X, ROCm 7.2)\n")
 print("Generated by `python tools/profiles_readme.py > profiles/README.md`: every figure in the round-3 ... round-6 tables is read from the file on its row.\n")
 print("## Round 6 (everything `r06_*`; one `gpurun` call of `tools/collect_profiles.sh r06` on the committed build -- the JSON files that `bench.py` reads carry "
@@ -242,6 +261,7 @@ rows.append(f"| `plan_builder_refactor.txt` | the plan builder's refactor (one o
 rows.append(f"| `io_batch_ab.txt` | all streams' inputs and results at once (`hevm_encrypt_batch`, `hevm_decrypt_result_batch`) against the sequential calls, 8 streams of the headline fixture at N = 2^15 / 14 primes, one process, forms alternating, from host and from device memory, with `hevm_last_io_stats`: {first_lines('io_batch_ab.txt', 'one setInputs, host', 1)} | `python tools/legs/io_batch_ab.py --out profiles/io_batch_ab.txt` |")
 rows.append("| `ks_flatten_ab.txt` | flattened rotate-and-add chains (option `ks_flatten_sums`, `dc_ct_rotate_sum_hoisted_add`): `run()` of the headline on alternating VMs, option off / on / off with `ks_hoist` = 1 and `ks_lazy_sum` = 2 in every arm, f = 2, 3, 4, 6 at 1 and 8 streams, a default-options VM beside them: ms per run with the off/off spread, the plan's report (pseudo-ops, steps, waves, launches), key switches, groups / members / hops absorbed, composite keys added and their HBM, rms against the torch logits; the benchmark line of the parent commit's tree and library on the same box; a kernel trace of one VM at the best f and of one with the option off (`f_ks_gsum_kernel` against the hop kernels it replaced) | `python tools/legs/ks_flatten_ab.py --out profiles/ks_flatten_ab.txt`; `rocprofv3 --kernel-trace --stats -- python tools/legs/ks_flatten_ab.py --trace-f F` |")
 rows.append(f"| `boot_real_msg_ab.txt` | the half bootstrap for real messages (`ckks_boot.BootstrapEmitter(real_msg=True)`: one EvalMod and one SlotToCoeff chain, no new kernel or key) against the default full form: one bootstrap at N = 2^15, N = 2^17 and config 4's geometry (without and with `hyb_lazy_sum`), full / half / full in one process — ms, key switches, worst-slot and rms error; config 4 and the 526-bootstrap ResNet-20 at N = 2^15 in both forms — `run_s`, key switches, rms against torch and the plaintext evaluation, argmax, plaintext bytes: {first_lines('boot_real_msg_ab.txt', 'half / full time', 1)} | `python tools/legs/boot_demo.py 17 [5 1 14 9 8] --forms full,half,full`; `python tools/legs/resnet_real_boot.py 1 resnet20_nt16 17 1 b14 9 8 [--real-msg]`; `python tools/legs/resnet_real_boot.py 1 [--real-msg]` |")
+rows.append(noise_row())
 print("\n".join(r for r in rows if r))
 print()
 print("## Round 5 (everything `r05_*`; one `gpurun` call of `tools/collect_profiles.sh r05` on the committed build -- the JSON files that `bench.py` reads carry "
