@@ -153,8 +153,14 @@ static void b_ks_tail(Context &c, const BatchWs &w, u64 *digits, const KsItem *i
     });
 }
 
-void b_rotate_hops(Context &c, const BatchWs &w, const KsItem *d_items, int B, int ell, hipStream_t s, const Handoff &h, int unique)
+void b_rotate_hops(Context &c, const BatchWs &w, const KsItem *d_items, int B, int ell, hipStream_t s, const Handoff &h, int unique, bool addend)
 {
+    // an item's addend (KsItem::add) is a start value of the fused middle's accumulators and of nothing else: same split as b_ks_tail
+    if (addend && (c.hybrid() || !fuse_mac() || (long)(c.N >> 10) * B * ell * ell >= fuse_mac_threshold())) {
+        fprintf(stderr, "[dacapo_amd] b_rotate_hops: an item carries an addend, which only the fused middle of SEAL-layout key switching adds "
+                        "(%s)\n", c.hybrid() ? "this context switches keys with grouped digits" : "option ks_fuse_mac = 0, or the batch is above ks_fuse_mac_tiles");
+        abort();
+    }
     if (c.hybrid()) { // (the plan links no steps in this mode: h is empty)
         hyb_rotate_hops(c, w, d_items, B, ell, s, unique);
         return;

@@ -373,6 +373,21 @@ void dc_ct_rotate_hop(dc_context *ctx, uint64_t *dst, long dst_stride, const uin
     const KsItem *d = static_cast<const KsItem *>(item_slot(ctx, &it, sizeof(it), S(stream)));
     b_rotate_hops(*ctx->c, batch_ws(ctx->c->ws0), d, 1, ell, S(stream));
 }
+// dst = apply_galois(src) + addend: dc_ct_rotate_hop with one addend at level ell, which the fused middle adds exactly (KsItem::add; fused_ks.hip
+// f_ks_frows_mac_kernel).  The addend is read by the middle launch alone, before the last launch writes dst: it may be src or dst.
+void dc_ct_rotate_hop_add(dc_context *ctx, uint64_t *dst, long dst_stride, const uint64_t *src, long src_stride, const uint64_t *addend,
+                          long addend_stride, uint32_t galois_elt, const uint64_t *galois_key, int ell, void *stream)
+{
+    if (ctx->c->hybrid()) {
+        fprintf(stderr, "[dacapo_amd] dc_ct_rotate_hop_add: this context switches keys with grouped digits (ks_special > 1); the call is for "
+                        "SEAL-layout keys (use dc_ct_rotate_hop and dc_ct_add)\n");
+        abort();
+    }
+    KsItem it{ V(src, src_stride), V(dst, dst_stride), galois_key, galois_elt, 0 };
+    it.add = V(addend, addend_stride);
+    const KsItem *d = static_cast<const KsItem *>(item_slot(ctx, &it, sizeof(it), S(stream)));
+    b_rotate_hops(*ctx->c, batch_ws(ctx->c->ws0), d, 1, ell, S(stream), Handoff{}, 0, true);
+}
 // `count` hops of one source on one decomposition (hoist_ks.hip).  The decomposition lives in the context's default workspace (one source);
 // what grows with the hop count -- the item table, the accumulators, the mod-down terms -- is kept in the handle.
 void dc_ct_rotate_hoisted(dc_context *ctx, uint64_t *const *dsts, long dst_stride, const uint64_t *src, long src_stride,

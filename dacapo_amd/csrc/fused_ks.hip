@@ -962,8 +962,22 @@ __global__ __launch_bounds__(kTileThreads) void f_ks_frows_mac_kernel(const u64 
         const u64 P = pmod[m];
         u64 cv[E];
         galois_gather<E>(cv, c0, (u32)g[0], it.elt, logN);
+        if (it.add.p) {
+            // ... and so does an addend y at the hop's level (option ks_fold_add: y' = y + rotate(y, o) as ONE key switch).  P y = 0 modulo the
+            // special prime, so the mod-down's term t is unchanged and ((acc + P (galois(c0) + y0)) - t) P^-1 = galois(c0) + y0 + (acc - t) P^-1,
+            // likewise y1 on the other accumulator: the limbs of "rotate, then add".  Both start values are canonical residues (the bound
+            // above holds as it is).  A ROWS tile leaves a thread the consecutive coefficients g[0] + e: y is read as 16-byte vectors, no map.
+            const u64 *y0 = it.add.limb(0, m, N) + g[0], *y1 = it.add.limb(1, m, N) + g[0];
 #pragma unroll
-        for (int e = 0; e < E; e++) a0[e].lo = mulmod(cv[e], P, M);
+            for (int e = 0; e < E; e += 2) {
+                const u64x2 v0 = *reinterpret_cast<const u64x2 *>(y0 + e), v1 = *reinterpret_cast<const u64x2 *>(y1 + e);
+                a0[e].lo = mulmod(addmod(cv[e], v0.x, M.q), P, M), a0[e + 1].lo = mulmod(addmod(cv[e + 1], v0.y, M.q), P, M);
+                a1[e].lo = mulmod(v1.x, P, M), a1[e + 1].lo = mulmod(v1.y, P, M);
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < E; e++) a0[e].lo = mulmod(cv[e], P, M);
+        }
     }
     if (FOLD && m == ell - 1) { // (start values for the reason given above: nothing else is live yet)
         const MulRsItem &it = reinterpret_cast<const MulRsItem *>(items)[b];

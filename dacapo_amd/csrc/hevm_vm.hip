@@ -509,6 +509,7 @@ void HEVM::init_context(int logN, int K, const u64 *primes, int dir_ksp, int dir
             abort();
         }
     }
+    ks_fold_add = option(OPT_KS_FOLD_ADD) != 0; // (grouped digits, ks_hoist, ks_fuse_mac = 0: the rule finds nothing to fold)
     zenc_head = option(OPT_ZENC_HEAD) != 0;
     // prime_bits = b (45..60; the generic-width build only): the chain CoeffModulus::Create(N, {b, b, ...}) instead of the reference's
     // 60-bit one (SEAL_HEVM.cpp:48-53) -- e.g. 51 for rescale primes of the HEaaN configuration's width
@@ -2279,7 +2280,7 @@ void HEVM::execute()
 {
     memset(op_counts, 0, sizeof(op_counts));
     n_keyswitch = n_ntt = 0;
-    n_hops = n_decomp = 0, n_fold = 0, n_relin_groups = n_relin_products = 0, n_flat_groups = n_flat_members = n_flat_hops = 0;
+    n_hops = n_decomp = 0, n_fold = 0, n_add_folds = 0, n_relin_groups = n_relin_products = 0, n_flat_groups = n_flat_members = n_flat_hops = 0;
     t_bootstrap = 0.0;
     int i = (int)((header.hevm_header_size + config.config_body_length) / 8), j = 0;
     for (const WireOp &op : ops) {
@@ -2771,6 +2772,10 @@ void hevm_last_run_flatten_stats(void *vm, int64_t *groups, int64_t *members, in
     if (members) *members = V(vm)->n_flat_members;
     if (hops_absorbed) *hops_absorbed = V(vm)->n_flat_hops;
 }
+
+// option ks_fold_add: two-term sums that the last run() computed inside a rotation's last hop (every stream counted); 0 with the option off and
+// in the loop (plan = 0)
+int64_t hevm_last_run_add_fold_stats(void *vm) { return V(vm)->n_add_folds; }
 
 // option ks_lazy_relin: the groups of ct x ct products that the plan of the last run() relinearises with one key switch each.
 // out = [n, closing_op, (mul_op, sign) x n, ...]: per group its size, the instruction index of the addcc / negate whose result it computes, and

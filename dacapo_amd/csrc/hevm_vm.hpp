@@ -263,6 +263,7 @@ class HEVM {
         int64_t n_hops = 0, n_decomp = 0; // rotation hops and the decompositions computed for them (hevm_last_run_hoist_stats)
         int64_t n_relin_groups = 0, n_relin_products = 0; // P_MULSUM items and their terms (hevm_last_run_relin_stats)
         int64_t n_flat_groups = 0, n_flat_members = 0, n_flat_hops = 0; // flattened stages, their rotations and the hops they absorbed, once per stream (hevm_last_run_flatten_stats)
+        int64_t n_add_folds = 0;          // two-term sums that a rotation's last hop computes (option ks_fold_add; hevm_last_run_add_fold_stats), per stream until the plan is ready
         int64_t n_fold = 0;               // items of multiply steps that run with their rescale folded in (hevm_last_run_fold_rescale_stats)
         size_t launches = 0, max_live = 0;
         hipGraph_t graph = nullptr;
@@ -322,6 +323,9 @@ class HEVM {
     // option ks_flatten_sums = f (2 .. 6; with ks_hoist and ks_lazy_sum): stages of up to f hops of a rotate-and-add chain run as one hoisted lazy
     // sum with an addend (plan_exec.hip section 1a; plan_flatten.hpp names the groups).  Changes the rounding: off by default.
     int ks_flatten = 0;
+    // option ks_fold_add = 1 (SEAL-layout keys): y + rotate(x, o) is the rotation's own last hop with y as its addend (plan_exec.hip section 3a;
+    // plan.hpp KsItem::add).  Every limb equals the default path's.  The loop (plan = 0) runs the instructions as written.
+    bool ks_fold_add = true;
     PlanFlow program_flow() const; // the loaded program's dataflow under the result registers of this moment (plan_flow.hpp)
     std::vector<FlattenGroup> flatten_groups(const PlanFlow &flow, bool every_key) const; // the program's groups under the key set held (every_key: as if every offset had a key)
     // option zenc_head = 1: the zero-encryptions at the start of a plan's run() transform only u (plan_zero_encrypt).  Every limb equals
@@ -352,6 +356,7 @@ class HEVM {
     int64_t n_keyswitch = 0, n_ntt = 0;
     int64_t n_hops = 0, n_decomp = 0; // hevm_last_run_hoist_stats
     int64_t n_fold = 0;               // hevm_last_run_fold_rescale_stats
+    int64_t n_add_folds = 0;          // hevm_last_run_add_fold_stats
     int64_t n_relin_groups = 0, n_relin_products = 0; // hevm_last_run_relin_stats
     int64_t n_flat_groups = 0, n_flat_members = 0, n_flat_hops = 0; // hevm_last_run_flatten_stats
     double t_bootstrap = 0.0; // host wall time spent inside opcode 10

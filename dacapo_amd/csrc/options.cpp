@@ -43,6 +43,7 @@ static const OptDef kDefs[OPT_COUNT] = {
     { "ks_fold_rescale", 0 },
     { "ks_lazy_relin", 0 },
     { "ks_flatten_sums", 0 },
+    { "ks_fold_add", 1 }, // measured: profiles/ks_fold_add_ab.txt
     { "zenc_head", 1 },
     { "seal_compr", 0 },
     { "trace", 0 },

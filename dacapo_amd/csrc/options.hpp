@@ -44,6 +44,7 @@ enum Opt : int {
     OPT_KS_FOLD_RESCALE,   // SEAL-layout keys: a ct x ct multiply whose value only a rescale reads runs with that rescale as ONE five-launch sequence -- one exact pass divides by P q_{l-1} (fused_ks.hip f_dr2_icols_lift_fcols_kernel); every limb equals the default path's (off until measured; hevm_last_run_fold_rescale_stats counts the pairs; with ks_special > 1 it aborts)
     OPT_KS_LAZY_RELIN,     // SEAL-layout keys: ct x ct products whose single-use results are only added / negated together (plan_relin.hpp: a tree of addcc / negate over mulcc leaves at one level) are relinearised by ONE key switch of the summed three-part ciphertext (batch_ops.hip b_mul_sum_relin) (changes the rounding: off; hevm_plan_relin_groups names the groups, hevm_last_run_relin_stats counts them; with ks_special > 1 it aborts)
     OPT_KS_FLATTEN_SUMS,   // SEAL-layout keys, with ks_hoist and ks_lazy_sum: rotate-and-add chains y' = y + rotate(y, o) run as ONE hoisted lazy sum with an addend per stage of up to this many hops (2 .. 6; plan_flatten.hpp: 2^h - 1 rotations of the stage's first y by the subset sums of its offsets, plus that y; hoist_ks.hip f_ks_gsum_kernel ADDEND); a stage whose composite offsets lack a key runs as written -- hevm_flatten_offsets lists them for hevm_add_rotation_keys (changes the rounding: 0 = off; hevm_plan_flatten_groups names the groups, hevm_last_run_flatten_stats counts them; without ks_hoist and ks_lazy_sum, or with ks_special > 1, it aborts; plan = 0 ignores it)
+    OPT_KS_FOLD_ADD,       // SEAL-layout keys, the default rotation path: a two-term sum y + rotate(x, o) whose rotated term nothing else reads is no step of its own -- the rotation's last hop takes y as its addend, a start value of the fused middle's accumulators (fused_ks.hip f_ks_frows_mac_kernel; plan_exec.hip section 3a states the rule), and writes the sum itself: one dependent launch and one wave fewer per stage of a reduction tree, every limb the same (1 = on; measured: profiles/ks_fold_add_ab.txt; hevm_last_run_add_fold_stats counts the folds; 0: the plan without them)
     OPT_ZENC_HEAD,         // plan mode, the zero-encryptions made at the start of run(): 1 transforms only u -- the public key's product and the noise ride on the divide-and-round (hevm_vm.hip plan_zero_encrypt: 3l + 3 transforms per item at target level l); 0 the encryption as Encryptor::encrypt does it, batched (5l + 5).  Every limb is the same
     OPT_SEAL_COMPR,        // compression of written .seal files: 0 none, 1 zlib, 2 zstd
     OPT_TRACE,             // plan statistics on stderr (2: per wave)

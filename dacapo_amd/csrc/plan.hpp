@@ -25,6 +25,11 @@ struct KsItem {   // one key-switch hop of a rotation: dst = apply_galois(src)
     // double hoisting (option hyb_double_hoist; items of a lazy sum only): the plaintext that multiplies this rotation's result before it joins
     // the sum -- its limbs over the data primes [level][N] and over the special primes [ksp][N] (both NTT form) -- or null
     const u64 *plain = nullptr, *plain_sp = nullptr;
+    // option ks_fold_add (dc_ct_rotate_hop_add): dst = apply_galois(src) + add, add a ciphertext at the hop's level that the fused middle puts
+    // into its accumulators' start values (fused_ks.hip f_ks_frows_mac_kernel) -- exact, no launch of its own; p == nullptr: no addend.  It may
+    // be src or dst.  Only b_rotate_hops on SEAL-layout keys with the fused middle reads it (it aborts where the middle is not fused); the
+    // grouped-digit, hoisted and lazy-sum kernels ignore it
+    CtView add = CtView{ nullptr, 0 };
 };
 struct MulItem {  // dst = relinearize(a * b)
     CtView a, b, dst;
@@ -126,7 +131,9 @@ struct BatchWs {
 };
 
 // `unique`: grouped-digit mode only -- the number of distinct decompositions the items' `slot` fields name (0: every item its own)
-void b_rotate_hops(Context &c, const BatchWs &w, const KsItem *d_items, int B, int ell, hipStream_t s, const Handoff &h = Handoff{}, int unique = 0);
+// `addend`: some item carries one (KsItem::add); aborts unless the batch runs the fused middle on SEAL-layout keys, which alone adds it
+void b_rotate_hops(Context &c, const BatchWs &w, const KsItem *d_items, int B, int ell, hipStream_t s, const Handoff &h = Handoff{}, int unique = 0,
+                   bool addend = false);
 void b_mul_relin(Context &c, const BatchWs &w, const MulItem *d_items, const u64 *relin_key, int B, int ell, hipStream_t s,
                  const Handoff &h = Handoff{});
 // a multiply and the rescale that alone reads it as ONE five-launch sequence (SEAL-layout keys, the latency-shaped launch forms only:

@@ -642,15 +642,62 @@ void HEVM::build_plan()
 
     // ---- 3. dataflow depth ------------------------------------------------------------------------------------------
     int max_wave = 0;
-    for (Pop &p : O) {
-        if (p.dead) continue;
-        int w = 0;
-        for (int s : p.srcs) {
-            const int dp = V[(size_t)s].def_pop;
-            if (dp >= 0) w = std::max(w, O[(size_t)dp].wave);
+    auto asap_waves = [&]() {
+        max_wave = 0;
+        for (Pop &p : O) {
+            if (p.dead) continue;
+            int w = 0;
+            for (int s : p.srcs) {
+                const int dp = V[(size_t)s].def_pop;
+                if (dp >= 0) w = std::max(w, O[(size_t)dp].wave);
+            }
+            p.wave = w + 1;
+            max_wave = std::max(max_wave, p.wave);
         }
-        p.wave = w + 1;
-        max_wave = std::max(max_wave, p.wave);
+    };
+    asap_waves();
+    // ---- 3a. rotate-and-add (option ks_fold_add; SEAL-layout keys, the fused middle) ------------------------------------------------------
+    // y' = y + rotate(y, o), the stage of a reduction tree: the sum has two readers (the next stage's rotation and its add), so it folds into
+    // neither and would be a step of its own, one wave and one dependent launch behind the key switch.  Instead the rotation's LAST hop takes
+    // the other term as its addend (plan.hpp KsItem::add: a start value of the fused middle's accumulators, exact) and writes the sum's value
+    // itself.  The rule sees what sections 1a ... 2b left: a live two-term sum without plaintexts; one term the single-use, unpinned result (no
+    // view of it) of a default rotation hop (not hoisted, not the boot context's, no member of a lazy sum) that ends a rotate instruction at
+    // the sum's level; the other term complete before that hop starts in the ASAP levelling above -- a rotation never waits for its addend,
+    // and two rotations of one wave that are added together keep their shared batch -- and made by an earlier pseudo-op (the list stays in
+    // dataflow order).  The sum's level and scale stay as the walk fixed them.  The addend is the hop's second source from here on: waves,
+    // lifetimes and the steps' read sets count it like the first.
+    if (ks_fold_add && !c.hybrid() && option(OPT_KS_FUSE_MAC) != 0) {
+        std::vector<int> asap(O.size(), 0); // (the unfolded plan's waves: a fold below must not change what a later one compares)
+        for (size_t i = 0; i < O.size(); i++) asap[i] = O[i].wave;
+        std::set<int> folded; // the sums' values that a rotation defines now
+        for (size_t si = 0; si < O.size(); si++) {
+            Pop &s = O[si];
+            if (s.dead || s.kind != P_SUM || s.srcs.size() != 2) continue;
+            if (std::any_of(s.src_plain.begin(), s.src_plain.end(), [](int pl) { return pl >= 0; })) continue;
+            // (the middle stays one launch for every batch a step of this level can hold: batch_ops.hip b_ks_tail's split)
+            if ((long long)(N >> 10) * (long long)step_chunk(P_ROT) * S * s.level * s.level >= option(OPT_KS_FUSE_MAC_TILES)) continue;
+            for (size_t w = 0; w < 2; w++) {
+                const int hv = s.srcs[w], a = s.srcs[1 - w], hi = own_pop(hv);
+                if (hi < 0 || a == hv) continue;
+                Pop &h = O[(size_t)hi];
+                if (h.kind != P_ROT || h.rot != 1 || h.target_level != 0 || !h.direct || h.op < 0 || h.addend >= 0 || h.level != s.level) continue;
+                if (V[(size_t)hv].uses != 1 || V[(size_t)hv].pinned || V[(size_t)s.dst].root != s.dst) continue;
+                // (the pop behind the addend: a sum folded above stands for the value it defined, with the wave it had)
+                const int ar = V[(size_t)a].root, ap = V[(size_t)ar].def_pop;
+                const int aw = ap < 0 ? 0 : folded.count(ar) ? asap[(size_t)ap] + 1 : asap[(size_t)ap];
+                if (ap >= 0 && (ap >= hi || O[(size_t)ap].dead || aw >= asap[(size_t)hi])) continue;
+                h.dst = s.dst, h.addend = a, h.srcs.push_back(a);
+                V[(size_t)s.dst].def_pop = hi;
+                V[(size_t)hv].uses = 0, V[(size_t)hv].def_pop = -1; // (no pop defines or reads this value any more)
+                s.dead = true;
+                folded.insert(s.dst);
+                P.n_add_folds++;
+                break;
+            }
+        }
+        for (Val &v : V) // a view of such a sum follows its buffer to the pop that writes it now
+            if (folded.count(v.root)) v.def_pop = V[(size_t)v.root].def_pop;
+        if (P.n_add_folds) asap_waves();
     }
     // ---- 3b. slack-aware levelling (option plan_level = 1; plan_levels.hpp): an operation off the longest chain waits, inside its window
     // [ASAP, ALAP], for a wave that already holds a step of its bucket.  Sections 4 ... 5 below work on the new waves as they are: a step is
@@ -957,6 +1004,8 @@ void HEVM::build_plan()
                         if (hoisted && !slot_of.count(sv.p)) sources.push_back(KsItem{ sv, sv, nullptr, 1u, 0 });
                         const u32 slot = (c.hybrid() || hoisted) ? slot_of.emplace(sv.p, (u32)slot_of.size()).first->second : 0u;
                         h_ks.push_back(KsItem{ sv, plan_view(O[(size_t)pi].dst, q), O[(size_t)pi].key, O[(size_t)pi].elt, slot });
+                        // (option ks_fold_add: the hop also adds this value, per stream like src and dst; items with and without one share a step)
+                        if (O[(size_t)pi].addend >= 0) h_ks.back().add = plan_view(O[(size_t)pi].addend, q), st.addend = true;
                     }
                 st.unique = (int)slot_of.size();
                 st.gfirst = (int)h_ks.size(), st.gcount = (int)sources.size();
@@ -1205,7 +1254,7 @@ void HEVM::build_plan()
         }
         if (aux_waves && !aux_stream) DC_HIP_CHECK(hipStreamCreateWithFlags(&aux_stream, hipStreamNonBlocking));
     }
-    P.n_keyswitch *= S, P.n_ntt *= S;
+    P.n_keyswitch *= S, P.n_ntt *= S, P.n_add_folds *= S;
     P.ready = true;
     if (plan_graph) capture_plan(); // part of the (untimed) preparation, like the plan itself
     if (option(OPT_TRACE)) report_plan(sum_stat, max_wave, levels_moved);
@@ -1445,6 +1494,10 @@ void HEVM::report_plan(const double (&sum_stat)[5], int max_wave, int levels_mov
                 plan_level, levels_moved, P.steps.size(), max_wave, multi, P.n_fused, launches - P.n_fused, P.max_live, P.pool.size(),
                 (double)P.pool.size() * buf_elems * (double)streams * 8 / 1e9);
     }
+    // (option ks_fold_add; no line without a fold, so that the option's 0 prints the plan as it was before the option existed)
+    if (P.n_add_folds)
+        fprintf(stderr, "[dacapo_amd] plan folds: %lld two-term sums ride on their rotation's last hop as its addend (option ks_fold_add)\n",
+                (long long)P.n_add_folds);
 }
 
 // the launches of one step, on stream q, with the scratch of the step's lane
@@ -1459,7 +1512,7 @@ void HEVM::issue_step(const Step &st, hipStream_t q)
             hoist_rotate_hops(c, w, P.d_ks + st.first, P.d_ks + st.gfirst, st.count, st.unique, st.level, q);
             break;
         }
-        b_rotate_hops(st.target < 0 ? *bctx : c, w, P.d_ks + st.first, st.count, st.level, q, st.h, st.unique); break;
+        b_rotate_hops(st.target < 0 ? *bctx : c, w, P.d_ks + st.first, st.count, st.level, q, st.h, st.unique, st.addend); break;
     case P_ROTSUM:
         if (!c.hybrid()) { // option ks_lazy_sum: st.gcount sums of st.count members over st.unique decompositions
             hoist_rotate_sum(c, w, P.d_ks + st.first, P.d_ks + st.gfirst + st.gcount, st.count, st.unique, P.d_ks + st.gfirst, st.gcount, st.level, q,
@@ -1722,6 +1775,7 @@ void HEVM::run_plan()
     n_keyswitch = P.n_keyswitch, n_ntt = P.n_ntt;
     n_hops = P.n_hops, n_decomp = P.n_decomp, n_fold = P.n_fold;
     n_relin_groups = P.n_relin_groups, n_relin_products = P.n_relin_products;
+    n_add_folds = P.n_add_folds;
     n_flat_groups = P.n_flat_groups, n_flat_members = P.n_flat_members, n_flat_hops = P.n_flat_hops;
     t_bootstrap = 0.0;
     const long ps = (long)c.K * (long)c.N;

@@ -81,6 +81,7 @@ def _bind(path):
         L.dc_ct_relin.argtypes = [vp, u64p, lng, u64p, lng, u64p, i32, vp]
         L.dc_ct_mul_sum_relin.argtypes = [vp, u64p, lng, vp, vp, vp, i32, lng, u64p, i32, vp]
         L.dc_ct_rotate_hop.argtypes = [vp, u64p, lng, u64p, lng, C.c_uint32, u64p, i32, vp]
+        L.dc_ct_rotate_hop_add.argtypes = [vp, u64p, lng, u64p, lng, u64p, lng, C.c_uint32, u64p, i32, vp]
         L.dc_ct_rotate_hoisted.argtypes = [vp, vp, lng, u64p, lng, vp, vp, i32, i32, vp]
         L.dc_ct_rotate_sum_hoisted.argtypes = [vp, u64p, lng, vp, lng, vp, vp, vp, vp, i32, i32, vp]
         L.dc_ct_rotate_sum_hoisted_add.argtypes = [vp, u64p, lng, u64p, lng, vp, lng, vp, vp, vp, vp, i32, i32, vp]

@@ -113,6 +113,8 @@ def bind_vm_lib(path):
     L.hevm_plan_flatten_groups.restype = ctypes.c_int64
     L.hevm_last_run_flatten_stats.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_int64)] * 3
     L.hevm_last_run_flatten_stats.restype = None
+    L.hevm_last_run_add_fold_stats.argtypes = [ctypes.c_void_p]
+    L.hevm_last_run_add_fold_stats.restype = ctypes.c_int64
     L.hevm_set_streams.argtypes = [ctypes.c_void_p, ctypes.c_int]
     L.hevm_select_stream.argtypes = [ctypes.c_void_p, ctypes.c_int]
     # all streams' inputs / results at once; the value pointers are host or device addresses (last argument: 0 / 1)
@@ -545,6 +547,7 @@ class HEVM:
         ks, ntt = ctypes.c_int64(), ctypes.c_int64()
         self.lw.hevm_last_run_stats(self.vm, counts, ctypes.byref(ks), ctypes.byref(ntt))
         return {"op_counts": list(counts), "keyswitches": ks.value, "ntts": ntt.value,
+                "add_folds": int(self.lw.hevm_last_run_add_fold_stats(self.vm)),  # option ks_fold_add: sums computed inside a rotation's last hop
                 "bootstrap_s": float(self.lw.hevm_last_run_bootstrap_seconds(self.vm))}
 
     def printer(self, latency, rms, mem_usage=0.0):  # runner.py:256-271

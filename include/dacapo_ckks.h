@@ -128,6 +128,14 @@ void dc_ct_mul_relin_rescale(dc_context *ctx, uint64_t *dst, long dst_stride, co
 /* Evaluator::apply_galois_inplace: one hop of Evaluator::rotate_vector   SEAL_HEVM.cpp:273 */
 void dc_ct_rotate_hop(dc_context *ctx, uint64_t *dst, long dst_stride, const uint64_t *src, long src_stride,
                       uint32_t galois_elt, const uint64_t *galois_key, int ell, void *stream);
+/* EXTENSION: dc_ct_rotate_hop plus one addend -- dst = apply_galois(src) + addend, the addend (a ciphertext of ell limbs, NTT form) added
+ * EXACTLY and with no launch of its own: it enters the key switch's accumulators of the data primes as P . addend, which the division by P
+ * returns unchanged, so every limb equals Oracle.add(Oracle.apply_galois(src, elt), addend).  addend may be src or dst (it is read before dst
+ * is written); dst must not be src.  SEAL-layout contexts only (a grouped-digit context aborts with a message), and only where the key
+ * switch's middle is one launch (options ks_fuse_mac, ks_fuse_mac_tiles: otherwise the call aborts with a message).  y' = y + rotate(y, o)
+ * is one such call (option ks_fold_add). */
+void dc_ct_rotate_hop_add(dc_context *ctx, uint64_t *dst, long dst_stride, const uint64_t *src, long src_stride, const uint64_t *addend,
+                          long addend_stride, uint32_t galois_elt, const uint64_t *galois_key, int ell, void *stream);
 /* EXTENSION (not SEAL's rounding): `count` hops of ONE source ciphertext sharing one decomposition -- the digits of c1 are taken before the
  * automorphism (inverse NTT, every digit lifted to every modulus, forward NTT: once per call) and each hop reads them through its Galois
  * permutation: oracle orc_rotate_ks_hybrid at one special prime / one prime per digit, limb for limb, for every count.  dsts / elts / keys:

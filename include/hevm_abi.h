@@ -135,6 +135,11 @@ void hevm_last_run_hoist_stats(void *vm, int64_t *hops, int64_t *decompositions)
  * executed as ONE merged step, the rescale folded into the multiply's key switch.  Every limb equals the default
  * path's; hevm_last_run_stats still counts a merged pair as one multiply and one rescale.  0 with the option off and under option "plan" = 0. */
 void hevm_last_run_fold_rescale_stats(void *vm, int64_t *pairs);
+/* option "ks_fold_add" (SEAL-layout keys, on by default): the two-term sums y + rotate(x, o) that the last run()'s plan computed inside the
+ * rotation's last key-switch hop -- y enters the fused middle's accumulators as P . y, which the division by P returns unchanged -- instead of
+ * as a step of their own, every stream counted.  Every limb equals the default path's; hevm_last_run_stats counts the rotation and the addcc
+ * as before.  0 with the option off, under option "plan" = 0, with grouped digits, "ks_hoist" or "ks_fuse_mac" = 0. */
+int64_t hevm_last_run_add_fold_stats(void *vm);
 /* options "hyb_lazy_sum" (grouped-digit mode) / "ks_lazy_sum" (SEAL-layout keys, with "ks_hoist"; both off by default): the rotate instructions
  * the last run()'s plan executed as lazy sums -- the accumulators of a group's key switches added in the raised basis, ONE division by P per
  * group.  The form is the same in both modes.  out = [n_0, op ...,
@@ -219,7 +224,7 @@ void hevm_load_ctxt(void *vm, int64_t reg, const char *path);
 
 /* Run-time options (dacapo_amd/csrc/options.hpp holds the ONE table: names, defaults, meaning).  VM options -- "logn", "primes",
  * "prime_bits", "ks_special", "ks_alpha", "secret_hw", "rot_compose", "plan", "plan_graph", "plan_lanes", "max_batch", "chain_fusion", "host_encoder",
- * "online_encode", "fold_rescale_boot", "ks_lazy_relin", "ks_flatten_sums", "zenc_head", "hyb_mfma", "hyb_fuse", "seal_compr", "trace", "step_profile" -- are read when a VM (or kernel-level
+ * "online_encode", "fold_rescale_boot", "ks_lazy_relin", "ks_flatten_sums", "ks_fold_add", "zenc_head", "hyb_mfma", "hyb_fuse", "seal_compr", "trace", "step_profile" -- are read when a VM (or kernel-level
  * context) is created; launch-shape thresholds -- "small_tile_wgs", "tiny_tile_wgs", "ntt_full_min_limbs", ... -- at every launch.
  * Process-wide, not thread-safe (like the rest of this ABI).  An unknown name aborts with the list of names.  A caller that only knows
  * the reference's 18 symbols sets the same names through the single environment variable DACAPO_HEVM_OPTIONS="name=value,...". */

@@ -260,6 +260,7 @@ rows.append(f"| `plan_levels_ab.txt` | slack-aware levelling of the plan and the
 rows.append(f"| `plan_builder_refactor.txt` | the plan builder's refactor (one owner for a plan's device memory, each rule once, four leaf blocks out of `build_plan`), parent commit against branch: the plan traces of the headline program and of a convolution-shaped program under ten option sets, byte for byte: {first_lines('plan_builder_refactor.txt', '^every plan|DIFFERENCES', 1)}; every kernel's listing, both builds: {first_lines('plan_builder_refactor.txt', 'kernels in 30 listings', 1)}; `bench.py` with the parent's library and the branch's alternating on one box: {first_lines('plan_builder_refactor.txt', '^parent mean', 1)}; load and first `run()` times; test counts; line counts | `python tools/legs/plan_identity.py PARENT_LIB BRANCH_LIB --out …`; `python tools/experiments/asm_compare.py PARENT_DIR BRANCH_DIR`; `DACAPO_AMD_LIB=… python bench.py --gpus 1 --steps 40 --warmup 5 --no-cpu-baseline` |")
 rows.append(f"| `io_batch_ab.txt` | all streams' inputs and results at once (`hevm_encrypt_batch`, `hevm_decrypt_result_batch`) against the sequential calls, 8 streams of the headline fixture at N = 2^15 / 14 primes, one process, forms alternating, from host and from device memory, with `hevm_last_io_stats`: {first_lines('io_batch_ab.txt', 'one setInputs, host', 1)} | `python tools/legs/io_batch_ab.py --out profiles/io_batch_ab.txt` |")
 rows.append("| `ks_flatten_ab.txt` | flattened rotate-and-add chains (option `ks_flatten_sums`, `dc_ct_rotate_sum_hoisted_add`): `run()` of the headline on alternating VMs, option off / on / off with `ks_hoist` = 1 and `ks_lazy_sum` = 2 in every arm, f = 2, 3, 4, 6 at 1 and 8 streams, a default-options VM beside them: ms per run with the off/off spread, the plan's report (pseudo-ops, steps, waves, launches), key switches, groups / members / hops absorbed, composite keys added and their HBM, rms against the torch logits; the benchmark line of the parent commit's tree and library on the same box; a kernel trace of one VM at the best f and of one with the option off (`f_ks_gsum_kernel` against the hop kernels it replaced) | `python tools/legs/ks_flatten_ab.py --out profiles/ks_flatten_ab.txt`; `rocprofv3 --kernel-trace --stats -- python tools/legs/ks_flatten_ab.py --trace-f F` |")
+rows.append(f"| `ks_fold_add_ab.txt` | rotate-and-add on the default path (option `ks_fold_add`, `dc_ct_rotate_hop_add`): the parent commit's kernel trace of one `run()` (every `b_sum*` kernel, the rotations' fused middle and last kernels: launches, mean and total µs) as the gate; the headline plan's report under the option 0 and 1 (steps by kind, waves, step launches, folds, live buffers); `run()` on three VMs with the option 0, 1, 0 in one process: {first_lines('ks_fold_add_ab.txt', 'run headline 1 - 0', 1)}; `bench.py` on the parent's tree and on this one, three alternating pairs on one box; the branch's kernel trace in the same table; the compile-time VGPR / occupancy table of the `MODE == 0` instantiations of `f_ks_frows_mac_kernel`, parent against branch; the decision | `python tools/legs/ks_fold_add_ab.py --out profiles/ks_fold_add_ab.txt`; `python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline`; `rocprofv3 --kernel-trace --stats -- python3 tools/legs/headline_only.py 3`, `python tools/summarize/fold_add_trace.py <trace>`; `hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage -c fused_ks.hip` |")
 rows.append(f"| `boot_real_msg_ab.txt` | the half bootstrap for real messages (`ckks_boot.BootstrapEmitter(real_msg=True)`: one EvalMod and one SlotToCoeff chain, no new kernel or key) against the default full form: one bootstrap at N = 2^15, N = 2^17 and config 4's geometry (without and with `hyb_lazy_sum`), full / half / full in one process — ms, key switches, worst-slot and rms error; config 4 and the 526-bootstrap ResNet-20 at N = 2^15 in both forms — `run_s`, key switches, rms against torch and the plaintext evaluation, argmax, plaintext bytes: {first_lines('boot_real_msg_ab.txt', 'half / full time', 1)} | `python tools/legs/boot_demo.py 17 [5 1 14 9 8] --forms full,half,full`; `python tools/legs/resnet_real_boot.py 1 resnet20_nt16 17 1 b14 9 8 [--real-msg]`; `python tools/legs/resnet_real_boot.py 1 [--real-msg]` |")
 rows.append(noise_row())
 print("\n".join(r for r in rows if r))
