@@ -196,13 +196,25 @@ void dc_ntt_inverse(dc_context *ctx, uint64_t *data, long limb_stride, int count
     launch_ntt(*ctx->c, true, data, limb_stride, count, d_prime_idx, prime_base, prime_period, S(stream));
 }
 
-// variant 0: the two-launch tiles whatever the batch size; 1: the single-crossing kernel (N = 2^15 only; aborts otherwise)
+// does dc_ntt_variant(variant) exist on this context's ring?  (0: every ring; 1: N = 2^12 .. 2^15)
+int dc_ntt_variant_supported(const dc_context *ctx, int variant)
+{
+    return variant == 0 || (variant == 1 && (ntt_full_supported(*ctx->c) || ntt_lds_supported(*ctx->c)));
+}
+
+// variant 0: the two-launch tiles whatever the batch size; 1: the single-launch kernel of the ring -- ntt_full.hip at N = 2^15, ntt_lds.hip at
+// N = 2^12 .. 2^14; aborts on the other rings (dc_ntt_variant_supported asks first)
 void dc_ntt_variant(dc_context *ctx, int variant, int inverse, uint64_t *data, long limb_stride, int count, const int32_t *d_prime_idx,
                     int prime_base, int prime_period, void *stream)
 {
     if (variant == 1) {
+        if (ntt_lds_supported(*ctx->c)) {
+            launch_ntt_lds(*ctx->c, inverse != 0, data, limb_stride, count, d_prime_idx, prime_base, prime_period, S(stream));
+            return;
+        }
         if (!ntt_full_supported(*ctx->c)) {
-            fprintf(stderr, "[dacapo_amd] dc_ntt_variant: the single-crossing transform exists for N = 2^15 only\n");
+            fprintf(stderr, "[dacapo_amd] dc_ntt_variant: the single-launch transform exists for N = 2^12 .. 2^15 only (this ring: 2^%d)\n",
+                    ctx->c->logN);
             abort();
         }
         launch_ntt_full(*ctx->c, inverse != 0, data, limb_stride, count, d_prime_idx, prime_base, prime_period, S(stream));

@@ -1523,7 +1523,9 @@ struct IoTabLayout {
         return off;
     }
 };
-int ntt_launches(const Context &c, bool inverse, int limbs) { return ntt_full_supported(c) && ntt_full_pays(inverse, limbs) ? 1 : 2; }
+int ntt_launches(const Context &c, bool inverse, int limbs) {
+    return (ntt_full_supported(c) && ntt_full_pays(inverse, limbs)) || (ntt_lds_supported(c) && ntt_lds_pays(inverse, limbs)) ? 1 : 2;
+}
 } // namespace
 
 // `count` calls of encrypt() on streams first_stream ... in ascending order, as one launch sequence per chunk: the device encoder on all

@@ -31,6 +31,12 @@ long ntt_full_min_limbs(bool inverse);
 bool ntt_full_pays(bool inverse, int count); // ... and the launch fills the persistent grid's last round well enough (ntt_full.hip)
 void launch_ntt_full(const Context &c, bool inverse, u64 *data, long limb_stride, int count, const int *d_prime_idx, int prime_base,
                      int prime_period, hipStream_t s);
+// single-launch transform for N = 2^12 .. 2^14 (ntt_lds.hip): one workgroup per limb, the whole limb resident in LDS between its passes.
+// launch_ntt takes it for launches of at least ntt_lds_min_limbs / ntt_lds_inv_min_limbs limbs (options; 0 = never)
+bool ntt_lds_supported(const Context &c);
+bool ntt_lds_pays(bool inverse, int count);
+void launch_ntt_lds(const Context &c, bool inverse, u64 *data, long limb_stride, int count, const int *d_prime_idx, int prime_base,
+                    int prime_period, hipStream_t s);
 
 // second (ROWS) phase of a forward NTT only: the input holds the output of a COLS phase (fused_ks.hip)
 void launch_ntt_rows_fwd(const Context &c, u64 *data, long limb_stride, int count, const int *d_prime_idx, int prime_base,

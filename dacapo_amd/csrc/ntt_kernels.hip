@@ -101,6 +101,8 @@ void launch_ntt(const Context &c, bool inverse, u64 *data, long limb_stride, int
 {
     if (ntt_full_supported(c) && ntt_full_pays(inverse, count))
         launch_ntt_full(c, inverse, data, limb_stride, count, d_prime_idx, prime_base, prime_period, s);
+    else if (ntt_lds_supported(c) && ntt_lds_pays(inverse, count))
+        launch_ntt_lds(c, inverse, data, limb_stride, count, d_prime_idx, prime_base, prime_period, s);
     else
         launch_ntt_two_phase(c, inverse, data, limb_stride, count, d_prime_idx, prime_base, prime_period, s);
 }

@@ -58,6 +58,8 @@ static const OptDef kDefs[OPT_COUNT] = {
     { "ntt_full_inv_persist", -1 },
     { "ntt_full_pairs", 1 },
     { "ntt_full_inv_pairs", 1 },
+    { "ntt_lds_min_limbs", 0 }, // measured: profiles/ntt_lds_ab.txt
+    { "ntt_lds_inv_min_limbs", 0 },
     { "cols_pairs", 1 },
     { "ks_merge_special_min_wgs", 2048 },
     { "ks_merge_lift_min_wgs", 1024 },

@@ -60,6 +60,8 @@ enum Opt : int {
     OPT_NTT_FULL_INV_PERSIST,    // ... inverse (-1: same as forward)
     OPT_NTT_FULL_PAIRS,          // twiddle pairs in its forward passes A and B
     OPT_NTT_FULL_INV_PAIRS,      // twiddle pairs in its inverse passes B and A
+    OPT_NTT_LDS_MIN_LIMBS,       // N = 2^12 .. 2^14: forward launches of at least this many limbs take the single-launch LDS-resident kernel (ntt_lds.hip; 0 = never)
+    OPT_NTT_LDS_INV_MIN_LIMBS,   // ... inverse launches
     OPT_COLS_PAIRS,              // twiddle pairs in the forward COLS tiles of the fused key-switch / rescale phases (60-bit build)
     OPT_KS_MERGE_SPECIAL_MIN_WGS, // fused key-switch middle: one workgroup row for both special-prime accumulators from this many workgroups
     OPT_KS_MERGE_LIFT_MIN_WGS,   // L2 / L6: share the inverse phase among a source limb's targets while this many workgroups remain

@@ -71,6 +71,8 @@ def _bind(path):
         for f in (L.dc_ntt_forward, L.dc_ntt_inverse):
             f.argtypes = [vp, u64p, lng, i32, vp, i32, i32, vp]
         L.dc_ntt_variant.argtypes = [vp, i32, i32, u64p, lng, i32, vp, i32, i32, vp]
+        L.dc_ntt_variant_supported.argtypes = [vp, i32]
+        L.dc_ntt_variant_supported.restype = i32
         L.dc_ct_negate.argtypes = [vp, u64p, lng, u64p, lng, i32, vp]
         L.dc_ct_add.argtypes = [vp, u64p, lng, u64p, lng, u64p, lng, i32, vp]
         L.dc_ct_add_plain.argtypes = [vp, u64p, lng, u64p, lng, u64p, i32, vp]
@@ -211,13 +213,18 @@ class Context:
 
     def ntt(self, buf: DeviceBuffer, count, inverse=False, prime_idx: DeviceBuffer | None = None, prime_base=0,
             prime_period=0, limb_stride=None, offset=0, stream=None, variant=None):
-        """variant None: the library chooses by batch size; 0 / 1: the two-launch tiles / the single-crossing kernel (dc_ntt_variant)"""
+        """variant None: the library chooses by batch size; 0 / 1: the two-launch tiles / the ring's single-launch kernel (dc_ntt_variant:
+        N = 2^12 .. 2^15; ntt_variant_supported asks)"""
         args = (buf.at(offset), self.N if limb_stride is None else limb_stride, count,
                 prime_idx.ptr if prime_idx is not None else None, prime_base, prime_period, stream)
         if variant is None:
             (self.L.dc_ntt_inverse if inverse else self.L.dc_ntt_forward)(self.h, *args)
         else:
             self.L.dc_ntt_variant(self.h, variant, int(inverse), *args)
+
+    def ntt_variant_supported(self, variant: int) -> bool:
+        """does ntt(variant=...) exist on this ring?  (dc_ntt_variant aborts the process where it does not)"""
+        return bool(self.L.dc_ntt_variant_supported(self.h, int(variant)))
 
     def mul_sum_relin(self, dst: int, dst_stride: int, a_ptrs, b_ptrs, signs, src_stride: int, relin_key: int, ell: int, stream=None):
         """dc_ct_mul_sum_relin: dst = relin(sum_k signs[k] a_k (x) b_k) with one key switch; a_ptrs / b_ptrs are device pointers (ints)"""

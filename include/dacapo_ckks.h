@@ -77,10 +77,13 @@ void dc_ntt_inverse(dc_context *ctx, uint64_t *data, long limb_stride, int count
                     int prime_period, void *stream);
 
 /* The same transform with the implementation named (tests and bench.py compare them; dc_ntt_forward/inverse choose by batch size):
- * variant 0 = two launches per transform (ntt_tile.hpp), 1 = one 1024-thread workgroup per limb, one HBM crossing (ntt_full.hip,
- * N = 2^15 only). */
+ * variant 0 = two launches per transform (ntt_tile.hpp), 1 = one launch, one workgroup per limb, one HBM crossing: at N = 2^15 1024
+ * threads with the limb in registers (ntt_full.hip), at N = 2^12 .. 2^14 the whole limb resident in LDS (ntt_lds.hip).  Variant 1 aborts
+ * on the other rings (2^16, 2^17): ask dc_ntt_variant_supported first. */
 void dc_ntt_variant(dc_context *ctx, int variant, int inverse, uint64_t *data, long limb_stride, int count, const int32_t *d_prime_idx,
                     int prime_base, int prime_period, void *stream);
+/* 1 if dc_ntt_variant(ctx, variant, ...) exists on this context's ring, 0 otherwise (never aborts) */
+int dc_ntt_variant_supported(const dc_context *ctx, int variant);
 
 /* Evaluator::negate            SEAL_HEVM.cpp:278 */
 void dc_ct_negate(dc_context *ctx, uint64_t *dst, long dst_stride, const uint64_t *a, long a_stride, int ell, void *stream);
