@@ -95,39 +95,26 @@ __global__ __launch_bounds__(kBT) void b_ks_mac_kernel(u64 *__restrict__ acc, co
     *reinterpret_cast<u64x2 *>(ac + ((size_t)1 * (ell + 1) + m) * N + k) = o1;
 }
 
-static bool fuse_mac() { return option(OPT_KS_FUSE_MAC) != 0; }
-// work (in 1024-coefficient tiles of lifted digits) from which a key switch takes the large-batch launch sequence
-static long big_threshold() { return (long)option(OPT_KS_BIG_TILES); }
-// ... and up to which the second NTT phase, the inner products and the special prime's first inverse phase stay one launch
-// (always, by default: at N = 2^16 / 24 primes the fused launch is 17 % faster than three, at the HEVM sizes it is even)
-static long fuse_mac_threshold() { return (long)option(OPT_KS_FUSE_MAC_TILES); }
-
 // L2..L7 of the key-switch pipeline (fused_ks.hip) once the digits' inverse ROWS phase (L1) has been issued
-// (with option ks_fuse_mac_tiles set, a linked step could fall on the un-fused middle, whose last kernel has no continuation form)
-bool chain_fusion_supported() { return fuse_mac() && fuse_mac_threshold() == (1L << 40); }
-
+// `sh`: the batch's launch sequence (launch_shape.hpp), which the caller's first and last launches follow too
 // `digits`: output of the inverse ROWS phase of the key-switch target [B][l][N] (w.digits, or the buffer a fused producer filled)
 // `own`: MODE 1 only -- the target itself in NTT form [B][l][N], where the fused middle reads the digit a modulus owns (a sum of products:
 // b_mul_sum_relin); null: the fused middle recomputes a1*b1 from the MulItem table
-// `last(fused_mac)`: the launch of the last forward ROWS phase
+// `last()`: the launch of the last forward ROWS phase
 template <int MODE, class Last>
-static void b_ks_tail(Context &c, const BatchWs &w, u64 *digits, const KsItem *items, const void *final_items, const u64 *shared_key, int B,
-                      int ell, hipStream_t s, const u64 *own, Last last)
+static void b_ks_tail(Context &c, const BatchWs &w, const KsShape &sh, u64 *digits, const KsItem *items, const void *final_items,
+                      const u64 *shared_key, int B, int ell, hipStream_t s, const u64 *own, Last last)
 {
     const size_t N = c.N;
     const int K = c.K, sp = K - 1;
-    // small batches: one launch that recomputes the inverse COLS phase per target modulus (latency); large batches: run it
-    // once per limb, then a base-change + forward launch (25-35 % less work in these two steps)
-    const long tiles = (long)(N >> 10) * B * ell * ell;
-    const bool big = tiles >= big_threshold(), fused_mac = fuse_mac() && tiles < fuse_mac_threshold();
-    if (big) {
+    if (sh.big) {
         launch_ntt_cols_inv(c, digits, (long)N, B * ell, nullptr, 0, ell, s);
         f_ks_lift_fcols(c, digits, w.ext, B, ell, s);
     } else
         f_ks_icols_lift_fcols(c, digits, w.ext, B, ell, s);
     u64 *acc_last = w.acc + (size_t)ell * N;
     const long acc_ps = (long)(ell + 1) * (long)N;
-    if (!fused_mac) {
+    if (!sh.fused_mac) {
         launch_ntt_rows_fwd(c, w.ext, (long)N, B * ell * ell, c.ks_prime_idx(ell), 0, ell * ell, s);
         DC_LAUNCH(b_ks_mac_kernel<MODE>, dim3((unsigned)(N / (2 * kBT)), ell + 1, B), dim3(kBT), 0, s, w.acc, w.ext, w.target, items,
                            shared_key, ell, K, N, c.logN, c.d_mods);
@@ -135,28 +122,28 @@ static void b_ks_tail(Context &c, const BatchWs &w, u64 *digits, const KsItem *i
     } else // MODE 1: the operand a1*b1 is recomputed from the MulItem table (no tensor launch, see b_mul_relin)
         f_ks_frows_mac(c, MODE, w.ext, MODE == 1 ? own : w.target, MODE == 1 ? reinterpret_cast<const KsItem *>(final_items) : items,
                        shared_key, w.acc, B, ell, s, MODE == 0);
-    if (big) {
+    if (sh.big) {
         launch_ntt_cols_inv(c, acc_last, acc_ps, 2 * B, nullptr, sp, 1, s);
         f_dr_lift_fcols(c, acc_last, acc_ps, w.tmp, 2 * B, ell, sp, s);
     } else
         f_dr_icols_lift_fcols(c, acc_last, acc_ps, w.tmp, 2 * B, ell, sp, s);
-    last(fused_mac);
+    last();
 }
 // ... with the last kernel of a rotation / a multiply (f_frows_final modes 0 / 1 / 4)
 template <int MODE>
-static void b_ks_tail(Context &c, const BatchWs &w, u64 *digits, const KsItem *items, const void *final_items, const u64 *shared_key, int B,
-                      int ell, hipStream_t s, const Handoff &h)
+static void b_ks_tail(Context &c, const BatchWs &w, const KsShape &sh, u64 *digits, const KsItem *items, const void *final_items,
+                      const u64 *shared_key, int B, int ell, hipStream_t s, const Handoff &h)
 {
-    b_ks_tail<MODE>(c, w, digits, items, final_items, shared_key, B, ell, s, nullptr, [&](bool fused_mac) {
-        f_frows_final(c, (MODE == 1 && fused_mac) ? 4 : MODE, w.tmp, final_items, w.acc, 2 * B, ell, c.K - 1, s, RsItem{}, nullptr, nullptr, h,
-                      MODE == 0 && fused_mac); // (a rotation's base term was folded into the fused middle's accumulators)
+    b_ks_tail<MODE>(c, w, sh, digits, items, final_items, shared_key, B, ell, s, nullptr, [&] {
+        f_frows_final(c, (MODE == 1 && sh.fused_mac) ? 4 : MODE, w.tmp, final_items, w.acc, 2 * B, ell, c.K - 1, s, RsItem{}, nullptr, nullptr, h,
+                      MODE == 0 && sh.fused_mac); // (a rotation's base term was folded into the fused middle's accumulators)
     });
 }
 
 void b_rotate_hops(Context &c, const BatchWs &w, const KsItem *d_items, int B, int ell, hipStream_t s, const Handoff &h, int unique, bool addend)
 {
-    // an item's addend (KsItem::add) is a start value of the fused middle's accumulators and of nothing else: same split as b_ks_tail
-    if (addend && (c.hybrid() || !fuse_mac() || (long)(c.N >> 10) * B * ell * ell >= fuse_mac_threshold())) {
+    const KsShape sh = ks_shape(c, B, ell);
+    if (addend && !sh.carries_addend()) {
         fprintf(stderr, "[dacapo_amd] b_rotate_hops: an item carries an addend, which only the fused middle of SEAL-layout key switching adds "
                         "(%s)\n", c.hybrid() ? "this context switches keys with grouped digits" : "option ks_fuse_mac = 0, or the batch is above ks_fuse_mac_tiles");
         abort();
@@ -166,7 +153,7 @@ void b_rotate_hops(Context &c, const BatchWs &w, const KsItem *d_items, int B, i
         return;
     }
     f_irows_rot_c1(c, d_items, ell, w.digits, B, s);
-    b_ks_tail<0>(c, w, w.digits, d_items, d_items, nullptr, B, ell, s, h);
+    b_ks_tail<0>(c, w, sh, w.digits, d_items, d_items, nullptr, B, ell, s, h);
 }
 
 void b_mul_relin(Context &c, const BatchWs &w, const MulItem *d_items, const u64 *relin_key, int B, int ell, hipStream_t s, const Handoff &h)
@@ -176,16 +163,16 @@ void b_mul_relin(Context &c, const BatchWs &w, const MulItem *d_items, const u64
         return;
     }
     const size_t N = c.N;
-    const bool fused_mac = fuse_mac() && (long)(N >> 10) * B * ell * ell < fuse_mac_threshold(); // same split as b_ks_tail
+    const KsShape sh = ks_shape(c, B, ell);
     u64 *digits = w.digits;
-    if (h.in) // a fused producer already ran the inverse ROWS phase of a1*b1 (the plan only links steps when fuse_mac() holds)
+    if (h.in) // a fused producer already ran the inverse ROWS phase of a1*b1 (the plan only links steps when chain_fusion_supported() holds)
         digits = const_cast<u64 *>(h.in);
-    else if (!fused_mac) {
+    else if (!sh.fused_mac) {
         DC_LAUNCH(b_tensor_kernel, dim3((unsigned)(N / (2 * kBT)), ell, B), dim3(kBT), 0, s, d_items, w.target, ell, N, c.d_mods);
         f_irows_strided(c, w.target, (long)N, 0, ell, w.digits, (long)N, B * ell, s);
     } else // small batches: a1*b1 is formed in the loaders and a0*b0, a0*b1 + a1*b0 in the last kernel's epilogue
         f_irows_tensor_c2(c, d_items, ell, w.digits, B, s);
-    b_ks_tail<1>(c, w, digits, nullptr, d_items, relin_key, B, ell, s, h);
+    b_ks_tail<1>(c, w, sh, digits, nullptr, d_items, relin_key, B, ell, s, h);
 }
 
 // prologue of a product sum where the fused middle is not used: dst.c0 = sum_k s_k a_k0 b_k0, dst.c1 = sum_k s_k (a_k0 b_k1 + a_k1 b_k0),
@@ -247,32 +234,22 @@ __global__ __launch_bounds__(kBT) void b_tensor_sum_kernel(const MulSumItem *__r
 void b_mul_sum_relin(Context &c, const BatchWs &w, const MulSumItem *d_items, const MulTerm *d_terms, const u64 *relin_key, int B, int ell,
                      hipStream_t s)
 {
-    if (c.hybrid()) {
-        fprintf(stderr, "[dacapo_amd] b_mul_sum_relin: this context switches keys with grouped digits; sums of products are relinearised once on "
-                        "SEAL-layout keys only\n");
-        abort();
-    }
+    refuse_grouped_digits(c, "b_mul_sum_relin", "; sums of products are relinearised once on SEAL-layout keys only");
     const size_t N = c.N;
-    const bool fused_mac = fuse_mac() && (long)(N >> 10) * B * ell * ell < fuse_mac_threshold(); // same split as b_ks_tail
-    if (fused_mac)
+    const KsShape sh = ks_shape(c, B, ell);
+    if (sh.fused_mac)
         f_irows_tensor_sum(c, d_items, d_terms, ell, w.digits, w.target, B, s);
     else {
         DC_LAUNCH(b_tensor_sum_kernel, dim3((unsigned)(N / (2 * kBT)), ell, B), dim3(kBT), 0, s, d_items, d_terms, w.target, ell, N, c.d_mods);
         f_irows_strided(c, w.target, (long)N, 0, ell, w.digits, (long)N, B * ell, s);
     }
-    b_ks_tail<1>(c, w, w.digits, nullptr, nullptr, relin_key, B, ell, s, w.target,
-                 [&](bool fused) { f_frows_sum_final(c, w.tmp, d_items, fused ? d_terms : nullptr, w.acc, B, ell, s); });
-}
-
-bool mul_relin_rescale_fused(const Context &c, int B, int ell)
-{
-    const long tiles = (long)(c.N >> 10) * B * ell * ell; // (b_ks_tail's split: the folded form exists for its latency-shaped sequence)
-    return !c.hybrid() && ell >= 2 && fuse_mac() && tiles < fuse_mac_threshold() && tiles < big_threshold();
+    b_ks_tail<1>(c, w, sh, w.digits, nullptr, nullptr, relin_key, B, ell, s, w.target,
+                 [&] { f_frows_sum_final(c, w.tmp, d_items, sh.fused_mac ? d_terms : nullptr, w.acc, B, ell, s); });
 }
 
 void b_mul_relin_rescale(Context &c, const BatchWs &w, const MulRsItem *d_items, const u64 *relin_key, int B, int ell, hipStream_t s, const Handoff &h)
 {
-    if (!mul_relin_rescale_fused(c, B, ell)) {
+    if (!ks_shape(c, B, ell).folds_rescale()) {
         fprintf(stderr, "[dacapo_amd] b_mul_relin_rescale: no folded form for %d items at level %d under this context / these launch options "
                         "(run b_mul_relin and b_rescale)\n", B, ell);
         abort();

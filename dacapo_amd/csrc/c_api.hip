@@ -35,38 +35,38 @@ void *item_slot(dc_context *ctx, const void *host_item, size_t bytes, hipStream_
 }
 BatchWs batch_ws(const Workspace &w) { return BatchWs{ w.ct_tmp, w.ks_digits, w.ks_ext, w.ks_acc, w.ks_tmp }; }
 bool overlaps(const uint64_t *a, const uint64_t *b) { return a == b; }
+// a scratch buffer of the handle, grown on demand (growing waits for the device: hipFree)
+template <class T>
+void grow_scratch(T *&p, size_t &cap, size_t need)
+{
+    if (need <= cap) return;
+    if (p) DC_HIP_CHECK(hipFree(p));
+    p = nullptr;
+    DC_HIP_CHECK(hipMalloc(&p, need));
+    cap = need;
+}
 
-// What the two hoisted entry points share.  A context with grouped digits is refused (`grouped`: why, in the entry point's words), count and level
-// are checked, build(h) fills the host item table and returns how many decompositions need scratch in the handle; then the handle's buffers --
-// the item table, `pairs` accumulator pairs with their mod-down terms, that scratch -- are grown on demand (growing waits for the device:
-// hipFree) and the table is uploaded.  Returns the device table.
+// What the two hoisted entry points share.  A context with grouped digits is refused (`grouped`: the rest of that message, in the entry
+// point's words), count and level are checked, build(h) fills the host item table and returns how many decompositions need scratch in the
+// handle; then the handle's buffers -- the item table, `pairs` accumulator pairs with their mod-down terms, that scratch -- are grown on demand
+// and the table is uploaded.  Returns the device table.
 template <class Build>
 const KsItem *hoist_items(dc_context *ctx, const char *who, const char *grouped, const char *what, int count, int ell, size_t pairs,
                                  hipStream_t s, Build build)
 {
     Context &c = *ctx->c;
-    if (c.hybrid()) {
-        fprintf(stderr, "[dacapo_amd] %s: this context switches keys with grouped digits%s; the call is for SEAL-layout keys\n", who, grouped);
-        abort();
-    }
+    refuse_grouped_digits(c, who, grouped);
     if (count < 1 || count > 65535 || ell < 1 || ell > c.max_level()) {
         fprintf(stderr, "[dacapo_amd] %s: %d %s at level %d (1..65535 %s, level 1..%d)\n", who, count, what, ell, what, c.max_level());
         abort();
     }
-    auto grow = [](auto *&p, size_t &cap, size_t need) {
-        if (need <= cap) return;
-        if (p) DC_HIP_CHECK(hipFree(p));
-        p = nullptr;
-        DC_HIP_CHECK(hipMalloc(&p, need));
-        cap = need;
-    };
     std::vector<KsItem> h;
     const size_t U = build(h), N = c.N;
-    grow(ctx->hoist_items, ctx->hoist_item_cap, h.size() * sizeof(KsItem));
-    grow(ctx->hoist_acc, ctx->hoist_acc_cap, pairs * 2 * ((size_t)ell + 1) * N * sizeof(u64));
-    grow(ctx->hoist_tmp, ctx->hoist_tmp_cap, pairs * 2 * (size_t)ell * N * sizeof(u64));
-    grow(ctx->hoist_digits, ctx->hoist_digits_cap, U * (size_t)ell * N * sizeof(u64));
-    grow(ctx->hoist_ext, ctx->hoist_ext_cap, U * (size_t)ell * ell * N * sizeof(u64));
+    grow_scratch(ctx->hoist_items, ctx->hoist_item_cap, h.size() * sizeof(KsItem));
+    grow_scratch(ctx->hoist_acc, ctx->hoist_acc_cap, pairs * 2 * ((size_t)ell + 1) * N * sizeof(u64));
+    grow_scratch(ctx->hoist_tmp, ctx->hoist_tmp_cap, pairs * 2 * (size_t)ell * N * sizeof(u64));
+    grow_scratch(ctx->hoist_digits, ctx->hoist_digits_cap, U * (size_t)ell * N * sizeof(u64));
+    grow_scratch(ctx->hoist_ext, ctx->hoist_ext_cap, U * (size_t)ell * ell * N * sizeof(u64));
     DC_HIP_CHECK(hipMemcpyAsync(ctx->hoist_items, h.data(), h.size() * sizeof(KsItem), hipMemcpyHostToDevice, s));
     DC_HIP_CHECK(hipStreamSynchronize(s)); // (the host table goes out of scope)
     return static_cast<const KsItem *>(ctx->hoist_items);
@@ -196,30 +196,25 @@ void dc_ntt_inverse(dc_context *ctx, uint64_t *data, long limb_stride, int count
     launch_ntt(*ctx->c, true, data, limb_stride, count, d_prime_idx, prime_base, prime_period, S(stream));
 }
 
-// does dc_ntt_variant(variant) exist on this context's ring?  (0: every ring; 1: N = 2^12 .. 2^15)
+// does dc_ntt_variant(variant) exist on this context's ring?  (0: every ring; 1: where the ring has a single-launch kernel -- ntt_full.hip at
+// N = 2^15, ntt_lds.hip at N = 2^12 .. 2^14, none at 2^16 and 2^17)
 int dc_ntt_variant_supported(const dc_context *ctx, int variant)
 {
-    return variant == 0 || (variant == 1 && (ntt_full_supported(*ctx->c) || ntt_lds_supported(*ctx->c)));
+    return variant == 0 || (variant == 1 && ntt_single_launch_kind(*ctx->c) != NttKind::TwoPhase);
 }
 
-// variant 0: the two-launch tiles whatever the batch size; 1: the single-launch kernel of the ring -- ntt_full.hip at N = 2^15, ntt_lds.hip at
-// N = 2^12 .. 2^14; aborts on the other rings (dc_ntt_variant_supported asks first)
+// variant 0: the two-launch tiles whatever the batch size; 1: the single-launch kernel of the ring; aborts on a ring that has none
+// (dc_ntt_variant_supported asks first)
 void dc_ntt_variant(dc_context *ctx, int variant, int inverse, uint64_t *data, long limb_stride, int count, const int32_t *d_prime_idx,
                     int prime_base, int prime_period, void *stream)
 {
-    if (variant == 1) {
-        if (ntt_lds_supported(*ctx->c)) {
-            launch_ntt_lds(*ctx->c, inverse != 0, data, limb_stride, count, d_prime_idx, prime_base, prime_period, S(stream));
-            return;
-        }
-        if (!ntt_full_supported(*ctx->c)) {
-            fprintf(stderr, "[dacapo_amd] dc_ntt_variant: the single-launch transform exists for N = 2^12 .. 2^15 only (this ring: 2^%d)\n",
-                    ctx->c->logN);
-            abort();
-        }
-        launch_ntt_full(*ctx->c, inverse != 0, data, limb_stride, count, d_prime_idx, prime_base, prime_period, S(stream));
-    } else
-        launch_ntt_two_phase(*ctx->c, inverse != 0, data, limb_stride, count, d_prime_idx, prime_base, prime_period, S(stream));
+    const NttKind kind = variant == 1 ? ntt_single_launch_kind(*ctx->c) : NttKind::TwoPhase;
+    if (variant == 1 && kind == NttKind::TwoPhase) {
+        fprintf(stderr, "[dacapo_amd] dc_ntt_variant: the single-launch transform exists for N = 2^12 .. 2^15 only (this ring: 2^%d)\n",
+                ctx->c->logN);
+        abort();
+    }
+    launch_ntt_as(*ctx->c, kind, inverse != 0, data, limb_stride, count, d_prime_idx, prime_base, prime_period, S(stream));
 }
 
 void dc_ct_negate(dc_context *ctx, uint64_t *dst, long dst_stride, const uint64_t *a, long a_stride, int ell, void *stream)
@@ -258,11 +253,8 @@ void dc_ct_mul_relin_rescale(dc_context *ctx, uint64_t *dst, long dst_stride, co
 {
     Context &c = *ctx->c;
     hipStream_t s = S(stream);
-    if (c.hybrid()) {
-        fprintf(stderr, "[dacapo_amd] dc_ct_mul_relin_rescale: this context switches keys with grouped digits, whose mod-down is an approximate base "
-                        "conversion; the call is for SEAL-layout keys (use dc_ct_mul_relin and dc_ct_rescale)\n");
-        abort();
-    }
+    refuse_grouped_digits(c, "dc_ct_mul_relin_rescale", ", whose mod-down is an approximate base conversion; the call is for SEAL-layout keys (use "
+                                                        "dc_ct_mul_relin and dc_ct_rescale)");
     if (ell < 2 || ell > c.max_level() || ell > kConstSlotWords) {
         fprintf(stderr, "[dacapo_amd] dc_ct_mul_relin_rescale: level %d (2..%d)\n", ell, std::min(c.max_level(), kConstSlotWords));
         abort();
@@ -275,16 +267,8 @@ void dc_ct_mul_relin_rescale(dc_context *ctx, uint64_t *dst, long dst_stride, co
         DC_HIP_CHECK(hipMemcpyAsync(slot, mul_const, (size_t)ell * sizeof(u64), hipMemcpyHostToDevice, s));
         d_consts = slot;
     }
-    const bool fused = mul_relin_rescale_fused(c, 1, ell), alias = overlaps(dst, a) || overlaps(dst, b);
-    if (!fused || alias) {
-        const size_t need = (size_t)3 * ell * N * sizeof(u64);
-        if (need > ctx->fold_tmp_cap) { // (growing waits for the device: hipFree)
-            if (ctx->fold_tmp) DC_HIP_CHECK(hipFree(ctx->fold_tmp));
-            ctx->fold_tmp = nullptr;
-            DC_HIP_CHECK(hipMalloc(&ctx->fold_tmp, need));
-            ctx->fold_tmp_cap = need;
-        }
-    }
+    const bool fused = ks_shape(c, 1, ell).folds_rescale(), alias = overlaps(dst, a) || overlaps(dst, b);
+    if (!fused || alias) grow_scratch(ctx->fold_tmp, ctx->fold_tmp_cap, (size_t)3 * ell * N * sizeof(u64));
     if (fused) { // the last kernel's epilogue reads a and b where other workgroups write dst: an aliased destination is written through scratch
         const CtView out = alias ? CtView{ ctx->fold_tmp, (long)(ell - 1) * (long)N } : V(dst, dst_stride);
         MulRsItem it;
@@ -324,11 +308,7 @@ void dc_ct_mul_sum_relin(dc_context *ctx, uint64_t *dst, long dst_stride, const 
 {
     Context &c = *ctx->c;
     hipStream_t s = S(stream);
-    if (c.hybrid()) {
-        fprintf(stderr, "[dacapo_amd] dc_ct_mul_sum_relin: this context switches keys with grouped digits (ks_special > 1); the call is for "
-                        "SEAL-layout keys (use dc_ct_mul_relin and dc_ct_add)\n");
-        abort();
-    }
+    refuse_grouped_digits(c, "dc_ct_mul_sum_relin", " (ks_special > 1); the call is for SEAL-layout keys (use dc_ct_mul_relin and dc_ct_add)");
     if (count < 1 || count > kMulSumMax || ell < 1 || ell > c.max_level()) {
         fprintf(stderr, "[dacapo_amd] dc_ct_mul_sum_relin: %d products at level %d (1..%d products, level 1..%d)\n", count, ell, kMulSumMax,
                 c.max_level());
@@ -343,15 +323,8 @@ void dc_ct_mul_sum_relin(dc_context *ctx, uint64_t *dst, long dst_stride, const 
         }
         alias = alias || overlaps(dst, as[k]) || overlaps(dst, bs[k]);
     }
-    if (alias) { // the last kernel reads the operands where other workgroups write dst: such a destination is written through scratch
-        const size_t need = (size_t)2 * ell * N * sizeof(u64);
-        if (need > ctx->fold_tmp_cap) { // (growing waits for the device: hipFree)
-            if (ctx->fold_tmp) DC_HIP_CHECK(hipFree(ctx->fold_tmp));
-            ctx->fold_tmp = nullptr;
-            DC_HIP_CHECK(hipMalloc(&ctx->fold_tmp, need));
-            ctx->fold_tmp_cap = need;
-        }
-    }
+    // the last kernel reads the operands where other workgroups write dst: such a destination is written through scratch
+    if (alias) grow_scratch(ctx->fold_tmp, ctx->fold_tmp_cap, (size_t)2 * ell * N * sizeof(u64));
     const CtView out = alias ? CtView{ ctx->fold_tmp, (long)ell * (long)N } : V(dst, dst_stride);
     constexpr size_t kTermsAt = 64; // the item, then the terms
     static_assert(sizeof(MulSumItem) <= kTermsAt && kTermsAt % alignof(MulTerm) == 0, "product-sum table layout");
@@ -362,12 +335,7 @@ void dc_ct_mul_sum_relin(dc_context *ctx, uint64_t *dst, long dst_stride, const 
         const MulTerm t{ V(as[k], src_stride), V(bs[k], src_stride), (int)signs[k] };
         memcpy(h.data() + kTermsAt + (size_t)k * sizeof(MulTerm), &t, sizeof(t));
     }
-    if (h.size() > ctx->mulsum_cap) {
-        if (ctx->mulsum_table) DC_HIP_CHECK(hipFree(ctx->mulsum_table));
-        ctx->mulsum_table = nullptr;
-        DC_HIP_CHECK(hipMalloc(&ctx->mulsum_table, kTermsAt + (size_t)kMulSumMax * sizeof(MulTerm)));
-        ctx->mulsum_cap = kTermsAt + (size_t)kMulSumMax * sizeof(MulTerm);
-    }
+    grow_scratch(ctx->mulsum_table, ctx->mulsum_cap, kTermsAt + (size_t)kMulSumMax * sizeof(MulTerm)); // (once: room for the longest sum)
     DC_HIP_CHECK(hipMemcpyAsync(ctx->mulsum_table, h.data(), h.size(), hipMemcpyHostToDevice, s));
     DC_HIP_CHECK(hipStreamSynchronize(s)); // (the host table goes out of scope)
     const char *d = static_cast<const char *>(ctx->mulsum_table);
@@ -390,11 +358,7 @@ void dc_ct_rotate_hop(dc_context *ctx, uint64_t *dst, long dst_stride, const uin
 void dc_ct_rotate_hop_add(dc_context *ctx, uint64_t *dst, long dst_stride, const uint64_t *src, long src_stride, const uint64_t *addend,
                           long addend_stride, uint32_t galois_elt, const uint64_t *galois_key, int ell, void *stream)
 {
-    if (ctx->c->hybrid()) {
-        fprintf(stderr, "[dacapo_amd] dc_ct_rotate_hop_add: this context switches keys with grouped digits (ks_special > 1); the call is for "
-                        "SEAL-layout keys (use dc_ct_rotate_hop and dc_ct_add)\n");
-        abort();
-    }
+    refuse_grouped_digits(*ctx->c, "dc_ct_rotate_hop_add", " (ks_special > 1); the call is for SEAL-layout keys (use dc_ct_rotate_hop and dc_ct_add)");
     KsItem it{ V(src, src_stride), V(dst, dst_stride), galois_key, galois_elt, 0 };
     it.add = V(addend, addend_stride);
     const KsItem *d = static_cast<const KsItem *>(item_slot(ctx, &it, sizeof(it), S(stream)));
@@ -406,8 +370,8 @@ void dc_ct_rotate_hoisted(dc_context *ctx, uint64_t *const *dsts, long dst_strid
                           const uint32_t *galois_elts, const uint64_t *const *galois_keys, int count, int ell, void *stream)
 {
     const size_t B = (size_t)count;
-    const KsItem *d = hoist_items(ctx, "dc_ct_rotate_hoisted", ", where dc_ct_rotate_hop already takes the digits before the automorphism", "hops",
-                                  count, ell, B, S(stream), [&](std::vector<KsItem> &h) {
+    const KsItem *d = hoist_items(ctx, "dc_ct_rotate_hoisted", ", where dc_ct_rotate_hop already takes the digits before the automorphism; the call is "
+                                  "for SEAL-layout keys", "hops", count, ell, B, S(stream), [&](std::vector<KsItem> &h) {
                                       for (size_t b = 0; b < B; b++)
                                           h.push_back(KsItem{ V(src, src_stride), V(dsts[b], dst_stride), galois_keys[b], galois_elts[b], 0 });
                                       h.push_back(KsItem{ V(src, src_stride), V(src, src_stride), nullptr, 1u, 0 }); // the source, for the decomposition's loader
@@ -427,7 +391,7 @@ static void rotate_sum_hoisted(dc_context *ctx, const char *who, uint64_t *dst, 
 {
     const size_t B = (size_t)count;
     size_t U = 0;
-    const KsItem *d = hoist_items(ctx, who, " (ks_special > 1)", "members", count, ell, 1, S(stream), [&](std::vector<KsItem> &h) {
+    const KsItem *d = hoist_items(ctx, who, " (ks_special > 1); the call is for SEAL-layout keys", "members", count, ell, 1, S(stream), [&](std::vector<KsItem> &h) {
         // members source-major (stable: equal sources keep the caller's order); then the group; then the distinct sources
         std::vector<size_t> order(B);
         for (size_t b = 0; b < B; b++) order[b] = b;
@@ -520,12 +484,7 @@ void dc_poly_error_stats(dc_context *ctx, const uint64_t *got, long got_stride, 
         abort();
     }
     const size_t bytes = noise_scratch_words(c, ell, count) * sizeof(u64);
-    if (bytes > ctx->noise_cap) { // (growing waits for the device: hipFree)
-        if (ctx->noise_buf) DC_HIP_CHECK(hipFree(ctx->noise_buf));
-        ctx->noise_buf = nullptr, ctx->noise_cap = 0;
-        DC_HIP_CHECK(hipMalloc(&ctx->noise_buf, bytes));
-        ctx->noise_cap = bytes;
-    }
+    grow_scratch(ctx->noise_buf, ctx->noise_cap, bytes);
     const NoiseStats *total = noise_error_stats(c, ctx->noise_buf, got, got_stride, want, want_stride, ell, count, lift_prime, s);
     DC_HIP_CHECK(hipMemcpyAsync(out_host, total, (size_t)count * sizeof(NoiseStats), hipMemcpyDeviceToHost, s));
     DC_HIP_CHECK(hipStreamSynchronize(s));

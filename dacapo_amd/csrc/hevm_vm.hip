@@ -1523,9 +1523,6 @@ struct IoTabLayout {
         return off;
     }
 };
-int ntt_launches(const Context &c, bool inverse, int limbs) {
-    return (ntt_full_supported(c) && ntt_full_pays(inverse, limbs)) || (ntt_lds_supported(c) && ntt_lds_pays(inverse, limbs)) ? 1 : 2;
-}
 } // namespace
 
 // `count` calls of encrypt() on streams first_stream ... in ascending order, as one launch sequence per chunk: the device encoder on all
@@ -1626,7 +1623,7 @@ void HEVM::encrypt_batch(int64_t arg, const double *vals, int len, int64_t strid
             DC_HIP_CHECK(hipMemcpy2DAsync(stage, w * sizeof(double), vals + (size_t)k0 * (size_t)stride, (size_t)stride * sizeof(double),
                                           w * sizeof(double), (size_t)B, hipMemcpyHostToDevice, S()));
         enc_batch(c, enc_tables, where == 0 ? stage : vals, d_enc + k0, B, ell, fft, pt, io.d_overflow, S());
-        io.launches += c.logN + 2 + ntt_launches(c, false, B * ell);
+        io.launches += c.logN + 2 + ntt_launches(ntt_kind(c, false, B * ell));
         if (hook) { // TEST HOOK: (plaintext, 0)
             io_add_plain(c, d_dst + k0, pt, B, ell, true, S());
             io.launches += 1;
@@ -1639,7 +1636,7 @@ void HEVM::encrypt_batch(int64_t arg, const double *vals, int len, int64_t strid
                 f_irows_zenc(c, d_zenc + k0, keys.pk, ell, digits, B, S());
                 f_dr_noise_icols_lift_fcols(c, digits, (long)N, tmp, 2 * B, ell, ell, noise, S());
                 f_frows_zenc_final(c, tmp, d_zenc + k0, keys.pk, B, ell, S());
-                io.launches += 4 + ntt_launches(c, false, cnt * B);
+                io.launches += 4 + ntt_launches(ntt_kind(c, false, cnt * B));
             } else {
                 DC_LAUNCH(sample_enc_batch_kernel, sgrid, dim3(kVmThreads), 0, S(), ue, N, cnt, rng.secret, enc_counter + (u64)k0, c.d_mods, d_epoch);
                 launch_ntt(c, false, ue, (long)N, 3 * cnt * B, nullptr, 0, cnt, S());
@@ -1648,7 +1645,7 @@ void HEVM::encrypt_batch(int64_t arg, const double *vals, int len, int64_t strid
                 BatchWs ws;
                 ws.digits = digits, ws.tmp = tmp;
                 b_rescale(c, ws, d_rs + k0, B, cnt, S()); // divide-and-round by the extra prime, straight into the register slices
-                io.launches += 5 + ntt_launches(c, false, 3 * cnt * B);
+                io.launches += 5 + ntt_launches(ntt_kind(c, false, 3 * cnt * B));
             }
             io_add_plain(c, d_dst + k0, pt, B, ell, false, S());
             io.launches += 1;

@@ -395,7 +395,7 @@ class HEVM {
     // ---- batched encrypt / decrypt (hevm_encrypt_batch / hevm_decrypt_batch): `count` streams' inputs or results as ONE launch sequence and
     // one synchronisation, values in host (where = 0) or device (where = 1) memory.  Limbs and doubles equal `count` calls of encrypt /
     // decrypt on those streams in ascending order.  The launches per chunk do not depend on the number of items in it (but for the
-    // transform's own form, kernels.hpp launch_ntt: one launch or two by its limb count at N = 2^15).
+    // transform's own form: one launch or two by its limb count, kernels.hpp ntt_kind).
     // Scratch is the VM's own (a client VM has no plan to borrow from): one block per direction, allocated on first use and grown when a call
     // needs more.  Chunk rule: io_chunk(per_item) = min(kIoChunk, max(1, kIoScratchBytes / per_item)) items per pass of the sequence, per_item
     // being the bytes one item needs at the call's level -- so a block is at most max(kIoScratchBytes, one item): at N = 2^17 with 31

@@ -285,7 +285,7 @@ static void hoist_decompose(Context &c, const BatchWs &w, const KsItem *d_source
 {
     const size_t N = c.N;
     f_irows_rot_c1(c, d_sources, ell, w.digits, U, s);
-    if ((long)(N >> 10) * U * ell * ell >= (long)option(OPT_KS_BIG_TILES)) {
+    if (ks_shape(c, U, ell).big) {
         launch_ntt_cols_inv(c, w.digits, (long)N, U * ell, nullptr, 0, ell, s);
         f_ks_lift_fcols(c, w.digits, w.ext, U, ell, s);
     } else
@@ -301,7 +301,7 @@ static void hoist_moddown(Context &c, const BatchWs &w, const KsItem *d_dsts, in
     const int sp = c.K - 1;
     u64 *acc_last = w.acc + (size_t)ell * N;
     const long acc_ps = (long)(ell + 1) * (long)N;
-    if ((long)(N >> 10) * R * ell * ell >= (long)option(OPT_KS_BIG_TILES)) {
+    if (ks_shape(c, R, ell).big) {
         launch_ntt_cols_inv(c, acc_last, acc_ps, 2 * R, nullptr, sp, 1, s);
         f_dr_lift_fcols(c, acc_last, acc_ps, w.tmp, 2 * R, ell, sp, s);
     } else

@@ -20,19 +20,27 @@ struct CtView {
 // Output canonical.
 void launch_ntt(const Context &c, bool inverse, u64 *data, long limb_stride, int count, const int *d_prime_idx,
                 int prime_base, int prime_period, hipStream_t s);
+// The kernel a transform takes: the two-launch tiles (every ring), the single-crossing kernel (N = 2^15) or the LDS-resident one (N = 2^12 .. 2^14;
+// 2^16 and 2^17 have no single-launch kernel).  ntt_kind alone decides "one launch or two": the ring's single-launch kernel where it pays, else the tiles.
+enum class NttKind { TwoPhase, Full, Lds };
+NttKind ntt_single_launch_kind(const Context &c); // the ring's single-launch kernel, or TwoPhase where the ring has none
+NttKind ntt_kind(const Context &c, bool inverse, int count);
+inline int ntt_launches(NttKind k) { return k == NttKind::TwoPhase ? 2 : 1; }
+void launch_ntt_as(const Context &c, NttKind kind, bool inverse, u64 *data, long limb_stride, int count, const int *d_prime_idx, int prime_base,
+                   int prime_period, hipStream_t s);
 
 // the two-launch transform whatever the batch size
 void launch_ntt_two_phase(const Context &c, bool inverse, u64 *data, long limb_stride, int count, const int *d_prime_idx,
                           int prime_base, int prime_period, hipStream_t s);
-// single-crossing transform (ntt_full.hip): one 1024-thread workgroup per limb, N = 2^15 only.  launch_ntt takes it for launches of
+// single-crossing transform (ntt_full.hip): one 1024-thread workgroup per limb, N = 2^15 only.  ntt_kind takes it for launches of
 // at least ntt_full_min_limbs() limbs (option ntt_full_min_limbs / option ntt_full_inv_min_limbs; 0 = never)
 bool ntt_full_supported(const Context &c);
 long ntt_full_min_limbs(bool inverse);
-bool ntt_full_pays(bool inverse, int count); // ... and the launch fills the persistent grid's last round well enough (ntt_full.hip)
+bool ntt_full_pays(bool inverse, int count); // ... and the launch fills the persistent grid's last round well enough (it asks the device's CU count)
 void launch_ntt_full(const Context &c, bool inverse, u64 *data, long limb_stride, int count, const int *d_prime_idx, int prime_base,
                      int prime_period, hipStream_t s);
 // single-launch transform for N = 2^12 .. 2^14 (ntt_lds.hip): one workgroup per limb, the whole limb resident in LDS between its passes.
-// launch_ntt takes it for launches of at least ntt_lds_min_limbs / ntt_lds_inv_min_limbs limbs (options; 0 = never)
+// ntt_kind takes it for launches of at least ntt_lds_min_limbs / ntt_lds_inv_min_limbs limbs (options; 0 = never)
 bool ntt_lds_supported(const Context &c);
 bool ntt_lds_pays(bool inverse, int count);
 void launch_ntt_lds(const Context &c, bool inverse, u64 *data, long limb_stride, int count, const int *d_prime_idx, int prime_base,

@@ -99,12 +99,23 @@ void launch_ntt_rows_inv(const Context &c, u64 *data, long limb_stride, int coun
 void launch_ntt(const Context &c, bool inverse, u64 *data, long limb_stride, int count, const int *d_prime_idx,
                 int prime_base, int prime_period, hipStream_t s)
 {
-    if (ntt_full_supported(c) && ntt_full_pays(inverse, count))
-        launch_ntt_full(c, inverse, data, limb_stride, count, d_prime_idx, prime_base, prime_period, s);
-    else if (ntt_lds_supported(c) && ntt_lds_pays(inverse, count))
-        launch_ntt_lds(c, inverse, data, limb_stride, count, d_prime_idx, prime_base, prime_period, s);
-    else
-        launch_ntt_two_phase(c, inverse, data, limb_stride, count, d_prime_idx, prime_base, prime_period, s);
+    launch_ntt_as(c, ntt_kind(c, inverse, count), inverse, data, limb_stride, count, d_prime_idx, prime_base, prime_period, s);
+}
+NttKind ntt_single_launch_kind(const Context &c) { return ntt_full_supported(c) ? NttKind::Full : ntt_lds_supported(c) ? NttKind::Lds : NttKind::TwoPhase; }
+NttKind ntt_kind(const Context &c, bool inverse, int count)
+{
+    const NttKind single = ntt_single_launch_kind(c);
+    const bool pays = single == NttKind::Full ? ntt_full_pays(inverse, count) : single == NttKind::Lds && ntt_lds_pays(inverse, count);
+    return pays ? single : NttKind::TwoPhase;
+}
+void launch_ntt_as(const Context &c, NttKind kind, bool inverse, u64 *data, long limb_stride, int count, const int *d_prime_idx, int prime_base,
+                   int prime_period, hipStream_t s)
+{
+    switch (kind) {
+    case NttKind::Full: launch_ntt_full(c, inverse, data, limb_stride, count, d_prime_idx, prime_base, prime_period, s); break;
+    case NttKind::Lds: launch_ntt_lds(c, inverse, data, limb_stride, count, d_prime_idx, prime_base, prime_period, s); break;
+    case NttKind::TwoPhase: launch_ntt_two_phase(c, inverse, data, limb_stride, count, d_prime_idx, prime_base, prime_period, s); break;
+    }
 }
 
 void launch_ntt_two_phase(const Context &c, bool inverse, u64 *data, long limb_stride, int count, const int *d_prime_idx,

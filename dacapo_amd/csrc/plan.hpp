@@ -14,9 +14,16 @@
 #pragma once
 #include "crt_device.hpp"
 #include "kernels.hpp"
+#include "launch_shape.hpp"
 
 namespace dacapo {
 
+inline KsShape ks_shape(const Context &c, int B, int ell) { return ks_shape(c.N, c.hybrid(), B, ell); }
+// a call that exists for SEAL-layout keys meets a context with grouped digits: abort in the caller's name, `rest` ending the sentence in its words
+inline void refuse_grouped_digits(const Context &c, const char *who, const char *rest)
+{
+    if (c.hybrid()) fprintf(stderr, "[dacapo_amd] %s: this context switches keys with grouped digits%s\n", who, rest), abort();
+}
 struct KsItem {   // one key-switch hop of a rotation: dst = apply_galois(src)
     CtView src, dst;
     const u64 *key;
@@ -131,15 +138,14 @@ struct BatchWs {
 };
 
 // `unique`: grouped-digit mode only -- the number of distinct decompositions the items' `slot` fields name (0: every item its own)
-// `addend`: some item carries one (KsItem::add); aborts unless the batch runs the fused middle on SEAL-layout keys, which alone adds it
+// `addend`: some item carries one (KsItem::add); aborts unless the batch's shape carries one (launch_shape.hpp carries_addend)
 void b_rotate_hops(Context &c, const BatchWs &w, const KsItem *d_items, int B, int ell, hipStream_t s, const Handoff &h = Handoff{}, int unique = 0,
                    bool addend = false);
 void b_mul_relin(Context &c, const BatchWs &w, const MulItem *d_items, const u64 *relin_key, int B, int ell, hipStream_t s,
                  const Handoff &h = Handoff{});
 // a multiply and the rescale that alone reads it as ONE five-launch sequence (SEAL-layout keys, the latency-shaped launch forms only:
-// mul_relin_rescale_fused says whether a batch of B at level ell has it; otherwise run b_mul_relin and b_rescale -- the limbs are the same).
-// h.in as for b_mul_relin; h.cont CONT_MUL / CONT_BOOT as for b_rescale.
-bool mul_relin_rescale_fused(const Context &c, int B, int ell);
+// ks_shape(c, B, ell).folds_rescale() says whether a batch of B at level ell has it; otherwise run b_mul_relin and b_rescale -- the limbs are
+// the same).  h.in as for b_mul_relin; h.cont CONT_MUL / CONT_BOOT as for b_rescale.
 void b_mul_relin_rescale(Context &c, const BatchWs &w, const MulRsItem *d_items, const u64 *relin_key, int B, int ell, hipStream_t s,
                          const Handoff &h = Handoff{});
 void b_rescale(Context &c, const BatchWs &w, const RsItem *d_items, int B, int ell, hipStream_t s, const SumSrc *d_srcs = nullptr,
@@ -159,7 +165,6 @@ void hoist_rotate_hops(Context &c, const BatchWs &w, const KsItem *d_items, cons
 // launch of its own (src.p == nullptr: that group has none); it may be a source or a destination of the batch
 void hoist_rotate_sum(Context &c, const BatchWs &w, const KsItem *d_items, const KsItem *d_sources, int B, int U, const KsItem *d_groups, int G,
                       int ell, hipStream_t s, bool addend = false);
-bool chain_fusion_supported(); // the continuation kernels exist for the default launch sequences only
 // grouped-digit hybrid key switching (hybrid_ks.hip; Context::hybrid()): b_rotate_hops / b_mul_relin / keyswitch route here
 void hyb_rotate_hops(Context &c, const BatchWs &w, const KsItem *d_items, int B, int ell, hipStream_t s, int unique = 0);
 // lazy sums (option hyb_lazy_sum): the B items' accumulators are added group by group and divided by P once per group.  d_groups[g]: dst = the

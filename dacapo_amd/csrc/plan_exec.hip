@@ -666,7 +666,7 @@ void HEVM::build_plan()
     // and two rotations of one wave that are added together keep their shared batch -- and made by an earlier pseudo-op (the list stays in
     // dataflow order).  The sum's level and scale stay as the walk fixed them.  The addend is the hop's second source from here on: waves,
     // lifetimes and the steps' read sets count it like the first.
-    if (ks_fold_add && !c.hybrid() && option(OPT_KS_FUSE_MAC) != 0) {
+    if (ks_fold_add) {
         std::vector<int> asap(O.size(), 0); // (the unfolded plan's waves: a fold below must not change what a later one compares)
         for (size_t i = 0; i < O.size(); i++) asap[i] = O[i].wave;
         std::set<int> folded; // the sums' values that a rotation defines now
@@ -674,8 +674,8 @@ void HEVM::build_plan()
             Pop &s = O[si];
             if (s.dead || s.kind != P_SUM || s.srcs.size() != 2) continue;
             if (std::any_of(s.src_plain.begin(), s.src_plain.end(), [](int pl) { return pl >= 0; })) continue;
-            // (the middle stays one launch for every batch a step of this level can hold: batch_ops.hip b_ks_tail's split)
-            if ((long long)(N >> 10) * (long long)step_chunk(P_ROT) * S * s.level * s.level >= option(OPT_KS_FUSE_MAC_TILES)) continue;
+            // (the middle stays one launch for every batch a step of this level can hold)
+            if (!ks_shape(c, (int)step_chunk(P_ROT) * S, s.level).carries_addend()) continue;
             for (size_t w = 0; w < 2; w++) {
                 const int hv = s.srcs[w], a = s.srcs[1 - w], hi = own_pop(hv);
                 if (hi < 0 || a == hv) continue;
@@ -759,7 +759,7 @@ void HEVM::build_plan()
     // a program result (its buffer is then never written), the rescale has no folded sum, and a folded multiplier is a constant polynomial --
     // decided from the plaintext's limbs, every value of a limb equal to its first, read back once here.  Qualifying multiplies get a bucket of
     // their own (target_level = -3), so a pair that does not qualify never holds back the other items of its wave; a chunk whose batch has no
-    // folded launch form (mul_relin_rescale_fused) stays two steps.  The merged step stands where the multiply stood, defines the RESCALE's
+    // folded launch form (launch_shape.hpp folds_rescale) stays two steps.  The merged step stands where the multiply stood, defines the RESCALE's
     // result, and takes part in the links of section 4b as the rescale would (CONT_MUL / CONT_BOOT out, a producer's hand-off in).
     std::map<int, int> fold_rs_of;                // qualifying multiply pop -> its rescale pop
     std::vector<char> absorbed(O.size(), 0);      // rescale pops that a merged step executes: in no step of their own
@@ -836,7 +836,7 @@ void HEVM::build_plan()
                 for (int pi : members) O[(size_t)pi].step = (int)P.steps.size();
                 if (kind == P_MULCC && st.target == -3) { // option ks_fold_rescale: the chunk and its rescales as one step, where a folded form exists
                     st.target = 0;
-                    if (mul_relin_rescale_fused(c, st.count * S, st.level)) {
+                    if (ks_shape(c, st.count * S, st.level).folds_rescale()) {
                         st.fold_rs = true;
                         std::vector<int> &rs = fold_pops[P.steps.size()];
                         for (int pi : members) {

@@ -214,7 +214,7 @@ class Context:
     def ntt(self, buf: DeviceBuffer, count, inverse=False, prime_idx: DeviceBuffer | None = None, prime_base=0,
             prime_period=0, limb_stride=None, offset=0, stream=None, variant=None):
         """variant None: the library chooses by batch size; 0 / 1: the two-launch tiles / the ring's single-launch kernel (dc_ntt_variant:
-        N = 2^12 .. 2^15; ntt_variant_supported asks)"""
+        single-crossing at N = 2^15, LDS-resident at 2^12 .. 2^14, none at 2^16 and 2^17; ntt_variant_supported asks)"""
         args = (buf.at(offset), self.N if limb_stride is None else limb_stride, count,
                 prime_idx.ptr if prime_idx is not None else None, prime_base, prime_period, stream)
         if variant is None:

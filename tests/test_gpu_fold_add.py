@@ -95,10 +95,12 @@ def test_rotate_hop_add_every_key(env, ell):
         _check_hop_add(ll, ctx, o, ell, elt, _case(o, cache, ell, elt))
 
 
-@pytest.mark.parametrize("opts", [{"ks_merge_special_min_wgs": 0, "ks_merge_lift_min_wgs": 0}, {"small_tile_wgs": 0, "wide_tile_wgs": 0}])
+@pytest.mark.parametrize("opts", [{"ks_merge_special_min_wgs": 0, "ks_merge_lift_min_wgs": 0}, {"small_tile_wgs": 0, "wide_tile_wgs": 0},
+                                  {"ks_big_tiles": 1}])
 def test_rotate_hop_add_launch_forms_l2(env, opts):
     """level 2 with the merged forms of the middle and the lift (one workgroup row for both special-prime accumulators: it gets no start
-    value), and with the forced tile geometries"""
+    value), with the forced tile geometries, and with the large-batch sequence around the fused middle (the un-fused middle carries no addend:
+    that side is an abort, stated by tests/test_launch_shape.py and not run here)"""
     from dacapo_amd import runner
 
     ll, ctx, o, cache = env

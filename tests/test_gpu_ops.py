@@ -125,6 +125,37 @@ def test_rescale_mulrelin_rotate(env, ell):
     assert (db.to_host()[:, : ell - 1] == want).all()
 
 
+@pytest.fixture(scope="module")
+def seq_case(env):
+    """operands at level 3 and the oracle's product and rotations of them: computed once for the option sets of the test below"""
+    _, _, o = env
+    a, b = _rand_ct(o, 3, 21), _rand_ct(o, 3, 22)
+    A, B = Ciphertext(a, 2.0**40), Ciphertext(b, 2.0**40)
+    return a, b, o.mul_relin(A, B).data, {elt: o.apply_galois(A, elt).data for elt in o.galois}
+
+
+@pytest.mark.parametrize("opts", [{"ks_big_tiles": 1}, {"ks_fuse_mac": 0}, {"ks_fuse_mac_tiles": 72}, {"ks_big_tiles": 1, "ks_fuse_mac_tiles": 72}])
+def test_mulrelin_rotate_launch_sequences_l3(env, seq_case, opts):
+    """the other launch sequences of the key switch (csrc/launch_shape.hpp) behind dc_ct_mul_relin and dc_ct_rotate_hop: level 3 at N = 2^13 is
+    (N / 1024) * 1 * 3^2 = 72 tiles of work, so ks_big_tiles = 1 takes the large-batch sequence, ks_fuse_mac = 0 and ks_fuse_mac_tiles = 72 (the
+    first size not below the threshold) the un-fused middle, and the last set both.  The default sequence is the test above."""
+    from dacapo_amd import runner
+
+    ll, ctx, o = env
+    L, N, cap, ell = ll.lib(), o.N, o.K - 1, 3
+    st = cap * N
+    a, b, want_mul, want_rot = seq_case
+    da, db, dd, drel = _dev_ct(ll, a, cap), _dev_ct(ll, b, cap), ll.DeviceBuffer((2, cap, N)), ll.DeviceBuffer.from_host(o.relin)
+    with runner.options(**opts):
+        L.dc_ct_mul_relin(ctx.h, dd.ptr, st, da.ptr, st, db.ptr, st, drel.ptr, ell, None)
+        assert (dd.to_host()[:, :ell] == want_mul).all()
+        for elt, key in o.galois.items():
+            dkey = ll.DeviceBuffer.from_host(key)
+            L.dc_ct_rotate_hop(ctx.h, dd.ptr, st, da.ptr, st, elt, dkey.ptr, ell, None)
+            assert (dd.to_host()[:, :ell] == want_rot[elt]).all()
+    assert (da.to_host()[:, :ell] == a).all() and (db.to_host()[:, :ell] == b).all()
+
+
 def test_homomorphic_roundtrip_on_gpu(env):
     """encrypt (oracle) -> mul_relin + rescale + rotate on the GPU -> decrypt (oracle) ~= plaintext result."""
     ll, ctx, o = env
