@@ -142,15 +142,15 @@ static void b_ks_tail(Context &c, const BatchWs &w, const KsShape &sh, u64 *digi
 
 void b_rotate_hops(Context &c, const BatchWs &w, const KsItem *d_items, int B, int ell, hipStream_t s, const Handoff &h, int unique, bool addend)
 {
+    if (c.hybrid()) { // (the plan links no steps in this mode: h is empty; every launch form there carries an addend)
+        hyb_rotate_hops(c, w, d_items, B, ell, s, unique, addend);
+        return;
+    }
     const KsShape sh = ks_shape(c, B, ell);
     if (addend && !sh.carries_addend()) {
         fprintf(stderr, "[dacapo_amd] b_rotate_hops: an item carries an addend, which only the fused middle of SEAL-layout key switching adds "
-                        "(%s)\n", c.hybrid() ? "this context switches keys with grouped digits" : "option ks_fuse_mac = 0, or the batch is above ks_fuse_mac_tiles");
+                        "(option ks_fuse_mac = 0, or the batch is above ks_fuse_mac_tiles)\n");
         abort();
-    }
-    if (c.hybrid()) { // (the plan links no steps in this mode: h is empty)
-        hyb_rotate_hops(c, w, d_items, B, ell, s, unique);
-        return;
     }
     f_irows_rot_c1(c, d_items, ell, w.digits, B, s);
     b_ks_tail<0>(c, w, sh, w.digits, d_items, d_items, nullptr, B, ell, s, h);

@@ -353,12 +353,12 @@ void dc_ct_rotate_hop(dc_context *ctx, uint64_t *dst, long dst_stride, const uin
     const KsItem *d = static_cast<const KsItem *>(item_slot(ctx, &it, sizeof(it), S(stream)));
     b_rotate_hops(*ctx->c, batch_ws(ctx->c->ws0), d, 1, ell, S(stream));
 }
-// dst = apply_galois(src) + addend: dc_ct_rotate_hop with one addend at level ell, which the fused middle adds exactly (KsItem::add; fused_ks.hip
-// f_ks_frows_mac_kernel).  The addend is read by the middle launch alone, before the last launch writes dst: it may be src or dst.
+// dst = apply_galois(src) + addend: dc_ct_rotate_hop with one addend at level ell, which the key switch adds exactly (KsItem::add; SEAL-layout
+// keys: fused_ks.hip f_ks_frows_mac_kernel; grouped digits: hybrid_ks.hip hyb_mac_kernel<3>, or hyb_prepare_rot_kernel under hyb_fuse = 0).  The
+// addend is read before any launch writes dst at the same index: it may be src or dst.
 void dc_ct_rotate_hop_add(dc_context *ctx, uint64_t *dst, long dst_stride, const uint64_t *src, long src_stride, const uint64_t *addend,
                           long addend_stride, uint32_t galois_elt, const uint64_t *galois_key, int ell, void *stream)
 {
-    refuse_grouped_digits(*ctx->c, "dc_ct_rotate_hop_add", " (ks_special > 1); the call is for SEAL-layout keys (use dc_ct_rotate_hop and dc_ct_add)");
     KsItem it{ V(src, src_stride), V(dst, dst_stride), galois_key, galois_elt, 0 };
     it.add = V(addend, addend_stride);
     const KsItem *d = static_cast<const KsItem *>(item_slot(ctx, &it, sizeof(it), S(stream)));

@@ -509,7 +509,8 @@ void HEVM::init_context(int logN, int K, const u64 *primes, int dir_ksp, int dir
             abort();
         }
     }
-    ks_fold_add = option(OPT_KS_FOLD_ADD) != 0; // (grouped digits, ks_hoist, ks_fuse_mac = 0: the rule finds nothing to fold)
+    ks_fold_add = option(OPT_KS_FOLD_ADD) != 0; // (ks_hoist, ks_fuse_mac = 0: the rule finds nothing to fold; grouped digits: hyb_fold_add is the option)
+    hyb_fold_add = option(OPT_HYB_FOLD_ADD) != 0; // (SEAL-layout keys: ignored)
     zenc_head = option(OPT_ZENC_HEAD) != 0;
     // prime_bits = b (45..60; the generic-width build only): the chain CoeffModulus::Create(N, {b, b, ...}) instead of the reference's
     // 60-bit one (SEAL_HEVM.cpp:48-53) -- e.g. 51 for rescale primes of the HEaaN configuration's width
@@ -2772,7 +2773,7 @@ void hevm_last_run_flatten_stats(void *vm, int64_t *groups, int64_t *members, in
     if (hops_absorbed) *hops_absorbed = V(vm)->n_flat_hops;
 }
 
-// option ks_fold_add: two-term sums that the last run() computed inside a rotation's last hop (every stream counted); 0 with the option off and
+// options ks_fold_add (SEAL-layout keys) / hyb_fold_add (grouped digits): two-term sums that the last run() computed inside a rotation's last hop (every stream counted); 0 with the option off and
 // in the loop (plan = 0)
 int64_t hevm_last_run_add_fold_stats(void *vm) { return V(vm)->n_add_folds; }
 

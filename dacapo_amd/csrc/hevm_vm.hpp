@@ -263,7 +263,7 @@ class HEVM {
         int64_t n_hops = 0, n_decomp = 0; // rotation hops and the decompositions computed for them (hevm_last_run_hoist_stats)
         int64_t n_relin_groups = 0, n_relin_products = 0; // P_MULSUM items and their terms (hevm_last_run_relin_stats)
         int64_t n_flat_groups = 0, n_flat_members = 0, n_flat_hops = 0; // flattened stages, their rotations and the hops they absorbed, once per stream (hevm_last_run_flatten_stats)
-        int64_t n_add_folds = 0;          // two-term sums that a rotation's last hop computes (option ks_fold_add; hevm_last_run_add_fold_stats), per stream until the plan is ready
+        int64_t n_add_folds = 0;          // two-term sums that a rotation's last hop computes (options ks_fold_add / hyb_fold_add; hevm_last_run_add_fold_stats), per stream until the plan is ready
         int64_t n_fold = 0;               // items of multiply steps that run with their rescale folded in (hevm_last_run_fold_rescale_stats)
         size_t launches = 0, max_live = 0;
         hipGraph_t graph = nullptr;
@@ -326,6 +326,9 @@ class HEVM {
     // option ks_fold_add = 1 (SEAL-layout keys): y + rotate(x, o) is the rotation's own last hop with y as its addend (plan_exec.hip section 3a;
     // plan.hpp KsItem::add).  Every limb equals the default path's.  The loop (plan = 0) runs the instructions as written.
     bool ks_fold_add = true;
+    // option hyb_fold_add = 1 (grouped digits): the same fold on the grouped-digit path, where every launch form of a rotation hop carries the
+    // addend (hybrid_ks.hip).  Off by default (profiles/hyb_fold_add_ab.txt); ks_fold_add is a no-op in that mode, this one on SEAL-layout keys.
+    bool hyb_fold_add = false;
     PlanFlow program_flow() const; // the loaded program's dataflow under the result registers of this moment (plan_flow.hpp)
     std::vector<FlattenGroup> flatten_groups(const PlanFlow &flow, bool every_key) const; // the program's groups under the key set held (every_key: as if every offset had a key)
     // option zenc_head = 1: the zero-encryptions at the start of a plan's run() transform only u (plan_zero_encrypt).  Every limb equals

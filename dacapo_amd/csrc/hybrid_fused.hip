@@ -316,14 +316,15 @@ static void f9_frows_final(const Context &c, const u64 *tmp, const u64 *accq, co
 
 // hybrid_ks.hip
 void hyb_launch_mac(Context &c, int mode, const BatchWs &w, const void *items, KsItem rot_single, const u64 *key, int B, int use_slots, int ell,
-                    hipStream_t s, bool fold_base);
+                    hipStream_t s, bool fold_base, bool addend);
 void hyb_launch_conv(Context &c, bool down, bool prescaled, const u64 *in, u64 *out, int count, int ell, hipStream_t s);
-void hyb_launch_mac_groups(Context &c, const BatchWs &w, const KsItem *items, const KsItem *groups, int G, int use_slots, int ell, hipStream_t s);
+void hyb_launch_mac_groups(Context &c, const BatchWs &w, const KsItem *items, const KsItem *groups, int G, int use_slots, int ell, hipStream_t s,
+                           bool addend);
 
 // F2 ... F5: everything between F1 and the accumulators.  digits [U][ell][N] hold the inverse ROWS phase's output.
 template <int MODE>
 static void hybf_front(Context &c, const BatchWs &w, const void *items, KsItem rot_single, const u64 *key, int B, int U, int use_slots, int ell,
-                       hipStream_t s, bool with_mac = true)
+                       hipStream_t s, bool with_mac = true, bool addend = false)
 {
     const size_t N = c.N;
     const int E = c.hyb_ext(ell);
@@ -336,7 +337,7 @@ static void hybf_front(Context &c, const BatchWs &w, const void *items, KsItem r
         f3_modup_fcols(c, w.digits, w.ext, U, ell, s);                                                             // F3
         launch_ntt_rows_fwd(c, w.ext, (long)N, U * E, c.hyb_pidx(ell), 0, E, s);                                   // F4
     }
-    if (with_mac) hyb_launch_mac(c, MODE, w, items, rot_single, key, B, use_slots, ell, s, MODE == 0);             // F5
+    if (with_mac) hyb_launch_mac(c, MODE, w, items, rot_single, key, B, use_slots, ell, s, MODE == 0, addend);     // F5
 }
 // F6 ... F9: the division by P of `B` accumulator pairs accq [2B][ell][N], accp [2B][ksp][N]; items[b] names where pair b goes
 template <int MODE>
@@ -357,9 +358,9 @@ static void hybf_back(Context &c, const BatchWs &w, const u64 *accq, u64 *accp, 
 }
 template <int MODE>
 static void hybf_core(Context &c, const BatchWs &w, const void *items, KsItem rot_single, HybOut single, const u64 *key, int B, int U, int use_slots,
-                      int ell, hipStream_t s)
+                      int ell, hipStream_t s, bool addend = false)
 {
-    hybf_front<MODE>(c, w, items, rot_single, key, B, U, use_slots, ell, s);
+    hybf_front<MODE>(c, w, items, rot_single, key, B, U, use_slots, ell, s, true, addend);
     hybf_back<MODE>(c, w, w.acc, w.acc + (size_t)B * 2 * ell * c.N, items, rot_single, single, B, ell, s);
 }
 
@@ -408,7 +409,9 @@ __global__ __launch_bounds__(256) void hybf_group_sum_kernel(const u64 *__restri
 // accumulator is ever stored).  option hyb_lazy_sum = 2 -- a second implementation of the same sums, kept for the parity tests: every item's
 // accumulators as for an ordinary step, added by hybf_group_sum_kernel into w.ext (free once F5 has read the raised limbs; 2 G (l + ksp) <= B E
 // limbs: every group has at least two items).
-void hybf_rotate_sum(Context &c, const BatchWs &w, const KsItem *d_items, int B, const KsItem *d_groups, int G, int ell, hipStream_t s, int unique)
+// `addend`: a planner's error here (hyb_launch_mac_groups) -- neither implementation reads KsItem::add
+void hybf_rotate_sum(Context &c, const BatchWs &w, const KsItem *d_items, int B, const KsItem *d_groups, int G, int ell, hipStream_t s, int unique,
+                     bool addend)
 {
     const size_t N = c.N;
     const int use_slots = unique > 0 ? 1 : 0, U = use_slots ? unique : B, ksp = c.ksp;
@@ -420,7 +423,7 @@ void hybf_rotate_sum(Context &c, const BatchWs &w, const KsItem *d_items, int B,
     f1_irows<0>(c, d_items, KsItem{}, nullptr, w.digits, B, ell, use_slots, s);
     hybf_front<0>(c, w, d_items, KsItem{}, nullptr, B, U, use_slots, ell, s, separate_sum);
     if (!separate_sum) {
-        hyb_launch_mac_groups(c, w, d_items, d_groups, G, use_slots, ell, s);
+        hyb_launch_mac_groups(c, w, d_items, d_groups, G, use_slots, ell, s, addend);
         hybf_back<0>(c, w, w.acc, w.acc + (size_t)G * 2 * ell * N, d_groups, KsItem{}, HybOut{}, G, ell, s);
         return;
     }
@@ -430,19 +433,22 @@ void hybf_rotate_sum(Context &c, const BatchWs &w, const KsItem *d_items, int B,
     hybf_back<0>(c, w, gq, gp, d_groups, KsItem{}, HybOut{}, G, ell, s);
 }
 
-void hybf_rotate_hops(Context &c, const BatchWs &w, const KsItem *d_items, int B, int ell, hipStream_t s, int unique)
+// `addend`: some item carries one (KsItem::add) -- F5 then runs as hyb_mac_kernel<3>; F1 (first item of a slot) and F9 do not look at it
+void hybf_rotate_hops(Context &c, const BatchWs &w, const KsItem *d_items, int B, int ell, hipStream_t s, int unique, bool addend)
 {
     const int use_slots = unique > 0 ? 1 : 0, U = use_slots ? unique : B;
     f1_irows<0>(c, d_items, KsItem{}, nullptr, w.digits, B, ell, use_slots, s);
-    hybf_core<0>(c, w, d_items, KsItem{}, HybOut{}, nullptr, B, U, use_slots, ell, s);
+    hybf_core<0>(c, w, d_items, KsItem{}, HybOut{}, nullptr, B, U, use_slots, ell, s, addend);
 }
 
-void hybf_rotate_hop_single(Context &c, const Workspace &w, CtView dst, CtView src, u32 galois_elt, const u64 *galois_key, int ell, hipStream_t s)
+void hybf_rotate_hop_single(Context &c, const Workspace &w, CtView dst, CtView src, u32 galois_elt, const u64 *galois_key, int ell, hipStream_t s,
+                            CtView add)
 {
-    const KsItem it{ src, dst, galois_key, galois_elt, 0 };
+    KsItem it{ src, dst, galois_key, galois_elt, 0 };
+    it.add = add;
     BatchWs bw{ nullptr, w.ks_digits, w.ks_ext, w.ks_acc, w.ks_tmp };
     f1_irows<0>(c, nullptr, it, nullptr, w.ks_digits, 1, ell, 0, s);
-    hybf_core<0>(c, bw, nullptr, it, HybOut{}, nullptr, 1, 1, 0, ell, s);
+    hybf_core<0>(c, bw, nullptr, it, HybOut{}, nullptr, 1, 1, 0, ell, s, add.p != nullptr);
 }
 
 // target [B][ell][N] = the tensor products' c2 (NTT form), dst.c0 / dst.c1 hold their c0 / c1 (hyb_prepare_mul_kernel has run)

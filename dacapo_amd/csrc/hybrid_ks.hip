@@ -34,16 +34,25 @@ struct HybSingle { // one key switch by value (the one-instruction-at-a-time loo
 
 // rotation items: dst.c0 = galois(src.c0); digits[slot] = src.c1 AS IT IS -- the digits are taken before the automorphism (see the header and
 // oracle orc_rotate_ks_hybrid), so hops of one source ciphertext share one decomposition: every item of a slot writes the same limbs.
+// An item with an addend (KsItem::add, wave-uniform): dst.c0 = galois(src.c0) + y0, dst.c1 = y1 -- hyb_final_kernel<0> then accumulates into
+// both polynomials.  A thread reads y at its own two coefficients before it writes them, so the addend may be dst (or src).
 // `single` (items == nullptr): one hop by value.  grid = (N/512, l, B)
 __global__ __launch_bounds__(kHT) void hyb_prepare_rot_kernel(const KsItem *__restrict__ items, KsItem single, u64 *__restrict__ digits, int ell,
-                                                               size_t N, int logN, int use_slots)
+                                                               size_t N, int logN, int use_slots, const DModulus *__restrict__ mods)
 {
     const int i = blockIdx.y, b = blockIdx.z;
     const KsItem it = items ? items[b] : single;
     const size_t k = ((size_t)blockIdx.x * kHT + threadIdx.x) * 2;
     const u32 g = galois_idx((u32)k, it.elt, logN); // an aligned pair of outputs reads an aligned pair of inputs, possibly swapped
     const u64x2 v0 = *reinterpret_cast<const u64x2 *>(it.src.limb(0, i, N) + (g & ~1u));
-    *reinterpret_cast<u64x2 *>(it.dst.limb(0, i, N) + k) = (g & 1u) ? u64x2{ v0.y, v0.x } : v0;
+    u64x2 c0 = (g & 1u) ? u64x2{ v0.y, v0.x } : v0;
+    if (it.add.p) {
+        const u64 q = mods[i].q;
+        const u64x2 y0 = *reinterpret_cast<const u64x2 *>(it.add.limb(0, i, N) + k), y1 = *reinterpret_cast<const u64x2 *>(it.add.limb(1, i, N) + k);
+        c0.x = addmod(c0.x, y0.x, q), c0.y = addmod(c0.y, y0.y, q);
+        *reinterpret_cast<u64x2 *>(it.dst.limb(1, i, N) + k) = y1;
+    }
+    *reinterpret_cast<u64x2 *>(it.dst.limb(0, i, N) + k) = c0;
     const size_t slot = use_slots ? it.slot : (size_t)b;
     *reinterpret_cast<u64x2 *>(digits + (slot * ell + i) * N + k) = *reinterpret_cast<const u64x2 *>(it.src.limb(1, i, N) + k);
 }
@@ -125,7 +134,14 @@ __global__ __launch_bounds__(kHT) void hyb_modup_kernel(const u64 *__restrict__ 
 
 // inner products with the key.  grid = (N/512, B, M).  MODE 0 rotation items (per-item key; every operand -- a raised limb of the item's
 // slot, or the NTT-form limb of src.c1 itself where the modulus belongs to the digit -- is read THROUGH the item's Galois permutation),
-// 1 ct x ct items (shared key), 2 one key switch by value
+// 1 ct x ct items (shared key), 2 one key switch by value,
+// 3 rotation items of which some carry an addend y at the hop's level (KsItem::add; option hyb_fold_add, dc_ct_rotate_hop_add; the fused
+// sequences only, pmod != nullptr).  y enters the data-prime accumulators as P y beside the base term and nothing enters the special-prime
+// ones: acc_P, and with it the mod-down's correction t, do not move, so (acc_q + P y - t) P^-1 = (acc_q - t) P^-1 + y limb for limb, with no
+// rounding of its own.  y is read where it lies, at index k (no gather), its two 16-byte loads issued behind the first digit's three;
+// galois(c0) + y0 is formed before the one multiplication by P, so polynomial 0 costs an addmod and polynomial 1 one mulmod per coefficient.
+// Whether an item has an addend is wave-uniform (blockIdx.y names the item): items with and without one share the launch.  A mode of its own,
+// so that modes 0 .. 2 stay the code objects they were.
 template <int MODE>
 __global__ __launch_bounds__(kHT) void hyb_mac_kernel(u64 *__restrict__ accq, u64 *__restrict__ accp, const u64 *__restrict__ ext,
                                                        const u64 *__restrict__ target, const void *__restrict__ items, KsItem single,
@@ -134,15 +150,16 @@ __global__ __launch_bounds__(kHT) void hyb_mac_kernel(u64 *__restrict__ accq, u6
 {
     // (items fastest: the items of a hoisted batch read the same raised limbs -- through their own Galois maps -- within a few MiB of traffic
     // of each other instead of a whole pass over the key apart)
+    constexpr bool ROT = MODE == 0 || MODE == 3, ADD = MODE == 3;
     const int mi = blockIdx.z, b = blockIdx.y, M = ell + ksp, pm = mi < ell ? mi : L + (mi - ell);
     const DModulus Md = mods[pm];
     KsItem it{};
-    if (MODE == 0) it = items ? static_cast<const KsItem *>(items)[b] : single;
-    const u64 *key = MODE == 0 ? it.key : shared_key;
+    if (ROT) it = items ? static_cast<const KsItem *>(items)[b] : single;
+    const u64 *key = ROT ? it.key : shared_key;
     const size_t k = ((size_t)blockIdx.x * kHT + threadIdx.x) * 2;
-    const size_t slot = MODE == 0 ? (use_slots ? it.slot : (size_t)b) : (size_t)b;
+    const size_t slot = ROT ? (use_slots ? it.slot : (size_t)b) : (size_t)b;
     u32 gsrc = (u32)k;
-    if (MODE == 0) gsrc = galois_idx((u32)k, it.elt, logN);
+    if (ROT) gsrc = galois_idx((u32)k, it.elt, logN);
     const int G = (ell + alpha - 1) / alpha;
     Acc128 a0[2], a1[2];
 #pragma unroll
@@ -152,19 +169,25 @@ __global__ __launch_bounds__(kHT) void hyb_mac_kernel(u64 *__restrict__ accq, u6
     auto fetch = [&](int g, u64x2 &x, u64x2 &y0, u64x2 &y1) {
         const int lo = g * alpha, hi = min(lo + alpha, ell);
         const bool own = mi >= lo && mi < hi;
-        const u64 *op = own ? (MODE == 0 ? it.src.limb(1, mi, N) : target + ((size_t)b * ell + mi) * N)
+        const u64 *op = own ? (ROT ? it.src.limb(1, mi, N) : target + ((size_t)b * ell + mi) * N)
                             : ext + (slot * E + (size_t)g * (M - alpha) + (mi < lo ? mi : mi - (hi - lo))) * N;
-        x = *reinterpret_cast<const u64x2 *>(MODE == 0 ? op + (gsrc & ~1u) : op + k);
+        x = *reinterpret_cast<const u64x2 *>(ROT ? op + (gsrc & ~1u) : op + k);
         y0 = *reinterpret_cast<const u64x2 *>(key + (((size_t)g * 2 + 0) * K + pm) * N + k);
         y1 = *reinterpret_cast<const u64x2 *>(key + (((size_t)g * 2 + 1) * K + pm) * N + k);
     };
     u64x2 xn, y0n, y1n;
     fetch(0, xn, y0n, y1n);
+    u64x2 ad0{ 0, 0 }, ad1{ 0, 0 };
+    const bool has_add = ADD && it.add.p != nullptr && mi < ell;
+    if (has_add) {
+        ad0 = *reinterpret_cast<const u64x2 *>(it.add.limb(0, mi, N) + k);
+        ad1 = *reinterpret_cast<const u64x2 *>(it.add.limb(1, mi, N) + k);
+    }
     for (int g = 0; g < G; g++) { // G <= 16: the 128-bit sums stay below 2^124
         u64x2 x = xn;
         const u64x2 y0 = y0n, y1 = y1n;
         if (g + 1 < G) fetch(g + 1, xn, y0n, y1n);
-        if (MODE == 0 && (gsrc & 1u)) x = u64x2{ x.y, x.x };
+        if (ROT && (gsrc & 1u)) x = u64x2{ x.y, x.x };
 #pragma unroll
         for (int e = 0; e < 2; e++) {
             a0[e].mac(x[e], y0[e]);
@@ -174,14 +197,21 @@ __global__ __launch_bounds__(kHT) void hyb_mac_kernel(u64 *__restrict__ accq, u6
     u64x2 o0, o1;
 #pragma unroll
     for (int e = 0; e < 2; e++) o0[e] = a0[e].reduce(Md), o1[e] = a1[e].reduce(Md);
-    if (MODE == 0 && pmod && mi < ell) {
+    if (ROT && pmod && mi < ell) {
         // fused sequence: the rotation's base term rides on the accumulator -- galois(c0) + (acc - t) P^-1 = ((acc + P galois(c0)) - t) P^-1
         // exactly, so the last kernel has no gather to do and nobody materialises galois(c0) (this kernel has the Galois index in hand,
         // 16-byte accesses, and arithmetic to spare next to the key's bytes)
         const u64x2 v = *reinterpret_cast<const u64x2 *>(it.src.limb(0, mi, N) + (gsrc & ~1u));
         const u64 P = pmod[pm];
-        o0.x = addmod(o0.x, mulmod((gsrc & 1u) ? v.y : v.x, P, Md), Md.q);
-        o0.y = addmod(o0.y, mulmod((gsrc & 1u) ? v.x : v.y, P, Md), Md.q);
+        if (has_add) {
+            o0.x = addmod(o0.x, mulmod(addmod((gsrc & 1u) ? v.y : v.x, ad0.x, Md.q), P, Md), Md.q);
+            o0.y = addmod(o0.y, mulmod(addmod((gsrc & 1u) ? v.x : v.y, ad0.y, Md.q), P, Md), Md.q);
+            o1.x = addmod(o1.x, mulmod(ad1.x, P, Md), Md.q);
+            o1.y = addmod(o1.y, mulmod(ad1.y, P, Md), Md.q);
+        } else {
+            o0.x = addmod(o0.x, mulmod((gsrc & 1u) ? v.y : v.x, P, Md), Md.q);
+            o0.y = addmod(o0.y, mulmod((gsrc & 1u) ? v.x : v.y, P, Md), Md.q);
+        }
     }
     if (mi < ell) {
         *reinterpret_cast<u64x2 *>(accq + (((size_t)b * 2 + 0) * ell + mi) * N + k) = o0;
@@ -194,7 +224,8 @@ __global__ __launch_bounds__(kHT) void hyb_mac_kernel(u64 *__restrict__ accq, u6
 
 // lazy sums (option hyb_lazy_sum; hybrid_fused.hip hybf_rotate_sum): the inner products of ALL rotations of a group into ONE accumulator pair.
 // grid = (N/512, groups, M); groups[g]: elt = first item, slot = item count.  Per item exactly hyb_mac_kernel<0>'s arithmetic (its own key,
-// Galois map, decomposition slot and base term P galois(c0)), reduced to the canonical residue and added to the running sum -- so the sum equals
+// Galois map, decomposition slot and base term P galois(c0); KsItem::add is NOT read: a group member has no addend, hyb_launch_mac_groups), reduced
+// to the canonical residue and added to the running sum -- so the sum equals
 // the sum of the items' accumulators limb for limb, and no item's accumulator crosses HBM (2 (l + ksp) limbs written and read again per
 // item otherwise: a third of this kernel's traffic at 12 primes, where a convolution's sums run).
 __global__ __launch_bounds__(kHT) void hyb_mac_group_kernel(u64 *__restrict__ accq, u64 *__restrict__ accp, const u64 *__restrict__ ext,
@@ -316,7 +347,8 @@ __global__ __launch_bounds__(kHT) void hyb_final_kernel(const u64 *__restrict__ 
     const u64 *base;
     if (MODE == 0) {
         const KsItem it = items ? static_cast<const KsItem *>(items)[b] : rot_single;
-        dst = it.dst.limb(c, i, N) + k, base = c == 0 ? dst : nullptr; // c0 holds the permuted source c0 (prepare), c1 starts at zero
+        // c0 holds the permuted source c0 (prepare); c1 starts at zero, or at the addend's c1 that prepare put there
+        dst = it.dst.limb(c, i, N) + k, base = (c == 0 || it.add.p) ? dst : nullptr;
     } else if (MODE == 1) {
         const MulItem it = static_cast<const MulItem *>(items)[b];
         dst = it.dst.limb(c, i, N) + k, base = dst;                     // the tensor product's c0 / c1
@@ -555,8 +587,15 @@ void hyb_launch_conv(Context &c, bool down, bool prescaled, const u64 *in, u64 *
 }
 
 // lazy sums: G groups of rotation items -> accq = w.acc [2G][ell][N], accp behind it [2G][ksp][N]
-void hyb_launch_mac_groups(Context &c, const BatchWs &w, const KsItem *items, const KsItem *groups, int G, int use_slots, int ell, hipStream_t s)
+// `addend`: what the caller knows of the items' KsItem::add.  A member of a group has none -- the kernels of a lazy sum do not read the field
+// (an addend on a group would be ks_flatten_sums under grouped digits, which does not exist) -- so a table that carries one is a planner's error
+void hyb_launch_mac_groups(Context &c, const BatchWs &w, const KsItem *items, const KsItem *groups, int G, int use_slots, int ell, hipStream_t s,
+                           bool addend)
 {
+    if (addend) {
+        fprintf(stderr, "[dacapo_amd] lazy sum: a member of a grouped-digit group carries an addend, which a group does not add (internal error)\n");
+        abort();
+    }
     const size_t N = c.N;
     const int ksp = c.ksp, M = ell + ksp;
     DC_LAUNCH(hyb_mac_group_kernel, dim3((unsigned)(N / (2 * kHT)), (unsigned)G, (unsigned)M), dim3(kHT), 0, s, w.acc,
@@ -566,16 +605,24 @@ void hyb_launch_mac_groups(Context &c, const BatchWs &w, const KsItem *items, co
 
 // inner products with the key: w.ext [U][E][N] (NTT form), w.target (modes 1, 2) -> accq = w.acc [2B][ell][N], accp behind it [2B][ksp][N]
 void hyb_launch_mac(Context &c, int mode, const BatchWs &w, const void *items, KsItem rot_single, const u64 *key, int B, int use_slots, int ell,
-                    hipStream_t s, bool fold_base)
+                    hipStream_t s, bool fold_base, bool addend)
 {
     const size_t N = c.N;
     const int ksp = c.ksp, alpha = c.alpha, L = c.max_level(), K = c.K, M = ell + ksp, E = c.hyb_ext(ell);
     const dim3 grid((unsigned)(N / (2 * kHT)), (unsigned)B, (unsigned)M);
     u64 *accq = w.acc, *accp = w.acc + (size_t)B * 2 * ell * N;
+    if (addend) { // rotation items of a fused sequence, some with KsItem::add (the un-fused sequence adds it in prepare instead)
+        if (mode != 0 || !fold_base) {
+            fprintf(stderr, "[dacapo_amd] hyb_launch_mac: an addend rides on a rotation's folded base term only (internal error)\n");
+            abort();
+        }
+    }
 #define DC_MAC(MD)                                                                                                                        \
     DC_LAUNCH(hyb_mac_kernel<MD>, grid, dim3(kHT), 0, s, accq, accp, w.ext, w.target, items, rot_single, key, ell, ksp, alpha, L, K, E, N, \
                        c.logN, use_slots, c.d_mods, fold_base ? c.d_pmod : (const u64 *)nullptr)
-    if (mode == 0)
+    if (mode == 0 && addend)
+        DC_MAC(3);
+    else if (mode == 0)
         DC_MAC(0);
     else if (mode == 1)
         DC_MAC(1);
@@ -597,7 +644,7 @@ static void hyb_core(Context &c, const BatchWs &w, const void *items, const u64 
     launch_ntt(c, true, w.digits, (long)N, U * ell, nullptr, 0, ell, s);
     hyb_launch_conv(c, false, false, w.digits, w.ext, U, ell, s);
     launch_ntt(c, false, w.ext, (long)N, U * E, c.hyb_pidx(ell), 0, E, s);
-    hyb_launch_mac(c, MODE, w, items, rot_single, MODE == 2 ? single.key : shared_key, B, use_slots, ell, s, false);
+    hyb_launch_mac(c, MODE, w, items, rot_single, MODE == 2 ? single.key : shared_key, B, use_slots, ell, s, false, false);
     launch_ntt(c, true, accp, (long)N, 2 * B * ksp, nullptr, L, ksp, s);
     hyb_launch_conv(c, true, false, accp, w.tmp, 2 * B, ell, s);
     launch_ntt(c, false, w.tmp, (long)N, 2 * B * ell, nullptr, 0, ell, s);
@@ -606,40 +653,46 @@ static void hyb_core(Context &c, const BatchWs &w, const void *items, const u64 
 }
 
 // the fused sequence (hybrid_fused.hip; option hyb_fuse != 0, the default)
-void hybf_rotate_hops(Context &c, const BatchWs &w, const KsItem *d_items, int B, int ell, hipStream_t s, int unique);
-void hybf_rotate_hop_single(Context &c, const Workspace &w, CtView dst, CtView src, u32 galois_elt, const u64 *galois_key, int ell, hipStream_t s);
+void hybf_rotate_hops(Context &c, const BatchWs &w, const KsItem *d_items, int B, int ell, hipStream_t s, int unique, bool addend);
+void hybf_rotate_hop_single(Context &c, const Workspace &w, CtView dst, CtView src, u32 galois_elt, const u64 *galois_key, int ell, hipStream_t s,
+                            CtView add);
 void hybf_mul_relin_tail(Context &c, const BatchWs &w, const MulItem *d_items, const u64 *relin_key, int B, int ell, hipStream_t s);
 void hybf_keyswitch(Context &c, const Workspace &w, CtView out, const u64 *base0, const u64 *base1, const u64 *target, const u64 *key, int ell,
                     hipStream_t s);
-void hybf_rotate_sum(Context &c, const BatchWs &w, const KsItem *d_items, int B, const KsItem *d_groups, int G, int ell, hipStream_t s, int unique);
+void hybf_rotate_sum(Context &c, const BatchWs &w, const KsItem *d_items, int B, const KsItem *d_groups, int G, int ell, hipStream_t s, int unique,
+                     bool addend);
 static bool hyb_fused() { return option(OPT_HYB_FUSE) != 0; }
 bool hyb_lazy_sum_supported(const Context &c) { return c.hybrid() && hyb_fused() && c.N >= 512; }
 
-void hyb_rotate_sum(Context &c, const BatchWs &w, const KsItem *d_items, int B, const KsItem *d_groups, int G, int ell, hipStream_t s, int unique)
+void hyb_rotate_sum(Context &c, const BatchWs &w, const KsItem *d_items, int B, const KsItem *d_groups, int G, int ell, hipStream_t s, int unique,
+                    bool addend)
 {
     if (!hyb_lazy_sum_supported(c)) {
         fprintf(stderr, "[dacapo_amd] lazy sums need the fused grouped-digit sequence (option hyb_fuse != 0)\n");
         abort();
     }
-    hybf_rotate_sum(c, w, d_items, B, d_groups, G, ell, s, unique);
+    hybf_rotate_sum(c, w, d_items, B, d_groups, G, ell, s, unique, addend);
 }
 
-void hyb_rotate_hops(Context &c, const BatchWs &w, const KsItem *d_items, int B, int ell, hipStream_t s, int unique)
+void hyb_rotate_hops(Context &c, const BatchWs &w, const KsItem *d_items, int B, int ell, hipStream_t s, int unique, bool addend)
 {
-    if (hyb_fused()) return hybf_rotate_hops(c, w, d_items, B, ell, s, unique);
+    if (hyb_fused()) return hybf_rotate_hops(c, w, d_items, B, ell, s, unique, addend);
+    // (prepare and final read KsItem::add themselves: this sequence needs no word from the caller)
     const int use_slots = unique > 0 ? 1 : 0, U = use_slots ? unique : B;
     DC_LAUNCH(hyb_prepare_rot_kernel, dim3((unsigned)(c.N / (2 * kHT)), (unsigned)ell, (unsigned)B), dim3(kHT), 0, s, d_items, KsItem{},
-                       w.digits, ell, c.N, c.logN, use_slots);
+                       w.digits, ell, c.N, c.logN, use_slots, c.d_mods);
     hyb_core<0>(c, w, d_items, nullptr, HybSingle{}, KsItem{}, B, U, use_slots, ell, s);
 }
 
-void hyb_rotate_hop_single(Context &c, const Workspace &w, CtView dst, CtView src, u32 galois_elt, const u64 *galois_key, int ell, hipStream_t s)
+void hyb_rotate_hop_single(Context &c, const Workspace &w, CtView dst, CtView src, u32 galois_elt, const u64 *galois_key, int ell, hipStream_t s,
+                           CtView add)
 {
-    if (hyb_fused()) return hybf_rotate_hop_single(c, w, dst, src, galois_elt, galois_key, ell, s);
-    const KsItem it{ src, dst, galois_key, galois_elt, 0 };
+    if (hyb_fused()) return hybf_rotate_hop_single(c, w, dst, src, galois_elt, galois_key, ell, s, add);
+    KsItem it{ src, dst, galois_key, galois_elt, 0 };
+    it.add = add;
     BatchWs bw{ nullptr, w.ks_digits, w.ks_ext, w.ks_acc, w.ks_tmp };
     DC_LAUNCH(hyb_prepare_rot_kernel, dim3((unsigned)(c.N / (2 * kHT)), (unsigned)ell, 1), dim3(kHT), 0, s, (const KsItem *)nullptr, it,
-                       w.ks_digits, ell, c.N, c.logN, 0);
+                       w.ks_digits, ell, c.N, c.logN, 0, c.d_mods);
     hyb_core<0>(c, bw, nullptr, nullptr, HybSingle{}, it, 1, 1, 0, ell, s);
 }
 

@@ -32,10 +32,11 @@ struct KsItem {   // one key-switch hop of a rotation: dst = apply_galois(src)
     // double hoisting (option hyb_double_hoist; items of a lazy sum only): the plaintext that multiplies this rotation's result before it joins
     // the sum -- its limbs over the data primes [level][N] and over the special primes [ksp][N] (both NTT form) -- or null
     const u64 *plain = nullptr, *plain_sp = nullptr;
-    // option ks_fold_add (dc_ct_rotate_hop_add): dst = apply_galois(src) + add, add a ciphertext at the hop's level that the fused middle puts
-    // into its accumulators' start values (fused_ks.hip f_ks_frows_mac_kernel) -- exact, no launch of its own; p == nullptr: no addend.  It may
-    // be src or dst.  Only b_rotate_hops on SEAL-layout keys with the fused middle reads it (it aborts where the middle is not fused); the
-    // grouped-digit, hoisted and lazy-sum kernels ignore it
+    // options ks_fold_add / hyb_fold_add (dc_ct_rotate_hop_add): dst = apply_galois(src) + add, add a ciphertext at the hop's level (NTT form)
+    // that enters the data-prime accumulators as P add -- exact, no launch of its own; p == nullptr: no addend.  It may be src or dst.
+    // SEAL-layout keys: the fused middle's start values (fused_ks.hip f_ks_frows_mac_kernel); b_rotate_hops aborts where the middle is not fused.
+    // Grouped digits: every launch form of a rotation hop (hybrid_ks.hip hyb_mac_kernel<3> beside the base term; hyb_prepare_rot_kernel in the
+    // un-fused sequence).  The hoisted (ks_hoist) and every lazy-sum kernel ignore it
     CtView add = CtView{ nullptr, 0 };
 };
 struct MulItem {  // dst = relinearize(a * b)
@@ -138,7 +139,7 @@ struct BatchWs {
 };
 
 // `unique`: grouped-digit mode only -- the number of distinct decompositions the items' `slot` fields name (0: every item its own)
-// `addend`: some item carries one (KsItem::add); aborts unless the batch's shape carries one (launch_shape.hpp carries_addend)
+// `addend`: some item carries one (KsItem::add); SEAL-layout keys: aborts unless the batch's shape carries one (launch_shape.hpp carries_addend)
 void b_rotate_hops(Context &c, const BatchWs &w, const KsItem *d_items, int B, int ell, hipStream_t s, const Handoff &h = Handoff{}, int unique = 0,
                    bool addend = false);
 void b_mul_relin(Context &c, const BatchWs &w, const MulItem *d_items, const u64 *relin_key, int B, int ell, hipStream_t s,
@@ -166,13 +167,17 @@ void hoist_rotate_hops(Context &c, const BatchWs &w, const KsItem *d_items, cons
 void hoist_rotate_sum(Context &c, const BatchWs &w, const KsItem *d_items, const KsItem *d_sources, int B, int U, const KsItem *d_groups, int G,
                       int ell, hipStream_t s, bool addend = false);
 // grouped-digit hybrid key switching (hybrid_ks.hip; Context::hybrid()): b_rotate_hops / b_mul_relin / keyswitch route here
-void hyb_rotate_hops(Context &c, const BatchWs &w, const KsItem *d_items, int B, int ell, hipStream_t s, int unique = 0);
+// `addend`: some item carries one (KsItem::add); items with and without one share the launches
+void hyb_rotate_hops(Context &c, const BatchWs &w, const KsItem *d_items, int B, int ell, hipStream_t s, int unique = 0, bool addend = false);
 // lazy sums (option hyb_lazy_sum): the B items' accumulators are added group by group and divided by P once per group.  d_groups[g]: dst = the
 // sum's destination, elt = first item of the group, slot = its item count (a group's items are adjacent in d_items; their own dst is unused)
-void hyb_rotate_sum(Context &c, const BatchWs &w, const KsItem *d_items, int B, const KsItem *d_groups, int G, int ell, hipStream_t s, int unique = 0);
+// `addend`: an item carries one -- a group adds none, so this aborts (the plan never folds a sum into a group's member)
+void hyb_rotate_sum(Context &c, const BatchWs &w, const KsItem *d_items, int B, const KsItem *d_groups, int G, int ell, hipStream_t s, int unique = 0,
+                    bool addend = false);
 bool hyb_lazy_sum_supported(const Context &c);
-// one rotation hop by value (the one-instruction-at-a-time loop): src must not alias dst
-void hyb_rotate_hop_single(Context &c, const Workspace &w, CtView dst, CtView src, u32 galois_elt, const u64 *galois_key, int ell, hipStream_t s);
+// one rotation hop by value (the one-instruction-at-a-time loop): src must not alias dst; add: KsItem::add (it may be src or dst), null for none
+void hyb_rotate_hop_single(Context &c, const Workspace &w, CtView dst, CtView src, u32 galois_elt, const u64 *galois_key, int ell, hipStream_t s,
+                           CtView add = CtView{ nullptr, 0 });
 void hyb_mul_relin(Context &c, const BatchWs &w, const MulItem *d_items, const u64 *relin_key, int B, int ell, hipStream_t s);
 void hyb_keyswitch(Context &c, const Workspace &w, CtView out, const u64 *base0, const u64 *base1, const u64 *target, const u64 *key, int ell,
                    hipStream_t s);

@@ -656,7 +656,7 @@ void HEVM::build_plan()
         }
     };
     asap_waves();
-    // ---- 3a. rotate-and-add (option ks_fold_add; SEAL-layout keys, the fused middle) ------------------------------------------------------
+    // ---- 3a. rotate-and-add (option ks_fold_add: SEAL-layout keys, the fused middle; option hyb_fold_add: grouped digits) ------------------
     // y' = y + rotate(y, o), the stage of a reduction tree: the sum has two readers (the next stage's rotation and its add), so it folds into
     // neither and would be a step of its own, one wave and one dependent launch behind the key switch.  Instead the rotation's LAST hop takes
     // the other term as its addend (plan.hpp KsItem::add: a start value of the fused middle's accumulators, exact) and writes the sum's value
@@ -666,7 +666,11 @@ void HEVM::build_plan()
     // and two rotations of one wave that are added together keep their shared batch -- and made by an earlier pseudo-op (the list stays in
     // dataflow order).  The sum's level and scale stay as the walk fixed them.  The addend is the hop's second source from here on: waves,
     // lifetimes and the steps' read sets count it like the first.
-    if (ks_fold_add) {
+    // Grouped digits (option hyb_fold_add; ks_fold_add is a no-op there and hyb_fold_add one on SEAL-layout keys): the same rule without the
+    // launch-shape test -- every launch form of a grouped-digit rotation hop carries an addend (hybrid_ks.hip).  "Default rotation hop" reads the
+    // same way: the last hop of a rotate instruction on the VM's own context; the boot context's KEYSWITCH hops have no instruction, and the
+    // members of a lazy sum or of a double-hoisted tap (section 2b) are no P_ROT pops any more -- a group takes no addend.
+    if (c.hybrid() ? hyb_fold_add : ks_fold_add) {
         std::vector<int> asap(O.size(), 0); // (the unfolded plan's waves: a fold below must not change what a later one compares)
         for (size_t i = 0; i < O.size(); i++) asap[i] = O[i].wave;
         std::set<int> folded; // the sums' values that a rotation defines now
@@ -675,7 +679,7 @@ void HEVM::build_plan()
             if (s.dead || s.kind != P_SUM || s.srcs.size() != 2) continue;
             if (std::any_of(s.src_plain.begin(), s.src_plain.end(), [](int pl) { return pl >= 0; })) continue;
             // (the middle stays one launch for every batch a step of this level can hold)
-            if (!ks_shape(c, (int)step_chunk(P_ROT) * S, s.level).carries_addend()) continue;
+            if (!c.hybrid() && !ks_shape(c, (int)step_chunk(P_ROT) * S, s.level).carries_addend()) continue;
             for (size_t w = 0; w < 2; w++) {
                 const int hv = s.srcs[w], a = s.srcs[1 - w], hi = own_pop(hv);
                 if (hi < 0 || a == hv) continue;
@@ -1494,10 +1498,10 @@ void HEVM::report_plan(const double (&sum_stat)[5], int max_wave, int levels_mov
                 plan_level, levels_moved, P.steps.size(), max_wave, multi, P.n_fused, launches - P.n_fused, P.max_live, P.pool.size(),
                 (double)P.pool.size() * buf_elems * (double)streams * 8 / 1e9);
     }
-    // (option ks_fold_add; no line without a fold, so that the option's 0 prints the plan as it was before the option existed)
+    // (options ks_fold_add / hyb_fold_add; no line without a fold, so that the option's 0 prints the plan as it was before the option existed)
     if (P.n_add_folds)
-        fprintf(stderr, "[dacapo_amd] plan folds: %lld two-term sums ride on their rotation's last hop as its addend (option ks_fold_add)\n",
-                (long long)P.n_add_folds);
+        fprintf(stderr, "[dacapo_amd] plan folds: %lld two-term sums ride on their rotation's last hop as its addend (option %s)\n",
+                (long long)P.n_add_folds, ctx->hybrid() ? "hyb_fold_add" : "ks_fold_add");
 }
 
 // the launches of one step, on stream q, with the scratch of the step's lane
@@ -1519,7 +1523,7 @@ void HEVM::issue_step(const Step &st, hipStream_t q)
                              st.addend);
             break;
         }
-        hyb_rotate_sum(c, w, P.d_ks + st.first, st.count, P.d_ks + st.gfirst, st.gcount, st.level, q, st.unique); break;
+        hyb_rotate_sum(c, w, P.d_ks + st.first, st.count, P.d_ks + st.gfirst, st.gcount, st.level, q, st.unique, st.addend); break;
     case P_MULCC:
         if (st.fold_rs) {
             b_mul_relin_rescale(c, w, P.d_mulrs + st.first, keys.relin, st.count, st.level, q, st.h);

@@ -547,7 +547,7 @@ class HEVM:
         ks, ntt = ctypes.c_int64(), ctypes.c_int64()
         self.lw.hevm_last_run_stats(self.vm, counts, ctypes.byref(ks), ctypes.byref(ntt))
         return {"op_counts": list(counts), "keyswitches": ks.value, "ntts": ntt.value,
-                "add_folds": int(self.lw.hevm_last_run_add_fold_stats(self.vm)),  # option ks_fold_add: sums computed inside a rotation's last hop
+                "add_folds": int(self.lw.hevm_last_run_add_fold_stats(self.vm)),  # options ks_fold_add / hyb_fold_add: sums computed inside a rotation's last hop
                 "bootstrap_s": float(self.lw.hevm_last_run_bootstrap_seconds(self.vm))}
 
     def printer(self, latency, rms, mem_usage=0.0):  # runner.py:256-271
