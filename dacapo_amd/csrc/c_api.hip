@@ -429,6 +429,34 @@ void dc_ct_rotate_sum_hoisted_add(dc_context *ctx, uint64_t *dst, long dst_strid
     rotate_sum_hoisted(ctx, "dc_ct_rotate_sum_hoisted_add", dst, dst_stride, addend, addend_stride, srcs, src_stride, galois_elts, galois_keys,
                        plains, plains_sp, count, ell, stream);
 }
+// EXTENSION, grouped digits: dst = addend + sum_k galois_k(src) with ONE decomposition of src and ONE division by P (hybrid_fused.hip
+// hybf_rotate_stages, hybrid_ks.hip hyb_mac_stage_kernel): a stage of a flattened rotate-and-add chain.  One source, so the decomposition, the
+// accumulator pair and the correction live in the context's default workspace; only the member table is kept in the handle and copied as
+// dc_ct_rotate_sum_hoisted copies its own.  dst is written by the last launch only: addend and dst may be src.
+void dc_ct_rotate_stage_add(dc_context *ctx, uint64_t *dst, long dst_stride, const uint64_t *addend, long addend_stride, const uint64_t *src,
+                            long src_stride, const uint32_t *galois_elts, const uint64_t *const *galois_keys, int count, int ell, void *stream)
+{
+    Context &c = *ctx->c;
+    if (!c.hybrid()) {
+        fprintf(stderr, "[dacapo_amd] dc_ct_rotate_stage_add: this context switches keys with SEAL-layout keys (ks_special = 1); the call is for "
+                        "grouped digits (use dc_ct_rotate_sum_hoisted_add)\n");
+        abort();
+    }
+    if (count < 1 || count > 65535 || ell < 1 || ell > c.max_level()) {
+        fprintf(stderr, "[dacapo_amd] dc_ct_rotate_stage_add: %d members at level %d (1..65535 members, level 1..%d)\n", count, ell, c.max_level());
+        abort();
+    }
+    const size_t B = (size_t)count;
+    std::vector<KsItem> h;
+    for (size_t b = 0; b < B; b++) h.push_back(KsItem{ V(src, src_stride), V(dst, dst_stride), galois_keys[b], galois_elts[b], 0 });
+    h.push_back(KsItem{ addend ? V(addend, addend_stride) : CtView{ nullptr, 0 }, V(dst, dst_stride), nullptr, 0u, (u32)B });
+    grow_scratch(ctx->hoist_items, ctx->hoist_item_cap, h.size() * sizeof(KsItem));
+    DC_HIP_CHECK(hipMemcpyAsync(ctx->hoist_items, h.data(), h.size() * sizeof(KsItem), hipMemcpyHostToDevice, S(stream)));
+    DC_HIP_CHECK(hipStreamSynchronize(S(stream))); // (the host table goes out of scope)
+    const KsItem *d = static_cast<const KsItem *>(ctx->hoist_items);
+    const BatchWs w{ nullptr, c.ws0.ks_digits, c.ws0.ks_ext, c.ws0.ks_acc, c.ws0.ks_tmp };
+    hyb_rotate_stages(c, w, d, count, d + B, 1, ell, S(stream), 1);
+}
 void dc_ct_rescale(dc_context *ctx, uint64_t *dst, long dst_stride, const uint64_t *src, long src_stride, int ell, void *stream)
 {
     const RsItem it{ V(src, src_stride), V(dst, dst_stride), 0, 0, nullptr, nullptr }; // element-wise epilogue: in place is fine

@@ -494,7 +494,7 @@ void HEVM::init_context(int logN, int K, const u64 *primes, int dir_ksp, int dir
         }
         if (ksp > 1 || alpha > 1) {
             fprintf(stderr, "[dacapo_amd] option ks_flatten_sums = %d is for SEAL-layout keys (ks_special = 1); with ks_special = %d, ks_alpha = %d key "
-                            "switching uses grouped digits, whose lazy sums take no addend\n", ks_flatten, ksp, alpha);
+                            "switching uses grouped digits, where the option is hyb_flatten_sums (with hyb_lazy_sum)\n", ks_flatten, ksp, alpha);
             abort();
         }
         if (!ks_hoist || !ks_lazy) {
@@ -506,6 +506,31 @@ void HEVM::init_context(int logN, int K, const u64 *primes, int dir_ksp, int dir
         if (option(OPT_ROT_COMPOSE) != 0) {
             fprintf(stderr, "[dacapo_amd] option ks_flatten_sums = %d does not combine with rot_compose = 1: a memoised hop may serve two rotate "
                             "instructions, and a flattened stage takes its rotations' hops away\n", ks_flatten);
+            abort();
+        }
+    }
+    hyb_flatten = (int)option(OPT_HYB_FLATTEN_SUMS);
+    if (hyb_flatten) {
+        if (hyb_flatten < 2 || hyb_flatten > kFlattenMaxHops) {
+            fprintf(stderr, "[dacapo_amd] option hyb_flatten_sums = %d: the most hops one flattened stage absorbs is 2 .. %d (2^%d - 1 = %d rotations "
+                            "of one decomposition), or 0 = off\n", hyb_flatten, kFlattenMaxHops, kFlattenMaxHops, (1 << kFlattenMaxHops) - 1);
+            abort();
+        }
+        if (ksp == 1 && alpha == 1) {
+            fprintf(stderr, "[dacapo_amd] option hyb_flatten_sums = %d is for grouped-digit keys (ks_special > 1); with ks_special = 1 the option is "
+                            "ks_flatten_sums (with ks_hoist and ks_lazy_sum)\n", hyb_flatten);
+            abort();
+        }
+        const bool lazy = option(OPT_HYB_LAZY_SUM) != 0, fused = option(OPT_HYB_FUSE) != 0;
+        if (!lazy || !fused) {
+            fprintf(stderr, "[dacapo_amd] option hyb_flatten_sums = %d needs%s%s%s: a flattened stage is a lazy sum of one source -- its rotations share "
+                            "one division by P (hyb_lazy_sum) in the fused sequence's accumulators (hyb_fuse)\n", hyb_flatten,
+                    lazy ? "" : " hyb_lazy_sum >= 1", !lazy && !fused ? " and" : "", fused ? "" : " hyb_fuse != 0");
+            abort();
+        }
+        if (option(OPT_ROT_COMPOSE) != 0) {
+            fprintf(stderr, "[dacapo_amd] option hyb_flatten_sums = %d does not combine with rot_compose = 1: a memoised hop may serve two rotate "
+                            "instructions, and a flattened stage takes its rotations' hops away\n", hyb_flatten);
             abort();
         }
     }
@@ -1844,7 +1869,7 @@ PlanFlow HEVM::program_flow() const
     return plan_flow(ops.data(), ops.size(), ciphers.size(), res_dst.data(), res_dst.size(), arg_level.data(), arg_level.size());
 }
 
-// Option ks_flatten_sums: the stages of the loaded program's rotate-and-add chains that one hoisted lazy sum with an addend can run
+// Options ks_flatten_sums / hyb_flatten_sums: the stages of the loaded program's rotate-and-add chains that one lazy sum with an addend can run
 // (plan_flatten.hpp), found on the program's flow.  every_key: as if every offset had a key (what hevm_flatten_offsets asks); otherwise a
 // stage needs a key for each of its members in this VM's key set.
 std::vector<FlattenGroup> HEVM::flatten_groups(const PlanFlow &flow, bool every_key) const
@@ -1858,7 +1883,7 @@ std::vector<FlattenGroup> HEVM::flatten_groups(const PlanFlow &flow, bool every_
             if (keys.galois.count((u32)e)) keyed.push_back(flatten_norm_offset(k, slots));
         std::sort(keyed.begin(), keyed.end());
     }
-    return flow_flatten_groups(flow, ops.data(), ks_flatten, slots, every_key ? nullptr : keyed.data(), (int)keyed.size());
+    return flow_flatten_groups(flow, ops.data(), flatten_hops(), slots, every_key ? nullptr : keyed.data(), (int)keyed.size());
 }
 
 // EXTENSION (option rot_compose = 1; off by default: SEAL's rotate_internal only ever composes from the power-of-two keys): a bounded key
@@ -2721,14 +2746,14 @@ int64_t hevm_plan_lazy_groups(void *vm, int32_t *out, int64_t cap)
     return (int64_t)flat.size();
 }
 
-// option ks_flatten_sums: the distinct composite slot offsets that the loaded program's flattened stages would use at the VM's option value and
+// options ks_flatten_sums / hyb_flatten_sums: the distinct composite slot offsets that the loaded program's flattened stages would use at the VM's option value and
 // that have no key in its key set yet -- what a caller hands to hevm_add_rotation_keys before the first run() (and before a server's key
 // directory is written).  Writes up to cap of them, ascending; returns how many there are.  0 with the option off, under plan = 0 or with
 // nothing loaded.
 int hevm_flatten_offsets(void *vm, int64_t *out, int cap)
 {
     auto h = V(vm);
-    if (!h->ks_flatten || !h->use_plan || h->ops.empty()) return 0; // (plan = 0 runs every rotate on its own)
+    if (!h->flatten_hops() || !h->use_plan || h->ops.empty()) return 0; // (plan = 0 runs every rotate on its own)
     std::set<int> missing;
     for (const dacapo::FlattenGroup &g : h->flatten_groups(h->program_flow(), true))
         for (int o : g.offsets) {

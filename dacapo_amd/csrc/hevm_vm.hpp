@@ -323,6 +323,10 @@ class HEVM {
     // option ks_flatten_sums = f (2 .. 6; with ks_hoist and ks_lazy_sum): stages of up to f hops of a rotate-and-add chain run as one hoisted lazy
     // sum with an addend (plan_exec.hip section 1a; plan_flatten.hpp names the groups).  Changes the rounding: off by default.
     int ks_flatten = 0;
+    // option hyb_flatten_sums = f (2 .. 6; grouped digits, with hyb_lazy_sum and hyb_fuse != 0): the same pass and the same P_ROTSUM with an addend; a
+    // stage runs through hyb_rotate_stages (hybrid_ks.hip hyb_mac_stage_kernel) in steps of its own.  Changes the rounding: off by default.
+    int hyb_flatten = 0;
+    int flatten_hops() const { return ks_flatten ? ks_flatten : hyb_flatten; } // (at most one of the two is set: each aborts in the other's mode)
     // option ks_fold_add = 1 (SEAL-layout keys): y + rotate(x, o) is the rotation's own last hop with y as its addend (plan_exec.hip section 3a;
     // plan.hpp KsItem::add).  Every limb equals the default path's.  The loop (plan = 0) runs the instructions as written.
     bool ks_fold_add = true;

@@ -320,6 +320,7 @@ void hyb_launch_mac(Context &c, int mode, const BatchWs &w, const void *items, K
 void hyb_launch_conv(Context &c, bool down, bool prescaled, const u64 *in, u64 *out, int count, int ell, hipStream_t s);
 void hyb_launch_mac_groups(Context &c, const BatchWs &w, const KsItem *items, const KsItem *groups, int G, int use_slots, int ell, hipStream_t s,
                            bool addend);
+void hyb_launch_mac_stages(Context &c, const BatchWs &w, const KsItem *items, const KsItem *stages, int G, int ell, hipStream_t s);
 
 // F2 ... F5: everything between F1 and the accumulators.  digits [U][ell][N] hold the inverse ROWS phase's output.
 template <int MODE>
@@ -431,6 +432,25 @@ void hybf_rotate_sum(Context &c, const BatchWs &w, const KsItem *d_items, int B,
     DC_LAUNCH(hybf_group_sum_kernel, dim3((unsigned)(N / 512), (unsigned)(ell + ksp), (unsigned)(2 * G)), dim3(256), 0, s, w.acc,
               w.acc + (size_t)B * 2 * ell * N, gq, gp, d_items, d_groups, ell, ksp, c.max_level(), N, c.d_mods);
     hybf_back<0>(c, w, gq, gp, d_groups, KsItem{}, HybOut{}, G, ell, s);
+}
+
+// flattened rotate-and-add stages (option hyb_flatten_sums, dc_ct_rotate_stage_add): B members in G stages of ONE source each -> G results
+// y_g + sum of the stage's rotations of its source.  F1 ... F4 for the `unique` distinct sources (every member's slot names its source's:
+// use_slots), hyb_mac_stage_kernel for the accumulators -- the addend rides there --, F6 ... F9 once per stage.  d_stages[g]: src = the addend
+// (p == nullptr: none), dst, elt = first member, slot = member count (a stage's members are adjacent; one member is a stage).  Scratch: the
+// accumulators and corrections of G <= B pairs and `unique` <= B decompositions fit what B items reserve.
+void hybf_rotate_stages(Context &c, const BatchWs &w, const KsItem *d_items, int B, const KsItem *d_stages, int G, int ell, hipStream_t s, int unique)
+{
+    const size_t N = c.N;
+    if (G < 1 || G > B || unique < 1 || unique > B || N < 512) {
+        fprintf(stderr, "[dacapo_amd] flattened stages: %d stages of %d members over %d sources do not fit the step's scratch (internal error)\n", G, B,
+                unique);
+        abort();
+    }
+    f1_irows<0>(c, d_items, KsItem{}, nullptr, w.digits, B, ell, 1, s);
+    hybf_front<0>(c, w, d_items, KsItem{}, nullptr, B, unique, 1, ell, s, false);
+    hyb_launch_mac_stages(c, w, d_items, d_stages, G, ell, s);
+    hybf_back<0>(c, w, w.acc, w.acc + (size_t)G * 2 * ell * N, d_stages, KsItem{}, HybOut{}, G, ell, s);
 }
 
 // `addend`: some item carries one (KsItem::add) -- F5 then runs as hyb_mac_kernel<3>; F1 (first item of a slot) and F9 do not look at it

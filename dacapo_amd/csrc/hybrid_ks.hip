@@ -294,6 +294,106 @@ __global__ __launch_bounds__(kHT) void hyb_mac_group_kernel(u64 *__restrict__ ac
     }
 }
 
+// flattened rotate-and-add stages (option hyb_flatten_sums, dc_ct_rotate_stage_add; hybrid_fused.hip hybf_rotate_stages): a stage is ONE source
+// ciphertext x, `count` members (Galois element and key each, no plaintext) and an optional addend y -> one accumulator pair of
+// y + sum_t galois_t(x).  grid = (N/512, stages, M); stages[s]: src = the addend (p == nullptr: none; stage-uniform, a launch may mix both),
+// elt = first member, slot = member count; the members name one source and one decomposition slot (the first member's are read).
+// The one-source form of hyb_mac_group_kernel, and what only a stage allows:
+//   * no member is multiplied by a plaintext, so the Acc128 pairs run ACROSS members and are reduced every floor(16 / G) members only -- the
+//     residue restarts the sum as one word: at most 16 products of canonical residues plus a word below q, below 2^(2b+4), the range the
+//     reduction takes (b = 60: 2^124).  The residue of a sum is the sum of residues: the limbs are hyb_mac_group_kernel's;
+//   * the base terms meet P once: galois_t(x.c0) are added as they go by, y0 joins them, one mulmod by P per coefficient (polynomial 1: P y1);
+//     a special prime has no base and reads no addend, so acc_P and the mod-down's correction are those of the bare sum;
+//   * member t + 1's first digit, first key pair and c0 pair are issued before member t's last products: the prefetch never restarts.
+// y is read at index k (no gather) before anything is written, and dst is written by F9 only: y may be the source or the destination.
+__global__ __launch_bounds__(kHT) void hyb_mac_stage_kernel(u64 *__restrict__ accq, u64 *__restrict__ accp, const u64 *__restrict__ ext,
+                                                            const KsItem *__restrict__ items, const KsItem *__restrict__ stages, int ell, int ksp,
+                                                            int alpha, int L, int K, int E, size_t N, int logN, const DModulus *__restrict__ mods,
+                                                            const u64 *__restrict__ pmod)
+{
+    const int mi = blockIdx.z, sg = blockIdx.y, M = ell + ksp, pm = mi < ell ? mi : L + (mi - ell);
+    const DModulus Md = mods[pm];
+    const u32 first = stages[sg].elt, count = stages[sg].slot;
+    const CtView add = stages[sg].src;
+    const bool data = mi < ell, has_add = data && add.p != nullptr;
+    const size_t k = ((size_t)blockIdx.x * kHT + threadIdx.x) * 2;
+    const int G = (ell + alpha - 1) / alpha;
+    const u32 every = (u32)(16 / G); // members between two reductions (G <= 16: hyb_launch_mac_stages)
+    const CtView src = items[first].src;
+    const u64 *xe = ext + (size_t)items[first].slot * E * N;
+    // digit g of the member whose Galois index is gs and whose key is `key`: the raised limb of this modulus, or x.c1 itself in its own digit
+    auto fetch = [&](int g, u32 gs, const u64 *key, u64x2 &x, u64x2 &y0, u64x2 &y1) {
+        const int lo = g * alpha, hi = min(lo + alpha, ell);
+        const bool own = mi >= lo && mi < hi;
+        const u64 *op = own ? src.limb(1, mi, N) : xe + ((size_t)g * (M - alpha) + (mi < lo ? mi : mi - (hi - lo))) * N;
+        x = *reinterpret_cast<const u64x2 *>(op + (gs & ~1u));
+        y0 = *reinterpret_cast<const u64x2 *>(key + (((size_t)g * 2 + 0) * K + pm) * N + k);
+        y1 = *reinterpret_cast<const u64x2 *>(key + (((size_t)g * 2 + 1) * K + pm) * N + k);
+    };
+    u32 gs = galois_idx((u32)k, items[first].elt, logN), gsn = gs;
+    const u64 *key = items[first].key, *keyn = key;
+    u64x2 xn, y0n, y1n, vn{ 0, 0 };
+    fetch(0, gs, key, xn, y0n, y1n);
+    if (data) vn = *reinterpret_cast<const u64x2 *>(src.limb(0, mi, N) + (gs & ~1u));
+    u64x2 ad0{ 0, 0 }, ad1{ 0, 0 };
+    if (has_add) {
+        ad0 = *reinterpret_cast<const u64x2 *>(add.limb(0, mi, N) + k);
+        ad1 = *reinterpret_cast<const u64x2 *>(add.limb(1, mi, N) + k);
+    }
+    Acc128 a0[2], a1[2];
+#pragma unroll
+    for (int e = 0; e < 2; e++) a0[e].clear(), a1[e].clear();
+    u64x2 b0{ 0, 0 }; // sum_t galois_t(x.c0), canonical
+    u32 since = 0;
+    for (u32 t = 0; t < count; t++) {
+        const u64x2 v = vn;
+        for (int g = 0; g < G; g++) {
+            u64x2 x = xn;
+            const u64x2 y0 = y0n, y1 = y1n;
+            if (g + 1 < G)
+                fetch(g + 1, gs, key, xn, y0n, y1n);
+            else if (t + 1 < count) {
+                const KsItem &nx = items[first + t + 1];
+                gsn = galois_idx((u32)k, nx.elt, logN), keyn = nx.key;
+                fetch(0, gsn, keyn, xn, y0n, y1n);
+                if (data) vn = *reinterpret_cast<const u64x2 *>(src.limb(0, mi, N) + (gsn & ~1u));
+            }
+            if (gs & 1u) x = u64x2{ x.y, x.x };
+#pragma unroll
+            for (int e = 0; e < 2; e++) {
+                a0[e].mac(x[e], y0[e]);
+                a1[e].mac(x[e], y1[e]);
+            }
+        }
+        if (data) b0.x = addmod(b0.x, (gs & 1u) ? v.y : v.x, Md.q), b0.y = addmod(b0.y, (gs & 1u) ? v.x : v.y, Md.q);
+        gs = gsn, key = keyn;
+        if (++since == every && t + 1 < count) { // the next member's G products would leave the 16-product window
+            since = 0;
+#pragma unroll
+            for (int e = 0; e < 2; e++) {
+                a0[e].lo = a0[e].reduce(Md), a0[e].hi = 0;
+                a1[e].lo = a1[e].reduce(Md), a1[e].hi = 0;
+            }
+        }
+    }
+    u64x2 o0, o1;
+#pragma unroll
+    for (int e = 0; e < 2; e++) o0[e] = a0[e].reduce(Md), o1[e] = a1[e].reduce(Md);
+    if (data) {
+        const u64 P = pmod[pm];
+        if (has_add) {
+            b0.x = addmod(b0.x, ad0.x, Md.q), b0.y = addmod(b0.y, ad0.y, Md.q);
+            o1.x = addmod(o1.x, mulmod(ad1.x, P, Md), Md.q), o1.y = addmod(o1.y, mulmod(ad1.y, P, Md), Md.q);
+        }
+        o0.x = addmod(o0.x, mulmod(b0.x, P, Md), Md.q), o0.y = addmod(o0.y, mulmod(b0.y, P, Md), Md.q);
+        *reinterpret_cast<u64x2 *>(accq + (((size_t)sg * 2 + 0) * ell + mi) * N + k) = o0;
+        *reinterpret_cast<u64x2 *>(accq + (((size_t)sg * 2 + 1) * ell + mi) * N + k) = o1;
+    } else {
+        *reinterpret_cast<u64x2 *>(accp + (((size_t)sg * 2 + 0) * ksp + (mi - ell)) * N + k) = o0;
+        *reinterpret_cast<u64x2 *>(accp + (((size_t)sg * 2 + 1) * ksp + (mi - ell)) * N + k) = o1;
+    }
+}
+
 // mod-down base conversion: accp [2B][ksp][N] (coefficient domain) -> tmp [2B][l][N].  grid = (N/512, 2B)
 __global__ __launch_bounds__(kHT) void hyb_moddown_kernel(const u64 *__restrict__ accp, u64 *__restrict__ tmp, int ell, int ksp, int L, size_t N,
                                                            const DModulus *__restrict__ mods, const u64 *__restrict__ dn)
@@ -588,7 +688,7 @@ void hyb_launch_conv(Context &c, bool down, bool prescaled, const u64 *in, u64 *
 
 // lazy sums: G groups of rotation items -> accq = w.acc [2G][ell][N], accp behind it [2G][ksp][N]
 // `addend`: what the caller knows of the items' KsItem::add.  A member of a group has none -- the kernels of a lazy sum do not read the field
-// (an addend on a group would be ks_flatten_sums under grouped digits, which does not exist) -- so a table that carries one is a planner's error
+// (a flattened stage, which has one, is no plain group: hyb_launch_mac_stages) -- so a table that carries one is a planner's error
 void hyb_launch_mac_groups(Context &c, const BatchWs &w, const KsItem *items, const KsItem *groups, int G, int use_slots, int ell, hipStream_t s,
                            bool addend)
 {
@@ -601,6 +701,21 @@ void hyb_launch_mac_groups(Context &c, const BatchWs &w, const KsItem *items, co
     DC_LAUNCH(hyb_mac_group_kernel, dim3((unsigned)(N / (2 * kHT)), (unsigned)G, (unsigned)M), dim3(kHT), 0, s, w.acc,
               w.acc + (size_t)G * 2 * ell * N, w.ext, items, groups, ell, ksp, c.alpha, c.max_level(), c.K, c.hyb_ext(ell), N, c.logN, use_slots, c.d_mods,
               c.d_pmod);
+}
+
+// flattened stages: G stages of one source each -> accq = w.acc [2G][ell][N], accp behind it [2G][ksp][N].  Every member's slot names its
+// source's decomposition in w.ext (use_slots); a stage's addend is its entry's src (hyb_mac_stage_kernel)
+void hyb_launch_mac_stages(Context &c, const BatchWs &w, const KsItem *items, const KsItem *stages, int G, int ell, hipStream_t s)
+{
+    const size_t N = c.N;
+    const int ksp = c.ksp, M = ell + ksp;
+    if (c.hyb_groups(ell) > 16) {
+        fprintf(stderr, "[dacapo_amd] flattened stage: %d digits at level %d; the stage kernel's accumulators hold 16 products between two "
+                        "reductions\n", c.hyb_groups(ell), ell);
+        abort();
+    }
+    DC_LAUNCH(hyb_mac_stage_kernel, dim3((unsigned)(N / (2 * kHT)), (unsigned)G, (unsigned)M), dim3(kHT), 0, s, w.acc,
+              w.acc + (size_t)G * 2 * ell * N, w.ext, items, stages, ell, ksp, c.alpha, c.max_level(), c.K, c.hyb_ext(ell), N, c.logN, c.d_mods, c.d_pmod);
 }
 
 // inner products with the key: w.ext [U][E][N] (NTT form), w.target (modes 1, 2) -> accq = w.acc [2B][ell][N], accp behind it [2B][ksp][N]
@@ -672,6 +787,17 @@ void hyb_rotate_sum(Context &c, const BatchWs &w, const KsItem *d_items, int B, 
         abort();
     }
     hybf_rotate_sum(c, w, d_items, B, d_groups, G, ell, s, unique, addend);
+}
+
+void hybf_rotate_stages(Context &c, const BatchWs &w, const KsItem *d_items, int B, const KsItem *d_stages, int G, int ell, hipStream_t s, int unique);
+void hyb_rotate_stages(Context &c, const BatchWs &w, const KsItem *d_items, int B, const KsItem *d_stages, int G, int ell, hipStream_t s, int unique)
+{
+    if (!hyb_lazy_sum_supported(c)) {
+        fprintf(stderr, "[dacapo_amd] flattened stages need what lazy sums need (hyb_lazy_sum_supported): grouped digits, the fused sequence "
+                        "(option hyb_fuse != 0) and N >= 512\n");
+        abort();
+    }
+    hybf_rotate_stages(c, w, d_items, B, d_stages, G, ell, s, unique);
 }
 
 void hyb_rotate_hops(Context &c, const BatchWs &w, const KsItem *d_items, int B, int ell, hipStream_t s, int unique, bool addend)

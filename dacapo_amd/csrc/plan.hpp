@@ -175,6 +175,11 @@ void hyb_rotate_hops(Context &c, const BatchWs &w, const KsItem *d_items, int B,
 void hyb_rotate_sum(Context &c, const BatchWs &w, const KsItem *d_items, int B, const KsItem *d_groups, int G, int ell, hipStream_t s, int unique = 0,
                     bool addend = false);
 bool hyb_lazy_sum_supported(const Context &c);
+// flattened rotate-and-add stages (option hyb_flatten_sums, dc_ct_rotate_stage_add): G stages of one source ciphertext each, B members in all
+// (adjacent per stage, each with the slot of its source's decomposition among the `unique` distinct sources), one division by P per stage.
+// d_stages[g]: src = the stage's addend at level ell, added exactly by the inner-product launch (p == nullptr: none; it may be the source or dst),
+// dst, elt = first member, slot = member count.  Aborts unless hyb_lazy_sum_supported(c)
+void hyb_rotate_stages(Context &c, const BatchWs &w, const KsItem *d_items, int B, const KsItem *d_stages, int G, int ell, hipStream_t s, int unique);
 // one rotation hop by value (the one-instruction-at-a-time loop): src must not alias dst; add: KsItem::add (it may be src or dst), null for none
 void hyb_rotate_hop_single(Context &c, const Workspace &w, CtView dst, CtView src, u32 galois_elt, const u64 *galois_key, int ell, hipStream_t s,
                            CtView add = CtView{ nullptr, 0 });

@@ -414,7 +414,10 @@ void HEVM::build_plan()
     // the stage's other pops -- every hop of its rotations, its other adds -- go away and their values are never materialised.  Groups are
     // closed: a P_ROTSUM is no term of section 2's n-ary sums and no member of section 2b's groups.  A different rounding than the program's
     // hops (one mod-down instead of h): off by default, and the groups are exported (hevm_plan_flatten_groups) for the oracle's replay.
-    if (ks_flatten && !c.hybrid()) {
+    // Grouped digits (option hyb_flatten_sums, with hyb_lazy_sum in the fused sequence): the same pass, rules and pop.  A stage there is a step
+    // kind of its own (target_level -4: never in a step with section 2b's plain groups) that runs through hyb_rotate_stages -- one decomposition
+    // slot, hyb_mac_stage_kernel's accumulators running across the members, the addend as P y on the data primes.
+    if (c.hybrid() ? hyb_flatten && hyb_lazy_sum_supported(c) : ks_flatten != 0) {
         const int slots = (int)(N >> 1);
         for (const FlattenGroup &g : flatten_groups(flow, false)) {
             const size_t h = g.rot_ops.size();
@@ -430,6 +433,7 @@ void HEVM::build_plan()
             grp.kind = P_ROTSUM, grp.level = O[(size_t)ap[h - 1]].level, grp.dst = O[(size_t)ap[h - 1]].dst, grp.op = g.closing_op, grp.addend = source;
             for (size_t k = 0; k < h; k++) grp.flat_ops.push_back(g.rot_ops[k]), grp.flat_ops.push_back(g.add_ops[k]);
             grp.flat_offsets = g.offsets;
+            if (c.hybrid()) grp.target_level = -4;
             for (int o : g.offsets) {
                 u64 e = (u64)(o < 0 ? slots + o : o), elt = 1, g3 = 3;
                 for (; e; e >>= 1, g3 = (g3 * g3) & (2 * N - 1))
@@ -823,7 +827,7 @@ void HEVM::build_plan()
                     while (end < kv.second.size() && (items == 0 || items + O[(size_t)kv.second[end]].srcs.size() <= chunk))
                         items += O[(size_t)kv.second[end]].srcs.size(), end++;
                     Step st;
-                    st.kind = kind, st.level = std::get<1>(kv.first), st.wave = w, st.count = (int)items;
+                    st.kind = kind, st.level = std::get<1>(kv.first), st.target = std::get<2>(kv.first), st.wave = w, st.count = (int)items;
                     std::vector<int> members(kv.second.begin() + (long)off, kv.second.begin() + (long)end);
                     for (int pi : members) O[(size_t)pi].step = (int)P.steps.size();
                     P.steps.push_back(st);
@@ -1046,7 +1050,7 @@ void HEVM::build_plan()
             st.unique = (int)slot_of.size();
             // (SEAL-layout keys: one decomposition per distinct source of the step; grouped digits report one per hop, as before)
             P.n_hops += (int64_t)(h_ks.size() - (size_t)st.first);
-            P.n_decomp += c.hybrid() ? (int64_t)(h_ks.size() - (size_t)st.first) : (int64_t)st.unique;
+            P.n_decomp += c.hybrid() && st.target != -4 ? (int64_t)(h_ks.size() - (size_t)st.first) : (int64_t)st.unique;
             st.gfirst = (int)h_ks.size(), st.gcount = (int)groups.size();
             h_ks.insert(h_ks.end(), groups.begin(), groups.end());
             h_ks.insert(h_ks.end(), sources.begin(), sources.end()); // (option ks_lazy_sum: the decompositions' loader items, behind the groups)
@@ -1521,6 +1525,10 @@ void HEVM::issue_step(const Step &st, hipStream_t q)
         if (!c.hybrid()) { // option ks_lazy_sum: st.gcount sums of st.count members over st.unique decompositions
             hoist_rotate_sum(c, w, P.d_ks + st.first, P.d_ks + st.gfirst + st.gcount, st.count, st.unique, P.d_ks + st.gfirst, st.gcount, st.level, q,
                              st.addend);
+            break;
+        }
+        if (st.target == -4) { // option hyb_flatten_sums: st.gcount stages of one source each, st.unique decompositions
+            hyb_rotate_stages(c, w, P.d_ks + st.first, st.count, P.d_ks + st.gfirst, st.gcount, st.level, q, st.unique);
             break;
         }
         hyb_rotate_sum(c, w, P.d_ks + st.first, st.count, P.d_ks + st.gfirst, st.gcount, st.level, q, st.unique, st.addend); break;

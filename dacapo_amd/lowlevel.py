@@ -88,6 +88,7 @@ def _bind(path):
         L.dc_ct_rotate_hoisted.argtypes = [vp, vp, lng, u64p, lng, vp, vp, i32, i32, vp]
         L.dc_ct_rotate_sum_hoisted.argtypes = [vp, u64p, lng, vp, lng, vp, vp, vp, vp, i32, i32, vp]
         L.dc_ct_rotate_sum_hoisted_add.argtypes = [vp, u64p, lng, u64p, lng, vp, lng, vp, vp, vp, vp, i32, i32, vp]
+        L.dc_ct_rotate_stage_add.argtypes = [vp, u64p, lng, u64p, lng, u64p, lng, vp, vp, i32, i32, vp]
         L.dc_ct_rescale.argtypes = [vp, u64p, lng, u64p, lng, i32, vp]
         L.dc_ct_modswitch.argtypes = [vp, u64p, lng, u64p, lng, i32, i32, vp]
         L.dc_keyswitch.argtypes = [vp, u64p, lng, u64p, u64p, u64p, u64p, i32, vp]
@@ -245,6 +246,14 @@ class Context:
         pl = (C.c_void_p * n)(*plains) if plains is not None else None
         sp = (C.c_void_p * n)(*plains_sp) if plains_sp is not None else None
         self.L.dc_ct_rotate_sum_hoisted_add(self.h, dst, dst_stride, addend, addend_stride, ps, src_stride, ge, pk, pl, sp, n, ell, stream)
+
+    def rotate_stage_add(self, dst, dst_stride: int, addend, addend_stride: int, src, src_stride: int, elts, key_ptrs, ell: int, stream=None):
+        """dc_ct_rotate_stage_add (grouped-digit contexts): dst = addend + sum_k galois_{elts[k]}(src) with one decomposition and one division
+        by P; DeviceBuffers or device addresses, addend may be None, src or dst, and dst may be src"""
+        n = len(elts)
+        assert len(key_ptrs) == n
+        pk, ge = (C.c_void_p * n)(*[_ptr(k) for k in key_ptrs]), (C.c_uint32 * n)(*[int(e) for e in elts])
+        self.L.dc_ct_rotate_stage_add(self.h, _ptr(dst), dst_stride, _ptr(addend), addend_stride, _ptr(src), src_stride, ge, pk, n, ell, stream)
 
     def poly_mul(self, dst, a, b, ell: int, stream=None):
         """dc_poly_mul: dst = a . b limb-wise over `ell` limbs (NTT form); DeviceBuffers or device addresses"""

@@ -170,6 +170,17 @@ void dc_ct_rotate_sum_hoisted_add(dc_context *ctx, uint64_t *dst, long dst_strid
                                   const uint64_t *const *srcs, long src_stride, const uint32_t *galois_elts,
                                   const uint64_t *const *galois_keys, const uint64_t *const *plains, const uint64_t *const *plains_sp,
                                   int count, int ell, void *stream);
+/* EXTENSION, grouped-digit contexts (ks_special > 1; not SEAL's rounding): one stage of a flattened rotate-and-add chain --
+ * dst = addend + sum_k galois_k(src) with ONE decomposition of src and ONE division by P (option hyb_flatten_sums).  With the oracle built with
+ * the context's (ks_special, ks_alpha): per member orc_rotate_acc_hybrid on src.c1 gives the raised accumulator, the members' accumulators are
+ * added limb-wise modulo each of the ell + ks_special moduli, one orc_moddown_hybrid brings the sum down onto the base (sum_k galois_k(src.c0), 0)
+ * (Oracle.rotate_lazy / lazy_add), and Oracle.add(addend, .) follows: every limb equal, for every count.  The addend enters the data-prime
+ * accumulators as P . addend and nothing enters the special-prime ones, so it costs no rounding and no launch.  galois_elts / galois_keys: host
+ * arrays of length count (1 .. 65535), keys in dc_ct_rotate_hop's layout.  addend may be NULL (the bare sum), src or dst; dst may be src.
+ * Needs the fused sequence (option hyb_fuse != 0) and at most 16 digits at level ell.  A SEAL-layout context aborts with a message that names
+ * dc_ct_rotate_sum_hoisted_add.  The member table is kept in the context and copied synchronously: the call waits for earlier work on `stream`. */
+void dc_ct_rotate_stage_add(dc_context *ctx, uint64_t *dst, long dst_stride, const uint64_t *addend, long addend_stride, const uint64_t *src,
+                            long src_stride, const uint32_t *galois_elts, const uint64_t *const *galois_keys, int count, int ell, void *stream);
 /* Evaluator::rescale_to_next: level ell -> ell-1   SEAL_HEVM.cpp:283 */
 void dc_ct_rescale(dc_context *ctx, uint64_t *dst, long dst_stride, const uint64_t *src, long src_stride, int ell,
                    void *stream);

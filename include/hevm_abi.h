@@ -168,7 +168,9 @@ void hevm_last_run_relin_stats(void *vm, int64_t *groups, int64_t *products);
  * offsets (member k - 1 <-> the hops whose bits are set in k, k = 1 .. 2^hops - 1); the group's source, which is also its addend, is the
  * value the first hop rotates.  Returns as hevm_plan_lazy_groups does, which does not list these groups.
  * hevm_last_run_flatten_stats: groups, the rotations in them and the hops they absorbed in the last run(), once per stream (0 with the
- * option off or under plan = 0).  hevm_last_run_stats counts a flattened stage as ONE key switch with one key switch's transforms. */
+ * option off or under plan = 0).  hevm_last_run_stats counts a flattened stage as ONE key switch with one key switch's transforms.
+ * Grouped-digit keys ("ks_special" > 1): option "hyb_flatten_sums" = f, with "hyb_lazy_sum" >= 1 and "hyb_fuse" != 0 -- the same pass and rules,
+ * a stage one grouped-digit key switch over one decomposition (dc_ct_rotate_stage_add); the three calls report under either option. */
 int hevm_flatten_offsets(void *vm, int64_t *out, int cap);
 int64_t hevm_plan_flatten_groups(void *vm, int32_t *out, int64_t cap);
 void hevm_last_run_flatten_stats(void *vm, int64_t *groups, int64_t *members, int64_t *hops_absorbed);
@@ -225,7 +227,7 @@ void hevm_load_ctxt(void *vm, int64_t reg, const char *path);
 
 /* Run-time options (dacapo_amd/csrc/options.hpp holds the ONE table: names, defaults, meaning).  VM options -- "logn", "primes",
  * "prime_bits", "ks_special", "ks_alpha", "secret_hw", "rot_compose", "plan", "plan_graph", "plan_lanes", "max_batch", "chain_fusion", "host_encoder",
- * "online_encode", "fold_rescale_boot", "ks_lazy_relin", "ks_flatten_sums", "ks_fold_add", "hyb_fold_add", "zenc_head", "hyb_mfma", "hyb_fuse", "seal_compr", "trace", "step_profile" -- are read when a VM (or kernel-level
+ * "online_encode", "fold_rescale_boot", "ks_lazy_relin", "ks_flatten_sums", "ks_fold_add", "hyb_fold_add", "hyb_flatten_sums", "zenc_head", "hyb_mfma", "hyb_fuse", "seal_compr", "trace", "step_profile" -- are read when a VM (or kernel-level
  * context) is created; launch-shape thresholds -- "small_tile_wgs", "tiny_tile_wgs", "ntt_full_min_limbs", ... -- at every launch.
  * Process-wide, not thread-safe (like the rest of this ABI).  An unknown name aborts with the list of names.  A caller that only knows
  * the reference's 18 symbols sets the same names through the single environment variable DACAPO_HEVM_OPTIONS="name=value,...". */
