@@ -249,6 +249,10 @@ void b_mul_sum_relin(Context &c, const BatchWs &w, const MulSumItem *d_items, co
 
 void b_mul_relin_rescale(Context &c, const BatchWs &w, const MulRsItem *d_items, const u64 *relin_key, int B, int ell, hipStream_t s, const Handoff &h)
 {
+    if (c.hybrid()) { // (the grouped-digit step takes and offers no hand-off: the plan links none, plan_exec.hip 4b)
+        hyb_mul_relin_rescale(c, w, d_items, relin_key, B, ell, s);
+        return;
+    }
     if (!ks_shape(c, B, ell).folds_rescale()) {
         fprintf(stderr, "[dacapo_amd] b_mul_relin_rescale: no folded form for %d items at level %d under this context / these launch options "
                         "(run b_mul_relin and b_rescale)\n", B, ell);

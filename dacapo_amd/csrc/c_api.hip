@@ -253,10 +253,9 @@ void dc_ct_mul_relin_rescale(dc_context *ctx, uint64_t *dst, long dst_stride, co
 {
     Context &c = *ctx->c;
     hipStream_t s = S(stream);
-    refuse_grouped_digits(c, "dc_ct_mul_relin_rescale", ", whose mod-down is an approximate base conversion; the call is for SEAL-layout keys (use "
-                                                        "dc_ct_mul_relin and dc_ct_rescale)");
     if (ell < 2 || ell > c.max_level() || ell > kConstSlotWords) {
-        fprintf(stderr, "[dacapo_amd] dc_ct_mul_relin_rescale: level %d (2..%d)\n", ell, std::min(c.max_level(), kConstSlotWords));
+        fprintf(stderr, "[dacapo_amd] dc_ct_mul_relin_rescale: level %d (2..%d; SEAL-layout and grouped-digit keys alike)\n", ell,
+                std::min(c.max_level(), kConstSlotWords));
         abort();
     }
     const size_t N = c.N;
@@ -267,7 +266,7 @@ void dc_ct_mul_relin_rescale(dc_context *ctx, uint64_t *dst, long dst_stride, co
         DC_HIP_CHECK(hipMemcpyAsync(slot, mul_const, (size_t)ell * sizeof(u64), hipMemcpyHostToDevice, s));
         d_consts = slot;
     }
-    const bool fused = ks_shape(c, 1, ell).folds_rescale(), alias = overlaps(dst, a) || overlaps(dst, b);
+    const bool fused = ks_folds_rescale(c, 1, ell), alias = overlaps(dst, a) || overlaps(dst, b);
     if (!fused || alias) grow_scratch(ctx->fold_tmp, ctx->fold_tmp_cap, (size_t)3 * ell * N * sizeof(u64));
     if (fused) { // the last kernel's epilogue reads a and b where other workgroups write dst: an aliased destination is written through scratch
         const CtView out = alias ? CtView{ ctx->fold_tmp, (long)(ell - 1) * (long)N } : V(dst, dst_stride);

@@ -479,6 +479,7 @@ void HEVM::init_context(int logN, int K, const u64 *primes, int dir_ksp, int dir
                         "is an approximate base conversion, and dividing by P q in one exact pass does not reproduce it\n", ksp, alpha);
         abort();
     }
+    hyb_fold_rescale = option(OPT_HYB_FOLD_RESCALE) != 0 && (ksp > 1 || alpha > 1); // (SEAL-layout keys: ignored; ks_fold_rescale is the option there)
     ks_lazy_relin = option(OPT_KS_LAZY_RELIN) != 0;
     if (ks_lazy_relin && (ksp > 1 || alpha > 1)) {
         fprintf(stderr, "[dacapo_amd] option ks_lazy_relin = 1 is for SEAL-layout keys (ks_special = 1); with ks_special = %d, ks_alpha = %d the summed "
@@ -2722,7 +2723,7 @@ void hevm_last_run_hoist_stats(void *vm, int64_t *hops, int64_t *decompositions)
     if (decompositions) *decompositions = h->n_decomp;
 }
 
-// option ks_fold_rescale: items (multiply-rescale pairs x streams) that the plan of the last run() executed as one merged step; 0 with the
+// options ks_fold_rescale / hyb_fold_rescale: items (multiply-rescale pairs x streams) that the plan of the last run() executed as one merged step; 0 with the
 // option off, in the loop (plan = 0), and for pairs that keep the default sequence
 void hevm_last_run_fold_rescale_stats(void *vm, int64_t *pairs)
 {

@@ -317,6 +317,9 @@ class HEVM {
     // option ks_fold_rescale = 1 (SEAL-layout keys): a multiply and the rescale that alone reads it run as one step
     // (plan_exec.hip section 4; plan.hpp b_mul_relin_rescale).  Every limb equals the default path's.
     bool ks_fold_rescale = false;
+    // option hyb_fold_rescale = 1 (grouped digits, hyb_fuse != 0): the same merged step on the grouped-digit path (hybrid_fused.hip
+    // hybf_mul_relin_rescale_tail).  Off by default (profiles/hyb_fold_rescale_ab.txt); ignored on SEAL-layout keys.
+    bool hyb_fold_rescale = false;
     // option ks_lazy_relin = 1 (SEAL-layout keys): sums of single-use ct x ct products are relinearised once (plan_exec.hip section 1b;
     // plan_relin.hpp names the groups, plan.hpp b_mul_sum_relin runs them).  Changes the rounding: off by default.
     bool ks_lazy_relin = false;

@@ -486,4 +486,306 @@ void hybf_keyswitch(Context &c, const Workspace &w, CtView out, const u64 *base0
     hybf_core<2>(c, bw, nullptr, KsItem{}, HybOut{ out, base0, base1 }, key, 1, 1, 0, ell, s);
 }
 
+// ---- a rescale folded into the multiply's mod-down (option hyb_fold_rescale; dc_ct_mul_relin_rescale on a grouped-digit context) --------------
+// A ct x ct product that only its own rescale reads.  Level l >= 2, D = l - 1 the dropped data prime, X_i the data-prime accumulators of
+// polynomial c (F5), z_j what F7 leaves, t_i = sum_j z_j (P / p_j) - floor(P/2) mod q_i the mod-down's correction (an approximate rounding of
+// acc / P, but a definite integer function of the z_j), d_i the tensor term of polynomial c (a0 b0 | a0 b1 + a1 b0), A_i a plaintext added to
+// c0, s_i a constant polynomial's value.  The default pair computes m_i = s_i ((X_i - NTT_i(t_i)) P^-1 + d_i + A_i) at level l and then SEAL's
+// divide-and-round by q_D, which inverts limb D and transforms l - 1 lifted limbs forward again.  Both steps are exact in every limb, so
+//     c_D = s_D (iNTT_D(X_D + P (d_D + A_D)) - t_D) P^-1                      coefficient domain, mod q_D
+//     u   = [c_D + floor(q_D / 2)]_{q_D},   u_i = (u mod q_i) - (floor(q_D / 2) mod q_i)
+//     v_i = (s_i P^-1 t_i + u_i) q_D^-1                                       ONE lifted polynomial per kept limb i < D
+//     r_i = s_i q_D^-1 (X_i P^-1 + d_i + A_i) - NTT_i(v_i)
+// equals rescale(mul_relin(a, b)) limb for limb (tests/test_hyb_fold_rescale_oracle.py restates it on the oracle's primitives).  Per polynomial
+// l - 1 forward transforms instead of 2 l - 1, the one inverse transform of a data limb rides with the special primes', and the product at
+// level l, with the rescale's three launches, is gone.
+//   F1 ... F5  as for a multiply (the target a1 b1 from hybf_fold_target_kernel: nobody stores the tensor's c0 / c1 -- F6' and F9' form them)
+//   F6' / F7'  inverse transforms of ksp + 1 rows per polynomial: the special rows as F6 / F7, row D of accq with P (d_D + A_D) added by its
+//              loader and N^-1 alone in its last stage, out of place into rowD [2B][N] -- the head of w.ext, free once F5 has read the raised
+//              limbs (B E >= B ksp >= 2 B limbs); no scratch grows
+//   F8'        hyb_fuse = 2 at l >= 4: the matrix-core conversion as it is (t for all l rows, row D included, in w.tmp), then a forward COLS
+//              kernel over the l - 1 kept rows whose loader forms v_i from t_i, t_D and rowD at the same coefficient, in place in w.tmp.
+//              Otherwise (hyb_fuse = 1, or below the matrix-core form's level): hybf_fold_u_kernel forms u once per polynomial, in place in
+//              rowD, and hybf_moddown_fcols_kernel's sibling forms t_i as that kernel does and v_i from it and u
+//   F9'        the last forward ROWS phase with r_i as its store epilogue: 16-byte accesses; d_i from a and b, A_i and s_i from the item
+// The step takes and offers no chain-fusion hand-off.
+
+// the key switch's target of B multiply-rescale items: target[b][i] = a1 b1.  grid = (N/512, l, B)
+__global__ __launch_bounds__(256) void hybf_fold_target_kernel(const MulRsItem *__restrict__ items, u64 *__restrict__ target, int ell, size_t N,
+                                                                const DModulus *__restrict__ mods)
+{
+    const int i = blockIdx.y, b = blockIdx.z;
+    const DModulus m = mods[i];
+    const size_t k = ((size_t)blockIdx.x * 256 + threadIdx.x) * 2;
+    const u64x2 a1 = *reinterpret_cast<const u64x2 *>(items[b].a.limb(1, i, N) + k), b1 = *reinterpret_cast<const u64x2 *>(items[b].b.limb(1, i, N) + k);
+    *reinterpret_cast<u64x2 *>(target + ((size_t)b * ell + i) * N + k) = u64x2{ mulmod(a1.x, b1.x, m), mulmod(a1.y, b1.y, m) };
+}
+
+// d + A of polynomial c at coefficients g, g + 1 of limb i: a0 b0 + A | a0 b1 + a1 b0 (hyb_prepare_mul_kernel's arithmetic)
+__device__ __forceinline__ u64x2 hf_tensor_pair(const MulRsItem &it, int c, int i, size_t N, int g, const DModulus &M)
+{
+    const u64x2 a0 = *reinterpret_cast<const u64x2 *>(it.a.limb(0, i, N) + g), b0 = *reinterpret_cast<const u64x2 *>(it.b.limb(0, i, N) + g);
+    u64x2 d;
+    if (c == 0) {
+        d.x = mulmod(a0.x, b0.x, M), d.y = mulmod(a0.y, b0.y, M);
+        if (it.add) {
+            const u64x2 A = *reinterpret_cast<const u64x2 *>(it.add + (size_t)i * N + g);
+            d.x = addmod(d.x, A.x, M.q), d.y = addmod(d.y, A.y, M.q);
+        }
+    } else {
+        const u64x2 a1 = *reinterpret_cast<const u64x2 *>(it.a.limb(1, i, N) + g), b1 = *reinterpret_cast<const u64x2 *>(it.b.limb(1, i, N) + g);
+#pragma unroll
+        for (int e = 0; e < 2; e++) {
+            Acc128 acc;
+            acc.clear();
+            acc.mac(a0[e], b1[e]);
+            acc.mac(a1[e], b0[e]);
+            d[e] = acc.reduce(M);
+        }
+    }
+    return d;
+}
+// a constant polynomial's value in limb i (MulRsItem::mul), 1 without one
+__device__ __forceinline__ u64 hf_const(const MulRsItem &it, int i) { return it.mul ? it.mul[(long)i * it.mul_stride] : 1; }
+// u = [s_D (x_D - t_D) P^-1 + floor(q_D / 2)]_{q_D}: the rounded last limb of the rescale, sp = s_D P^-1 mod q_D
+__device__ __forceinline__ u64 hf_fold_u(u64 x, u64 t, u64 sp, const DModulus &MD)
+{
+    return addmod(mulmod(sp, submod(x, t, MD.q), MD), MD.q >> 1, MD.q);
+}
+
+// ---- F6': inverse ROWS phase of ksp + 1 rows per polynomial.  y = z (ksp + 1) + j: j < ksp the special-prime accumulator, in place (F6);
+// j = ksp row D = l - 1 of accq with P (d_D + A_D) added by the loader, into rowD[z].  A ROWS tile's first inverse pass holds E consecutive
+// coefficients per thread (F9's map), so the extra row's four streams are 16-byte loads
+template <int K, int LOGE>
+__global__ __launch_bounds__(kTileThreads) void hybf_irows_fold_kernel(u64 *__restrict__ accp, const u64 *__restrict__ accq, u64 *__restrict__ rowd,
+                                                                        const MulRsItem *__restrict__ items, int ell, int ksp, int L,
+                                                                        const DModulus *__restrict__ mods, const u64 *__restrict__ pmod,
+                                                                        const u64 *__restrict__ itw, int logN, int prime_major)
+{
+    __shared__ __attribute__((aligned(16))) u64 lds[TileGeo<LOGE>::LDS_ELEMS];
+    constexpr int EC = 1 << LOGE, NP = num_passes<LOGE>(K);
+    const size_t N = (size_t)1 << logN;
+    const int R = ksp + 1, polys = gridDim.y / R;
+    const int j = prime_major ? blockIdx.y / polys : blockIdx.y % R, z = prime_major ? blockIdx.y % polys : blockIdx.y / R;
+    if (j < ksp) {
+        const int p = L + j;
+        u64 *a = accp + (((size_t)z * ksp + j) << logN);
+        ntt_tile<K, LOGE, false, true, false>(
+            mods[p], itw + ((size_t)p << logN), logN, blockIdx.x, [=](int g) { return a[g]; }, [=](int g, u64 v) { a[g] = v; }, lds);
+        return;
+    }
+    const int D = ell - 1, c = z & 1;
+    const DModulus M = mods[D];
+    const u64 P = pmod[D];
+    const MulRsItem it = items[z >> 1];
+    const u64 *ac = accq + ((size_t)z * ell + D) * N;
+    u64 *out = rowd + (size_t)z * N;
+    const int g0 = tile_gidx<K, LOGE, false>(NP - 1, logN, blockIdx.x, 0);
+    u64 x[EC];
+#pragma unroll
+    for (int e = 0; e < EC; e += 2) {
+        const u64x2 X = *reinterpret_cast<const u64x2 *>(ac + g0 + e), d = hf_tensor_pair(it, c, D, N, g0 + e, M);
+        x[e] = addmod(X.x, mulmod(P, d.x, M), M.q), x[e + 1] = addmod(X.y, mulmod(P, d.y, M), M.q);
+    }
+    auto nold = [](int) -> u64 { return 0; };
+    ntt_tile_x<K, LOGE, false, true, false, true, false>(x, M, itw + ((size_t)D << logN), logN, blockIdx.x, nold, [=](int g, u64 v) { out[g] = v; }, lds);
+}
+
+// ---- F7': second inverse phase of the same ksp + 1 rows, in place.  j < ksp: F7 itself (N^-1 phat_j^-1 in the last stage, floor(P/2) phat_j^-1
+// added by the store); j = ksp: rowD[z] with the prime's own constants -- N^-1 only
+template <int K, int LOGE>
+__global__ __launch_bounds__(kTileThreads) void hybf_icols_fold_kernel(u64 *__restrict__ accp, u64 *__restrict__ rowd, int ell, int ksp, int L,
+                                                                        const DModulus *__restrict__ dnmods, const DModulus *__restrict__ mods,
+                                                                        const u64 *__restrict__ hp, const u64 *__restrict__ itw, int logN)
+{
+    __shared__ __attribute__((aligned(16))) u64 lds[TileGeo<LOGE>::LDS_ELEMS];
+    const int R = ksp + 1, j = blockIdx.y % R, z = blockIdx.y / R;
+    if (j < ksp) {
+        const int p = L + j;
+        const DModulus M = dnmods[p];
+        const u64 h = hp[j];
+        u64 *a = accp + (((size_t)z * ksp + j) << logN);
+        ntt_tile<K, LOGE, true, true, true>(
+            M, itw + ((size_t)p << logN), logN, blockIdx.x, [=](int g) { return a[g]; }, [=](int g, u64 v) { a[g] = addmod(v, h, M.q); }, lds);
+        return;
+    }
+    const int D = ell - 1;
+    u64 *a = rowd + ((size_t)z << logN);
+    ntt_tile<K, LOGE, true, true, true>(
+        mods[D], itw + ((size_t)D << logN), logN, blockIdx.x, [=](int g) { return a[g]; }, [=](int g, u64 v) { a[g] = v; }, lds);
+}
+
+// ---- F8' where the conversion rides in the loaders: u once per polynomial, in place in rowD.  t_D is F8's sum for row D (three columns of
+// 30-bit limb products, banked every 8 terms).  grid = (N/512, 2B)
+__global__ __launch_bounds__(256) void hybf_fold_u_kernel(const u64 *__restrict__ accp, u64 *__restrict__ rowd, const MulRsItem *__restrict__ items,
+                                                           int ell, int ksp, int L, size_t N, const DModulus *__restrict__ mods,
+                                                           const u64 *__restrict__ dn)
+{
+    const int z = blockIdx.y, D = ell - 1;
+    const DModulus MD = mods[D];
+    const size_t k = ((size_t)blockIdx.x * 256 + threadIdx.x) * 2;
+    const u64 *w = dn + 2 * ksp + 2 * L + D; // w[j * L] = (P / p_j) mod q_D
+    const u64 sp = mulmod(dn[2 * ksp + L + D], hf_const(items[z >> 1], D), MD);
+    const u64 *src = accp + (size_t)z * ksp * N + k;
+    Acc3 acc[2];
+    u64 t[2] = { 0, 0 };
+    acc[0].clear(), acc[1].clear();
+    for (int j = 0; j < ksp; j++) {
+        const u64x2 y = *reinterpret_cast<const u64x2 *>(src + (size_t)j * N);
+        const u64 cw = w[(size_t)j * L];
+        acc[0].mac(y.x, w_lo30(cw), w_hi30(cw)), acc[1].mac(y.y, w_lo30(cw), w_hi30(cw));
+        if ((j & 7) == 7 && j + 1 < ksp) {
+#pragma unroll
+            for (int e = 0; e < 2; e++) t[e] = addmod(t[e], acc[e].reduce(MD), MD.q), acc[e].clear();
+        }
+    }
+    const u64x2 x = *reinterpret_cast<const u64x2 *>(rowd + (size_t)z * N + k);
+    u64x2 u;
+#pragma unroll
+    for (int e = 0; e < 2; e++) u[e] = hf_fold_u(x[e], submod(addmod(t[e], acc[e].reduce(MD), MD.q), dn[2 * ksp + D], MD.q), sp, MD);
+    *reinterpret_cast<u64x2 *>(rowd + (size_t)z * N + k) = u;
+}
+
+// ---- F8': the lift v_i as the loader of the kept limbs' first forward phase.  y = z (l - 1) + i, i < D = l - 1; tmp [2B][l][N] (row D of a
+// polynomial is no output).  CONV: t_i by F8's own conversion from accp, u from rowD (hybf_fold_u_kernel has run).  Otherwise t_i and t_D from
+// tmp -- the matrix-core conversion's outputs, below 2q in the 60-bit build: folded first -- and u formed here from t_D and rowD; in place.
+// u mod q_i is a reduction in either direction of a mixed-width chain (recanon)
+template <int K, int LOGE, bool CONV>
+__global__ __launch_bounds__(kTileThreads) void hybf_fold_lift_fcols_kernel(const u64 *__restrict__ accp, u64 *__restrict__ tmp,
+                                                                             const u64 *__restrict__ rowd, const MulRsItem *__restrict__ items,
+                                                                             int ell, int ksp, int L, int Kp, const DModulus *__restrict__ mods,
+                                                                             const u64 *__restrict__ dn, const u64 *__restrict__ inv_last,
+                                                                             const u64 *__restrict__ half_mod, const u64 *__restrict__ tw, int logN)
+{
+    __shared__ __attribute__((aligned(16))) u64 lds[TileGeo<LOGE>::LDS_ELEMS];
+    constexpr int EC = 1 << LOGE;
+    const size_t N = (size_t)1 << logN;
+    const int D = ell - 1, i = blockIdx.y % D, z = blockIdx.y / D;
+    const DModulus Mo = mods[i], MD = mods[D];
+    const MulRsItem it = items[z >> 1];
+    const u64 k2 = inv_last[(size_t)D * Kp + i];                                          // q_D^-1
+    const u64 k3 = mulmod(mulmod(dn[2 * ksp + L + i], k2, Mo), hf_const(it, i), Mo);      // s_i P^-1 q_D^-1   mod q_i
+    const u64 half_d = half_mod[(size_t)D * Kp + i];
+    const u64 *ud = rowd + (size_t)z * N;
+    u64 *row = tmp + ((size_t)z * ell + i) * N;
+    int gi[EC];
+#pragma unroll
+    for (int j = 0; j < EC; j++) gi[j] = tile_gidx<K, LOGE, true>(0, logN, blockIdx.x, j);
+    u64 x[EC], u[EC];
+    if (CONV) {
+        const u64 half_q = dn[2 * ksp + i];
+        const u64 *w = dn + 2 * ksp + 2 * L + i; // w[j * L] = (P / p_j) mod q_i
+        const u64 *src = accp + (size_t)z * ksp * N;
+        Acc3 acc[EC];
+#pragma unroll
+        for (int j = 0; j < EC; j++) acc[j].clear(), x[j] = 0, u[j] = ud[gi[j]];
+        for (int t0 = 0; t0 < ksp; t0 += kConvChunk<LOGE>) {
+            u64 y[kConvChunk<LOGE>][EC];
+#pragma unroll
+            for (int tt = 0; tt < kConvChunk<LOGE>; tt++) {
+                if (t0 + tt < ksp) {
+#pragma unroll
+                    for (int j = 0; j < EC; j++) y[tt][j] = src[(size_t)(t0 + tt) * N + gi[j]];
+                }
+            }
+#pragma unroll
+            for (int tt = 0; tt < kConvChunk<LOGE>; tt++) {
+                if (t0 + tt < ksp) {
+                    const u64 cw = w[(size_t)(t0 + tt) * L];
+                    const u32 c0 = w_lo30(cw), c1 = w_hi30(cw);
+#pragma unroll
+                    for (int j = 0; j < EC; j++) acc[j].mac(y[tt][j], c0, c1);
+                }
+            }
+            if (((t0 + kConvChunk<LOGE>) & 7) == 0 && t0 + kConvChunk<LOGE> < ksp) {
+#pragma unroll
+                for (int j = 0; j < EC; j++) x[j] = addmod(x[j], acc[j].reduce(Mo), Mo.q), acc[j].clear();
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < EC; j++) x[j] = submod(addmod(x[j], acc[j].reduce(Mo), Mo.q), half_q, Mo.q);
+    } else {
+        const u64 sp = mulmod(dn[2 * ksp + L + D], hf_const(it, D), MD);
+        const u64 *td = tmp + ((size_t)z * ell + D) * N;
+        u64 tD[EC];
+#pragma unroll
+        for (int j = 0; j < EC; j++) x[j] = row[gi[j]], tD[j] = td[gi[j]], u[j] = ud[gi[j]];
+#pragma unroll
+        for (int j = 0; j < EC; j++) x[j] = recanon(x[j], Mo), u[j] = hf_fold_u(u[j], recanon(tD[j], MD), sp, MD);
+    }
+#pragma unroll
+    for (int j = 0; j < EC; j++) { // v_i = t_i k3 + (u mod q_i - floor(q_D / 2) mod q_i) k2: one reduction
+        Acc128 a;
+        a.clear();
+        a.mac(x[j], k3);
+        a.mac(submod(recanon(u[j], Mo), half_d, Mo.q), k2);
+        x[j] = a.reduce(Mo);
+    }
+    auto nold = [](int) -> u64 { return 0; };
+    ntt_tile_x<K, LOGE, true, false, false, true, false>(x, Mo, tw + ((size_t)i << logN), logN, blockIdx.x, nold, [=](int gg, u64 v) { row[gg] = v; }, lds);
+}
+
+// ---- F9': last forward phase of the kept limbs with r_i = s_i q_D^-1 (X_i P^-1 + d_i + A_i) - NTT_i(v_i) as its epilogue.  y = z (l - 1) + i.
+// F9's access pattern: E consecutive coefficients per thread, every stream (accumulator, a0, b0 | a0, a1, b0, b1, plaintext, destination) 16 bytes
+template <int K, int LOGE>
+__global__ __launch_bounds__(kTileThreads) void hybf_frows_fold_final_kernel(const u64 *__restrict__ tmp, const u64 *__restrict__ accq,
+                                                                              const MulRsItem *__restrict__ items, int ell, int ksp, int L, int Kp,
+                                                                              const DModulus *__restrict__ mods, const u64 *__restrict__ dn,
+                                                                              const u64 *__restrict__ inv_last, const u64 *__restrict__ tw, int logN,
+                                                                              int prime_major)
+{
+    __shared__ __attribute__((aligned(16))) u64 lds[TileGeo<LOGE>::LDS_ELEMS];
+    constexpr int EC = 1 << LOGE, NP = num_passes<LOGE>(K);
+    const size_t N = (size_t)1 << logN;
+    const int D = ell - 1, polys = gridDim.y / D;
+    const int i = prime_major ? blockIdx.y / polys : blockIdx.y % D, z = prime_major ? blockIdx.y % polys : blockIdx.y / D, c = z & 1;
+    const DModulus M = mods[i];
+    const MulRsItem it = items[z >> 1];
+    const u64 pinv = dn[2 * ksp + L + i];
+    const u64 k1 = mulmod(inv_last[(size_t)D * Kp + i], hf_const(it, i), M); // s_i q_D^-1 mod q_i
+    const u64 *in = tmp + ((size_t)z * ell + i) * N, *ac = accq + ((size_t)z * ell + i) * N;
+    u64 *dst = it.dst.limb(c, i, N);
+    u64 x[EC];
+    auto nost = [](int, u64) {};
+    ntt_tile_x<K, LOGE, false, false, true, false, true>(x, M, tw + ((size_t)i << logN), logN, blockIdx.x, [=](int g) { return in[g]; }, nost, lds);
+    const int g0 = tile_gidx<K, LOGE, false>(NP - 1, logN, blockIdx.x, 0); // register j holds coefficient g0 + j
+#pragma unroll
+    for (int j = 0; j < EC; j += 2) {
+        const u64x2 a = *reinterpret_cast<const u64x2 *>(ac + g0 + j), d = hf_tensor_pair(it, c, i, N, g0 + j, M);
+        u64x2 r;
+        r.x = submod(mulmod(k1, addmod(mulmod(pinv, a.x, M), d.x, M.q), M), x[j], M.q);
+        r.y = submod(mulmod(k1, addmod(mulmod(pinv, a.y, M), d.y, M.q), M), x[j + 1], M.q);
+        *reinterpret_cast<u64x2 *>(dst + g0 + j) = r;
+    }
+}
+
+// B multiply-rescale pairs at level ell -> d_items[b].dst at level ell - 1 (the caller has checked ks_shape(c, B, ell).hyb_folds_rescale()).
+// One item through a one-entry table is the single call's form (dc_ct_mul_relin_rescale).
+void hybf_mul_relin_rescale_tail(Context &c, const BatchWs &w, const MulRsItem *d_items, const u64 *relin_key, int B, int ell, hipStream_t s)
+{
+    const size_t N = c.N;
+    const int ksp = c.ksp, L = c.max_level(), D = ell - 1;
+    const bool separate_conv = option(OPT_HYB_FUSE) == 2 && c.hyb_mfma && N >= 512 && ell >= 4;
+    u64 *accq = w.acc, *accp = w.acc + (size_t)B * 2 * ell * N, *rowd = w.ext;
+    DC_LAUNCH(hybf_fold_target_kernel, dim3((unsigned)(N / 512), (unsigned)ell, (unsigned)B), dim3(256), 0, s, d_items, w.target, ell, N, c.d_mods);
+    f1_irows<1>(c, nullptr, KsItem{}, w.target, w.digits, B, ell, 0, s);
+    hybf_front<1>(c, w, nullptr, KsItem{}, relin_key, B, B, 0, ell, s);                                            // F2 ... F5
+    DC_GEO_SWITCH(c.k2, 2 * B * (ksp + 1), DC_LAUNCH((hybf_irows_fold_kernel<KK, LE>), grid, dim3(kTileThreads), 0, s, accp, accq, rowd, d_items, ell,
+                                                               ksp, L, c.d_mods, c.d_pmod, c.d_itw, c.logN, (int)rows_prime_major(c)));        // F6'
+    DC_GEO_SWITCH(c.k1, 2 * B * (ksp + 1), DC_LAUNCH((hybf_icols_fold_kernel<KK, LE>), grid, dim3(kTileThreads), 0, s, accp, rowd, ell, ksp, L,
+                                                               c.d_hyb_dnmods, c.d_mods, c.d_hyb_hp, c.d_itw, c.logN));                        // F7'
+    if (separate_conv) {                                                                                                                        // F8'
+        hyb_launch_conv(c, true, true, accp, w.tmp, 2 * B, ell, s);
+        DC_GEO_SWITCH(c.k1, 2 * B * D, DC_LAUNCH((hybf_fold_lift_fcols_kernel<KK, LE, false>), grid, dim3(kTileThreads), 0, s, accp, w.tmp, rowd, d_items,
+                                                          ell, ksp, L, c.K, c.d_mods, c.d_hyb_dn, c.d_inv_last, c.d_half_mod, c.d_tw, c.logN));
+    } else {
+        DC_LAUNCH(hybf_fold_u_kernel, dim3((unsigned)(N / 512), (unsigned)(2 * B)), dim3(256), 0, s, accp, rowd, d_items, ell, ksp, L, N, c.d_mods,
+                  c.d_hyb_dn);
+        DC_GEO_SWITCH(c.k1, 2 * B * D, DC_LAUNCH((hybf_fold_lift_fcols_kernel<KK, LE, true>), grid, dim3(kTileThreads), 0, s, accp, w.tmp, rowd, d_items,
+                                                          ell, ksp, L, c.K, c.d_mods, c.d_hyb_dn, c.d_inv_last, c.d_half_mod, c.d_tw, c.logN));
+    }
+    DC_GEO_SWITCH(c.k2, 2 * B * D, DC_LAUNCH((hybf_frows_fold_final_kernel<KK, LE>), grid, dim3(kTileThreads), 0, s, w.tmp, accq, d_items, ell, ksp, L,
+                                                      c.K, c.d_mods, c.d_hyb_dn, c.d_inv_last, c.d_tw, c.logN, (int)rows_prime_major(c)));     // F9'
+}
+
 } // namespace dacapo

@@ -830,6 +830,17 @@ void hyb_mul_relin(Context &c, const BatchWs &w, const MulItem *d_items, const u
     hyb_core<1>(c, w, d_items, relin_key, HybSingle{}, KsItem{}, B, B, 0, ell, s);
 }
 
+void hybf_mul_relin_rescale_tail(Context &c, const BatchWs &w, const MulRsItem *d_items, const u64 *relin_key, int B, int ell, hipStream_t s);
+void hyb_mul_relin_rescale(Context &c, const BatchWs &w, const MulRsItem *d_items, const u64 *relin_key, int B, int ell, hipStream_t s)
+{
+    if (!ks_shape(c, B, ell).hyb_folds_rescale()) {
+        fprintf(stderr, "[dacapo_amd] hyb_mul_relin_rescale: no folded form for %d items at level %d under this context / option hyb_fuse = 0 "
+                        "(run b_mul_relin and b_rescale)\n", B, ell);
+        abort();
+    }
+    hybf_mul_relin_rescale_tail(c, w, d_items, relin_key, B, ell, s);
+}
+
 // Evaluator::switch_key_inplace's role for one ciphertext: out = (base0, base1) + KS(target).  target [l][N] NTT form, preserved.
 void hyb_keyswitch(Context &c, const Workspace &w, CtView out, const u64 *base0, const u64 *base1, const u64 *target, const u64 *key, int ell,
                    hipStream_t s)

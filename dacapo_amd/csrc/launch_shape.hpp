@@ -15,6 +15,8 @@ struct KsShape {
     int ell;
     // a rescale folds into the multiply's key switch (b_mul_relin_rescale): the folded form exists for the latency-shaped sequence only
     bool folds_rescale() const { return !hybrid && ell >= 2 && fused_mac && !big; }
+    // ... and into the grouped-digit multiply's mod-down (hybrid_fused.hip hybf_mul_relin_rescale_tail): the fused sequence, any batch size
+    bool hyb_folds_rescale() const { return hybrid && ell >= 2 && option(OPT_HYB_FUSE) != 0; }
     // an item may carry an addend (KsItem::add): a start value of the fused middle's accumulators and of nothing else
     bool carries_addend() const { return !hybrid && fused_mac; }
 };

@@ -46,6 +46,7 @@ static const OptDef kDefs[OPT_COUNT] = {
     { "ks_fold_add", 1 }, // measured: profiles/ks_fold_add_ab.txt
     { "hyb_fold_add", 0 }, // measured: profiles/hyb_fold_add_ab.txt
     { "hyb_flatten_sums", 0 }, // profiles/hyb_flatten_ab.txt
+    { "hyb_fold_rescale", 0 }, // profiles/hyb_fold_rescale_ab.txt
     { "zenc_head", 1 },
     { "seal_compr", 0 },
     { "trace", 0 },

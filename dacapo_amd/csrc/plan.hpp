@@ -19,6 +19,12 @@
 namespace dacapo {
 
 inline KsShape ks_shape(const Context &c, int B, int ell) { return ks_shape(c.N, c.hybrid(), B, ell); }
+// does a batch of B multiply-rescale pairs at level ell have a folded launch form (b_mul_relin_rescale)?
+inline bool ks_folds_rescale(const Context &c, int B, int ell)
+{
+    const KsShape sh = ks_shape(c, B, ell);
+    return sh.folds_rescale() || sh.hyb_folds_rescale();
+}
 // a call that exists for SEAL-layout keys meets a context with grouped digits: abort in the caller's name, `rest` ending the sentence in its words
 inline void refuse_grouped_digits(const Context &c, const char *who, const char *rest)
 {
@@ -147,6 +153,8 @@ void b_mul_relin(Context &c, const BatchWs &w, const MulItem *d_items, const u64
 // a multiply and the rescale that alone reads it as ONE five-launch sequence (SEAL-layout keys, the latency-shaped launch forms only:
 // ks_shape(c, B, ell).folds_rescale() says whether a batch of B at level ell has it; otherwise run b_mul_relin and b_rescale -- the limbs are
 // the same).  h.in as for b_mul_relin; h.cont CONT_MUL / CONT_BOOT as for b_rescale.
+// Grouped digits: hyb_mul_relin_rescale where ks_shape(c, B, ell).hyb_folds_rescale() holds (it takes and offers no hand-off).
+// ks_folds_rescale(c, B, ell) is the question for either key layout.
 void b_mul_relin_rescale(Context &c, const BatchWs &w, const MulRsItem *d_items, const u64 *relin_key, int B, int ell, hipStream_t s,
                          const Handoff &h = Handoff{});
 void b_rescale(Context &c, const BatchWs &w, const RsItem *d_items, int B, int ell, hipStream_t s, const SumSrc *d_srcs = nullptr,
@@ -184,6 +192,9 @@ void hyb_rotate_stages(Context &c, const BatchWs &w, const KsItem *d_items, int 
 void hyb_rotate_hop_single(Context &c, const Workspace &w, CtView dst, CtView src, u32 galois_elt, const u64 *galois_key, int ell, hipStream_t s,
                            CtView add = CtView{ nullptr, 0 });
 void hyb_mul_relin(Context &c, const BatchWs &w, const MulItem *d_items, const u64 *relin_key, int B, int ell, hipStream_t s);
+// b_mul_relin_rescale's grouped-digit form (hybrid_fused.hip hybf_mul_relin_rescale_tail): the rescale's lift rides the mod-down's correction,
+// one forward transform per kept limb.  Aborts unless ks_shape(c, B, ell).hyb_folds_rescale().  No destination may be an operand of the batch
+void hyb_mul_relin_rescale(Context &c, const BatchWs &w, const MulRsItem *d_items, const u64 *relin_key, int B, int ell, hipStream_t s);
 void hyb_keyswitch(Context &c, const Workspace &w, CtView out, const u64 *base0, const u64 *base1, const u64 *target, const u64 *key, int ell,
                    hipStream_t s);
 // NTT-equivalents of one key switch at level ell: (l + 1)(l + 2) for SEAL's scheme, G (l + ksp) + 2 ksp + 2 l with grouped digits

@@ -772,7 +772,10 @@ void HEVM::build_plan()
     std::map<int, int> fold_rs_of;                // qualifying multiply pop -> its rescale pop
     std::vector<char> absorbed(O.size(), 0);      // rescale pops that a merged step executes: in no step of their own
     std::map<size_t, std::vector<int>> fold_pops; // merged step -> the rescale pops it absorbed, item for item
-    if (ks_fold_rescale && !online_encode && !c.hybrid()) {
+    // Grouped digits (option hyb_fold_rescale; ks_fold_rescale is the SEAL-layout option and hyb_fold_rescale is ignored there): the same rule;
+    // the merged step runs hybrid_fused.hip hybf_mul_relin_rescale_tail where the fused sequence is on (launch_shape.hpp hyb_folds_rescale) and
+    // takes and offers no hand-off (4b links nothing under grouped digits).
+    if ((c.hybrid() ? hyb_fold_rescale : ks_fold_rescale) && !online_encode) {
         std::map<int, bool> constant; // plaintext register -> is it a constant polynomial
         auto is_constant = [&](int reg) {
             auto it = constant.find(reg);
@@ -842,9 +845,9 @@ void HEVM::build_plan()
                 st.count = (int)std::min(chunk, kv.second.size() - off);
                 std::vector<int> members(kv.second.begin() + (long)off, kv.second.begin() + (long)off + st.count);
                 for (int pi : members) O[(size_t)pi].step = (int)P.steps.size();
-                if (kind == P_MULCC && st.target == -3) { // option ks_fold_rescale: the chunk and its rescales as one step, where a folded form exists
+                if (kind == P_MULCC && st.target == -3) { // options ks_fold_rescale / hyb_fold_rescale: the chunk and its rescales as one step, where a folded form exists
                     st.target = 0;
-                    if (ks_shape(c, st.count * S, st.level).folds_rescale()) {
+                    if (ks_folds_rescale(c, st.count * S, st.level)) {
                         st.fold_rs = true;
                         std::vector<int> &rs = fold_pops[P.steps.size()];
                         for (int pi : members) {

@@ -537,7 +537,7 @@ class HEVM:
         return {"groups": g.value, "members": m.value, "hops_absorbed": h.value}
 
     def fold_rescale_stats(self):
-        """option ks_fold_rescale: items (multiply-rescale pairs, once per stream) the last run() executed as one merged step"""
+        """options ks_fold_rescale / hyb_fold_rescale: items (multiply-rescale pairs, once per stream) the last run() executed as one merged step"""
         pairs = ctypes.c_int64()
         self.lw.hevm_last_run_fold_rescale_stats(self.vm, ctypes.byref(pairs))
         return pairs.value

@@ -131,7 +131,7 @@ void hevm_last_run_stats(void *vm, int64_t *op_counts /*[11]*/, int64_t *keyswit
  * them.  With the option on, the hops of a plan step that read one source ciphertext share one decomposition; with it off, or under option
  * "plan" = 0, every hop computes its own and the two numbers are equal. */
 void hevm_last_run_hoist_stats(void *vm, int64_t *hops, int64_t *decompositions);
-/* option "ks_fold_rescale" (SEAL-layout keys, off by default): the items -- multiply-rescale pairs, once per stream -- that the last run()'s plan
+/* options "ks_fold_rescale" (SEAL-layout keys) / "hyb_fold_rescale" (grouped digits, "hyb_fuse" != 0), both off by default: the items -- multiply-rescale pairs, once per stream -- that the last run()'s plan
  * executed as ONE merged step, the rescale folded into the multiply's key switch.  Every limb equals the default
  * path's; hevm_last_run_stats still counts a merged pair as one multiply and one rescale.  0 with the option off and under option "plan" = 0. */
 void hevm_last_run_fold_rescale_stats(void *vm, int64_t *pairs);
@@ -227,7 +227,7 @@ void hevm_load_ctxt(void *vm, int64_t reg, const char *path);
 
 /* Run-time options (dacapo_amd/csrc/options.hpp holds the ONE table: names, defaults, meaning).  VM options -- "logn", "primes",
  * "prime_bits", "ks_special", "ks_alpha", "secret_hw", "rot_compose", "plan", "plan_graph", "plan_lanes", "max_batch", "chain_fusion", "host_encoder",
- * "online_encode", "fold_rescale_boot", "ks_lazy_relin", "ks_flatten_sums", "ks_fold_add", "hyb_fold_add", "hyb_flatten_sums", "zenc_head", "hyb_mfma", "hyb_fuse", "seal_compr", "trace", "step_profile" -- are read when a VM (or kernel-level
+ * "online_encode", "fold_rescale_boot", "ks_lazy_relin", "ks_flatten_sums", "ks_fold_add", "hyb_fold_add", "hyb_flatten_sums", "hyb_fold_rescale", "zenc_head", "hyb_mfma", "hyb_fuse", "seal_compr", "trace", "step_profile" -- are read when a VM (or kernel-level
  * context) is created; launch-shape thresholds -- "small_tile_wgs", "tiny_tile_wgs", "ntt_full_min_limbs", ... -- at every launch.
  * Process-wide, not thread-safe (like the rest of this ABI).  An unknown name aborts with the list of names.  A caller that only knows
  * the reference's 18 symbols sets the same names through the single environment variable DACAPO_HEVM_OPTIONS="name=value,...". */
