@@ -229,18 +229,27 @@ __global__ __launch_bounds__(kBT) void b_tensor_sum_kernel(const MulSumItem *__r
     *reinterpret_cast<u64x2 *>(target + ((size_t)b * ell + i) * N + k) = c[2];
 }
 
+void b_tensor_sum(Context &c, const MulSumItem *d_items, const MulTerm *d_terms, u64 *target, int B, int ell, hipStream_t s)
+{
+    const size_t N = c.N;
+    DC_LAUNCH(b_tensor_sum_kernel, dim3((unsigned)(N / (2 * kBT)), ell, B), dim3(kBT), 0, s, d_items, d_terms, target, ell, N, c.d_mods);
+}
+
 // b_mul_relin's launch sequence for sums of products: the first kernel (or the tensor launch) and the last one walk the item's terms; the
 // key switch between them is b_ks_tail<1> itself, reading the summed c2 from w.target.
 void b_mul_sum_relin(Context &c, const BatchWs &w, const MulSumItem *d_items, const MulTerm *d_terms, const u64 *relin_key, int B, int ell,
                      hipStream_t s)
 {
-    refuse_grouped_digits(c, "b_mul_sum_relin", "; sums of products are relinearised once on SEAL-layout keys only");
+    if (c.hybrid()) {
+        hyb_mul_sum_relin(c, w, d_items, d_terms, relin_key, B, ell, s);
+        return;
+    }
     const size_t N = c.N;
     const KsShape sh = ks_shape(c, B, ell);
     if (sh.fused_mac)
         f_irows_tensor_sum(c, d_items, d_terms, ell, w.digits, w.target, B, s);
     else {
-        DC_LAUNCH(b_tensor_sum_kernel, dim3((unsigned)(N / (2 * kBT)), ell, B), dim3(kBT), 0, s, d_items, d_terms, w.target, ell, N, c.d_mods);
+        b_tensor_sum(c, d_items, d_terms, w.target, B, ell, s);
         f_irows_strided(c, w.target, (long)N, 0, ell, w.digits, (long)N, B * ell, s);
     }
     b_ks_tail<1>(c, w, sh, w.digits, nullptr, nullptr, relin_key, B, ell, s, w.target,

@@ -307,7 +307,6 @@ void dc_ct_mul_sum_relin(dc_context *ctx, uint64_t *dst, long dst_stride, const 
 {
     Context &c = *ctx->c;
     hipStream_t s = S(stream);
-    refuse_grouped_digits(c, "dc_ct_mul_sum_relin", " (ks_special > 1); the call is for SEAL-layout keys (use dc_ct_mul_relin and dc_ct_add)");
     if (count < 1 || count > kMulSumMax || ell < 1 || ell > c.max_level()) {
         fprintf(stderr, "[dacapo_amd] dc_ct_mul_sum_relin: %d products at level %d (1..%d products, level 1..%d)\n", count, ell, kMulSumMax,
                 c.max_level());

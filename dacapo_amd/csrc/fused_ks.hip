@@ -16,6 +16,7 @@
 // / L3-L5 that do not repeat work per target modulus / per accumulator; see the kernels.)  L2/L6 recompute the inverse COLS phase once per
 // target modulus (it is 1/(l+1) of that kernel's work) to keep every workgroup at two phases.
 #include "ks_mac.hpp"
+#include "tensor_sum.hpp"
 
 namespace dacapo {
 
@@ -180,50 +181,7 @@ __global__ __launch_bounds__(kTileThreads) void f_irows_kernel(Src src, u64 *__r
 }
 
 // ---- sums of signed ct x ct products relinearised once (plan.hpp MulSumItem, b_mul_sum_relin) ----------------------------------------------
-// Component COMP of sum_k s_k (a_k (x) b_k) at limb i, for the E coefficients g[] a thread owns: 0 = a0 b0, 1 = a0 b1 + a1 b0, 2 = a1 b1.
-// Terms of either sign gather in an accumulator of their own and the canonical difference is taken once at the end: modular arithmetic is
-// exact, so the value is what tensor + poly_add / poly_sub give term by term, in any order.
-// Ranges (modarith.hpp): an operand is a canonical residue, at most q - 1 < 2^60, so a product is below 2^120 and Acc128 takes 16 of them with
-// hi < 2^60, the precondition of reduce128_lazy.  A term adds at most 2 products (COMP 1) to ONE accumulator; both are folded every 8 terms
-// -- at most 16 products since the last fold -- and a folded accumulator restarts from its canonical residue, one more term below 2^60:
-// 16 (q - 1)^2 + 2^60 < 2^124 for operands q - 1 throughout, whatever the count and the signs.
-template <int E, int COMP>
-__device__ __forceinline__ void tensor_sum(u64 (&v)[E], const int (&g)[E], const MulTerm *__restrict__ terms, int first, int count, int i, size_t N,
-                                           const DModulus &M)
-{
-    Acc128 pos[E], neg[E];
-#pragma unroll
-    for (int j = 0; j < E; j++) pos[j].clear(), neg[j].clear();
-    auto mac_all = [&](Acc128(&a)[E], const u64 *x, const u64 *y) {
-#pragma unroll
-        for (int j = 0; j < E; j++) a[j].mac(x[g[j]], y[g[j]]);
-    };
-    for (int t = 0; t < count; t++) {
-        const MulTerm tm = terms[first + t];
-        const u64 *x = tm.a.limb(COMP == 2 ? 1 : 0, i, N), *y = tm.b.limb(COMP == 0 ? 0 : 1, i, N);
-        if (tm.sign > 0) // (wave-uniform)
-            mac_all(pos, x, y);
-        else
-            mac_all(neg, x, y);
-        if (COMP == 1) {
-            const u64 *x1 = tm.a.limb(1, i, N), *y0 = tm.b.limb(0, i, N);
-            if (tm.sign > 0)
-                mac_all(pos, x1, y0);
-            else
-                mac_all(neg, x1, y0);
-        }
-        if ((t & 7) == 7 && t + 1 < count) {
-#pragma unroll
-            for (int j = 0; j < E; j++) {
-                const u64 fp = pos[j].reduce(M), fn = neg[j].reduce(M);
-                pos[j].clear(), neg[j].clear();
-                pos[j].lo = fp, neg[j].lo = fn;
-            }
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < E; j++) v[j] = submod(pos[j].reduce(M), neg[j].reduce(M), M.q);
-}
+// (the term walk itself -- tensor_sum, with the accumulators' ranges -- is tensor_sum.hpp: the grouped-digit sequence walks the same tables)
 
 // L1 of a product sum: the term-walking form of f_irows_kernel<SrcTensorC2>.  z = b*ell + i.  The sum's c2 limb also goes to target[z] in NTT
 // form: the key switch's middle reads the digit a modulus owns from there (f_ks_frows_mac_kernel with a target, as it stands).

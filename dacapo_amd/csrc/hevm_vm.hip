@@ -486,6 +486,7 @@ void HEVM::init_context(int logN, int K, const u64 *primes, int dir_ksp, int dir
                         "three-part ciphertext has no grouped-digit key switch here\n", ksp, alpha);
         abort();
     }
+    hyb_lazy_relin = option(OPT_HYB_LAZY_RELIN) != 0 && (ksp > 1 || alpha > 1); // (SEAL-layout keys: ignored; ks_lazy_relin is the option there)
     ks_flatten = (int)option(OPT_KS_FLATTEN_SUMS);
     if (ks_flatten) {
         if (ks_flatten < 2 || ks_flatten > kFlattenMaxHops) {

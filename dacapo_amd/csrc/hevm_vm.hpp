@@ -323,6 +323,9 @@ class HEVM {
     // option ks_lazy_relin = 1 (SEAL-layout keys): sums of single-use ct x ct products are relinearised once (plan_exec.hip section 1b;
     // plan_relin.hpp names the groups, plan.hpp b_mul_sum_relin runs them).  Changes the rounding: off by default.
     bool ks_lazy_relin = false;
+    // option hyb_lazy_relin = 1 (grouped digits): the same groups, each one grouped-digit key switch (plan.hpp hyb_mul_sum_relin).  Changes the
+    // rounding: off by default; ignored on SEAL-layout keys.
+    bool hyb_lazy_relin = false;
     // option ks_flatten_sums = f (2 .. 6; with ks_hoist and ks_lazy_sum): stages of up to f hops of a rotate-and-add chain run as one hoisted lazy
     // sum with an addend (plan_exec.hip section 1a; plan_flatten.hpp names the groups).  Changes the rounding: off by default.
     int ks_flatten = 0;

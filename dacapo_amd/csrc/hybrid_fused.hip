@@ -21,6 +21,7 @@
 // option hyb_fuse = 2 keeps the two conversions as separate matrix-core launches (hyb_conv_mfma_kernel on pre-scaled inputs) inside this
 // sequence: F3 / F8 become conversion + two-phase transform.  Which of 1 / 2 is the default is decided by measurement.
 #include "plan.hpp"
+#include "tensor_sum.hpp"
 #include "tile_dispatch.hpp"
 
 namespace dacapo {
@@ -340,10 +341,8 @@ static void hybf_front(Context &c, const BatchWs &w, const void *items, KsItem r
     }
     if (with_mac) hyb_launch_mac(c, MODE, w, items, rot_single, key, B, use_slots, ell, s, MODE == 0, addend);     // F5
 }
-// F6 ... F9: the division by P of `B` accumulator pairs accq [2B][ell][N], accp [2B][ksp][N]; items[b] names where pair b goes
-template <int MODE>
-static void hybf_back(Context &c, const BatchWs &w, const u64 *accq, u64 *accp, const void *items, KsItem rot_single, HybOut single, int B, int ell,
-                      hipStream_t s)
+// F6 ... F8: the mod-down's correction t of `B` accumulator pairs accp [2B][ksp][N], after its forward COLS phase, in w.tmp [2B][ell][N]
+static void hybf_correction(Context &c, const BatchWs &w, u64 *accp, int B, int ell, hipStream_t s)
 {
     const size_t N = c.N;
     const int ksp = c.ksp, L = c.max_level();
@@ -355,6 +354,13 @@ static void hybf_back(Context &c, const BatchWs &w, const u64 *accq, u64 *accp, 
         launch_ntt_cols_fwd(c, w.tmp, (long)N, 2 * B * ell, nullptr, 0, ell, s);
     } else
         f8_moddown_fcols(c, accp, w.tmp, 2 * B, ell, s);                                                           // F8
+}
+// F6 ... F9: the division by P of `B` accumulator pairs accq [2B][ell][N], accp [2B][ksp][N]; items[b] names where pair b goes
+template <int MODE>
+static void hybf_back(Context &c, const BatchWs &w, const u64 *accq, u64 *accp, const void *items, KsItem rot_single, HybOut single, int B, int ell,
+                      hipStream_t s)
+{
+    hybf_correction(c, w, accp, B, ell, s);                                                                        // F6 ... F8
     f9_frows_final<MODE>(c, w.tmp, accq, items, rot_single, single, 2 * B, ell, s);                                // F9
 }
 template <int MODE>
@@ -484,6 +490,92 @@ void hybf_keyswitch(Context &c, const Workspace &w, CtView out, const u64 *base0
     BatchWs bw{ const_cast<u64 *>(target), w.ks_digits, w.ks_ext, w.ks_acc, w.ks_tmp };
     f1_irows<1>(c, nullptr, KsItem{}, target, w.ks_digits, 1, ell, 0, s);
     hybf_core<2>(c, bw, nullptr, KsItem{}, HybOut{ out, base0, base1 }, key, 1, 1, 0, ell, s);
+}
+
+// ---- lazy relinearisation (option hyb_lazy_relin; dc_ct_mul_sum_relin on a grouped-digit context) ---------------------------------------------
+// relin(sum_k s_k a_k (x) b_k), s_k = +-1, is ONE key switch where `count` multiplies take `count`.  The three-part sum T = (T0, T1, T2) is
+// formed in exact modular arithmetic (tensor_sum.hpp), T2 is all that enters the key switch and (T0, T1) is the base term that mode 1 of the
+// last kernel adds: dst = (T0, T1) + (acc_q - NTT(t)) P^-1 is Oracle.keyswitch(T2, relin, T0, T1) on the unchanged oracle, limb for limb.
+//   F1S        hybf_irows_tensor_sum_kernel: F1's inverse ROWS phase with T2 formed by its loader; T2 also goes to w.target in NTT form, where
+//              F5 (hyb_mac_kernel<1>) reads the limbs of a modulus' own digit
+//   F2 ... F8  as for a multiply: nothing there reads an item
+//   F9S        hybf_frows_sum_final_kernel: F9 with (T0 | T1) formed in its store epilogue -- nobody stores the base
+// One launch fewer than a multiply (no hyb_prepare_mul_kernel), whatever the count; per saved product a whole key switch.
+
+// F1S.  z = b * ell + i; F1's geometry and grid.  A ROWS tile's first inverse pass holds E consecutive coefficients per thread (F9's map)
+template <int K, int LOGE>
+__global__ __launch_bounds__(kTileThreads) void hybf_irows_tensor_sum_kernel(const MulSumItem *__restrict__ items, const MulTerm *__restrict__ terms,
+                                                                              u64 *__restrict__ target, u64 *__restrict__ digits, int ell,
+                                                                              const DModulus *__restrict__ mods, const u64 *__restrict__ itw, int logN,
+                                                                              int prime_major)
+{
+    __shared__ __attribute__((aligned(16))) u64 lds[TileGeo<LOGE>::LDS_ELEMS];
+    constexpr int EC = 1 << LOGE, NP = num_passes<LOGE>(K);
+    const int B = gridDim.y / ell;
+    const int i = prime_major ? blockIdx.y / B : blockIdx.y % ell, b = prime_major ? blockIdx.y % B : blockIdx.y / ell, z = b * ell + i;
+    const size_t N = (size_t)1 << logN;
+    const MulSumItem it = items[b];
+    const DModulus M = mods[i];
+    const int g0 = tile_gidx<K, LOGE, false>(NP - 1, logN, blockIdx.x, 0);
+    u64 x[EC];
+    tensor_sum_rows<EC, 2>(x, g0, terms, it.first, it.count, i, N, M);
+    u64 *tg = target + (size_t)z * N + g0, *out = digits + (size_t)z * N;
+#pragma unroll
+    for (int j = 0; j < EC; j += 2) *reinterpret_cast<u64x2 *>(tg + j) = u64x2{ x[j], x[j + 1] };
+    auto nold = [](int) -> u64 { return 0; };
+    ntt_tile_x<K, LOGE, false, true, false, true, false>(x, M, itw + ((size_t)i << logN), logN, blockIdx.x, nold, [=](int g, u64 v) { out[g] = v; }, lds);
+}
+
+// F9S: hybf_frows_final_kernel<.., 1> with the base sum_k s_k a_k0 b_k0 | sum_k s_k (a_k0 b_k1 + a_k1 b_k0) of limb i formed in the epilogue.
+// A kernel of its own and no fourth mode: the term table is one more argument, and an argument more moves the argument loads of modes 0 .. 2.
+// A thread reads every operand at its coefficients before it writes dst there, but polynomial 1's workgroups read a_k0 / b_k0 where
+// polynomial 0's write dst.c0: no destination may be an operand of the batch (dc_ct_mul_sum_relin writes such a one through scratch)
+template <int K, int LOGE>
+__global__ __launch_bounds__(kTileThreads) void hybf_frows_sum_final_kernel(const u64 *__restrict__ tmp, const u64 *__restrict__ accq,
+                                                                             const MulSumItem *__restrict__ items, const MulTerm *__restrict__ terms,
+                                                                             int ell, int ksp, int L, const DModulus *__restrict__ mods,
+                                                                             const u64 *__restrict__ dn, const u64 *__restrict__ tw, int logN,
+                                                                             int prime_major)
+{
+    __shared__ __attribute__((aligned(16))) u64 lds[TileGeo<LOGE>::LDS_ELEMS];
+    constexpr int EC = 1 << LOGE, NP = num_passes<LOGE>(K);
+    const size_t N = (size_t)1 << logN;
+    const int polys = gridDim.y / ell;
+    const int i = prime_major ? blockIdx.y / polys : blockIdx.y % ell, z = prime_major ? blockIdx.y % polys : blockIdx.y / ell, b = z >> 1, c = z & 1;
+    const DModulus M = mods[i];
+    const MulSumItem it = items[b];
+    const u64 pinv = dn[2 * ksp + L + i];
+    const u64 *in = tmp + ((size_t)z * ell + i) * N, *ac = accq + ((size_t)z * ell + i) * N;
+    u64 *dst = it.dst.limb(c, i, N);
+    u64 x[EC], base[EC];
+    auto nost = [](int, u64) {};
+    ntt_tile_x<K, LOGE, false, false, true, false, true>(x, M, tw + ((size_t)i << logN), logN, blockIdx.x, [=](int g) { return in[g]; }, nost, lds);
+    const int g0 = tile_gidx<K, LOGE, false>(NP - 1, logN, blockIdx.x, 0); // register j holds coefficient g0 + j
+    if (c == 0) // (uniform over the workgroup)
+        tensor_sum_rows<EC, 0>(base, g0, terms, it.first, it.count, i, N, M);
+    else
+        tensor_sum_rows<EC, 1>(base, g0, terms, it.first, it.count, i, N, M);
+#pragma unroll
+    for (int j = 0; j < EC; j += 2) {
+        const u64x2 a = *reinterpret_cast<const u64x2 *>(ac + g0 + j);
+        u64x2 r;
+        r.x = addmod(base[j], mulmod(submod(a.x, x[j], M.q), pinv, M), M.q);
+        r.y = addmod(base[j + 1], mulmod(submod(a.y, x[j + 1], M.q), pinv, M), M.q);
+        *reinterpret_cast<u64x2 *>(dst + g0 + j) = r;
+    }
+}
+
+// B sums at level ell -> d_items[b].dst (hyb_mul_sum_relin has checked the ring).  Scratch: what B multiplies reserve.
+void hybf_mul_sum_relin_tail(Context &c, const BatchWs &w, const MulSumItem *d_items, const MulTerm *d_terms, const u64 *relin_key, int B, int ell,
+                             hipStream_t s)
+{
+    u64 *accq = w.acc, *accp = w.acc + (size_t)B * 2 * ell * c.N;
+    DC_GEO_SWITCH(c.k2, B * ell, DC_LAUNCH((hybf_irows_tensor_sum_kernel<KK, LE>), grid, dim3(kTileThreads), 0, s, d_items, d_terms, w.target, w.digits,
+                                                    ell, c.d_mods, c.d_itw, c.logN, (int)(B > 1 && rows_prime_major(c))));                      // F1S
+    hybf_front<1>(c, w, nullptr, KsItem{}, relin_key, B, B, 0, ell, s);                                            // F2 ... F5
+    hybf_correction(c, w, accp, B, ell, s);                                                                        // F6 ... F8
+    DC_GEO_SWITCH(c.k2, 2 * B * ell, DC_LAUNCH((hybf_frows_sum_final_kernel<KK, LE>), grid, dim3(kTileThreads), 0, s, w.tmp, accq, d_items, d_terms,
+                                                        ell, c.ksp, c.max_level(), c.d_mods, c.d_hyb_dn, c.d_tw, c.logN, (int)rows_prime_major(c))); // F9S
 }
 
 // ---- a rescale folded into the multiply's mod-down (option hyb_fold_rescale; dc_ct_mul_relin_rescale on a grouped-digit context) --------------

@@ -452,6 +452,9 @@ __global__ __launch_bounds__(kHT) void hyb_final_kernel(const u64 *__restrict__ 
     } else if (MODE == 1) {
         const MulItem it = static_cast<const MulItem *>(items)[b];
         dst = it.dst.limb(c, i, N) + k, base = dst;                     // the tensor product's c0 / c1
+    } else if (MODE == 3) {
+        const MulSumItem it = static_cast<const MulSumItem *>(items)[b];
+        dst = it.dst.limb(c, i, N) + k, base = dst;                     // a sum of tensor products: its c0 / c1 (b_tensor_sum)
     } else {
         dst = single.out.limb(c, i, N) + k;
         const u64 *bp = c == 0 ? single.base0 : single.base1;
@@ -748,7 +751,8 @@ void hyb_launch_mac(Context &c, int mode, const BatchWs &w, const void *items, K
 
 // everything after `prepare`.  U = decompositions to compute (digits [U][l][N] in NTT form on entry, transformed in place here): U = B
 // except for rotation batches whose items share sources (use_slots); MODE 1 / 2: target [B][l][N] NTT form.
-template <int MODE>
+// FIN: the last kernel's mode where it is not MODE -- 3: a multiply's key switch whose items are MulSumItem (hyb_mul_sum_relin)
+template <int MODE, int FIN = MODE>
 static void hyb_core(Context &c, const BatchWs &w, const void *items, const u64 *shared_key, HybSingle single, KsItem rot_single, int B, int U,
                      int use_slots, int ell, hipStream_t s)
 {
@@ -763,7 +767,7 @@ static void hyb_core(Context &c, const BatchWs &w, const void *items, const u64 
     launch_ntt(c, true, accp, (long)N, 2 * B * ksp, nullptr, L, ksp, s);
     hyb_launch_conv(c, true, false, accp, w.tmp, 2 * B, ell, s);
     launch_ntt(c, false, w.tmp, (long)N, 2 * B * ell, nullptr, 0, ell, s);
-    DC_LAUNCH(hyb_final_kernel<MODE>, dim3(gx, (unsigned)ell, (unsigned)(2 * B)), dim3(kHT), 0, s, accq, w.tmp, items, single, rot_single, ell,
+    DC_LAUNCH(hyb_final_kernel<FIN>, dim3(gx, (unsigned)ell, (unsigned)(2 * B)), dim3(kHT), 0, s, accq, w.tmp, items, single, rot_single, ell,
                        ksp, L, N, c.d_mods, c.d_hyb_dn);
 }
 
@@ -828,6 +832,24 @@ void hyb_mul_relin(Context &c, const BatchWs &w, const MulItem *d_items, const u
                        hyb_fused() ? (u64 *)nullptr : w.digits, ell, c.N, c.d_mods);
     if (hyb_fused()) return hybf_mul_relin_tail(c, w, d_items, relin_key, B, ell, s);
     hyb_core<1>(c, w, d_items, relin_key, HybSingle{}, KsItem{}, B, B, 0, ell, s);
+}
+
+// B sums of signed ct x ct products, one key switch each (b_mul_sum_relin's grouped-digit form).  The fused sequence where lazy sums have it
+// (hyb_lazy_sum_supported: hyb_fuse != 0 and N >= 512) forms the three parts in its first and last kernel; otherwise ONE tensor-sum launch
+// leaves (T0, T1) in dst and T2 in w.target, whose copy in w.digits hyb_core transforms in place, and the last kernel adds onto dst
+void hybf_mul_sum_relin_tail(Context &c, const BatchWs &w, const MulSumItem *d_items, const MulTerm *d_terms, const u64 *relin_key, int B, int ell,
+                             hipStream_t s);
+void hyb_mul_sum_relin(Context &c, const BatchWs &w, const MulSumItem *d_items, const MulTerm *d_terms, const u64 *relin_key, int B, int ell,
+                       hipStream_t s)
+{
+    if (ell < 1 || ell > c.max_level() || B < 1) {
+        fprintf(stderr, "[dacapo_amd] hyb_mul_sum_relin: %d sums at level %d (level 1..%d)\n", B, ell, c.max_level());
+        abort();
+    }
+    if (hyb_lazy_sum_supported(c)) return hybf_mul_sum_relin_tail(c, w, d_items, d_terms, relin_key, B, ell, s);
+    b_tensor_sum(c, d_items, d_terms, w.target, B, ell, s);
+    DC_LAUNCH(hyb_copy_kernel, dim3((unsigned)((size_t)B * ell * c.N / (2 * kHT))), dim3(kHT), 0, s, w.digits, w.target);
+    hyb_core<1, 3>(c, w, d_items, relin_key, HybSingle{}, KsItem{}, B, B, 0, ell, s);
 }
 
 void hybf_mul_relin_rescale_tail(Context &c, const BatchWs &w, const MulRsItem *d_items, const u64 *relin_key, int B, int ell, hipStream_t s);

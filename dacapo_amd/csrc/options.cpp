@@ -47,6 +47,7 @@ static const OptDef kDefs[OPT_COUNT] = {
     { "hyb_fold_add", 0 }, // measured: profiles/hyb_fold_add_ab.txt
     { "hyb_flatten_sums", 0 }, // profiles/hyb_flatten_ab.txt
     { "hyb_fold_rescale", 0 }, // profiles/hyb_fold_rescale_ab.txt
+    { "hyb_lazy_relin", 0 }, // changes the rounding; profiles/hyb_lazy_relin_ab.txt
     { "zenc_head", 1 },
     { "seal_compr", 0 },
     { "trace", 0 },

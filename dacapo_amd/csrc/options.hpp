@@ -48,6 +48,7 @@ enum Opt : int {
     OPT_HYB_FOLD_ADD,      // grouped digits (ks_special > 1): ks_fold_add's rule for that mode -- the last hop of a rotate instruction takes the other term of a two-term sum as its addend, P y beside the base term in the data-prime accumulators (hybrid_ks.hip hyb_mac_kernel<3>; hyb_prepare_rot_kernel under hyb_fuse = 0), and writes the sum itself; never a member of a lazy sum (hyb_lazy_sum, hyb_double_hoist) or a hop of the boot context; every limb the same (0 = off until a later change flips it: profiles/hyb_fold_add_ab.txt; hevm_last_run_add_fold_stats counts the folds; ignored on SEAL-layout keys and by plan = 0)
     OPT_HYB_FLATTEN_SUMS,  // grouped digits (ks_special > 1), with hyb_lazy_sum and the fused sequence (hyb_fuse != 0): ks_flatten_sums' rule for that mode -- rotate-and-add chains y' = y + rotate(y, o) run as ONE stage per up to this many hops (2 .. 6; plan_flatten.hpp): the 2^h - 1 rotations of the stage's first y read its one decomposition, one Acc128 pair runs across them and y rides as P y on the data primes (hybrid_ks.hip hyb_mac_stage_kernel, hybrid_fused.hip hybf_rotate_stages); a stage whose composite offsets lack a key runs as written -- hevm_flatten_offsets lists them (changes the rounding: 0 = off; hevm_plan_flatten_groups names the groups, hevm_last_run_flatten_stats counts them; without hyb_lazy_sum, with hyb_fuse = 0 or rot_compose = 1, or on SEAL-layout keys it aborts; plan = 0 ignores it)
     OPT_HYB_FOLD_RESCALE,  // grouped digits (ks_special > 1), the fused sequence (hyb_fuse != 0): ks_fold_rescale's rule for that mode -- a ct x ct multiply whose value only a rescale reads runs with that rescale as ONE sequence: the mod-down's correction and the rescale's lift are one polynomial per kept limb (hybrid_fused.hip hybf_mul_relin_rescale_tail); every limb equals the default pair's (off until measured: profiles/hyb_fold_rescale_ab.txt; hevm_last_run_fold_rescale_stats counts the pairs; ignored on SEAL-layout keys)
+    OPT_HYB_LAZY_RELIN,    // grouped digits (ks_special > 1): ks_lazy_relin's rule for that mode -- the same pass, the same groups, ONE grouped-digit key switch of the summed three-part ciphertext per group (hybrid_ks.hip hyb_mul_sum_relin; hybrid_fused.hip hybf_irows_tensor_sum_kernel / hybf_frows_sum_final_kernel under hyb_fuse != 0, one tensor-sum launch and the un-fused sequence under hyb_fuse = 0) (changes the rounding -- one mod-down per sum instead of one per product: off; hevm_plan_relin_groups names the groups, hevm_last_run_relin_stats counts them; ignored on SEAL-layout keys and by plan = 0)
     OPT_ZENC_HEAD,         // plan mode, the zero-encryptions made at the start of run(): 1 transforms only u -- the public key's product and the noise ride on the divide-and-round (hevm_vm.hip plan_zero_encrypt: 3l + 3 transforms per item at target level l); 0 the encryption as Encryptor::encrypt does it, batched (5l + 5).  Every limb is the same
     OPT_SEAL_COMPR,        // compression of written .seal files: 0 none, 1 zlib, 2 zstd
     OPT_TRACE,             // plan statistics on stderr (2: per wave)

@@ -57,7 +57,7 @@ struct MulRsItem : MulItem {
     long mul_stride = 0;
 };
 // dst = relinearize(sum of `count` signed tensor products terms[first ...]) with ONE key switch (dc_ct_mul_sum_relin; fused_ks.hip
-// f_irows_tensor_sum_kernel / f_frows_sum_final_kernel).  The three-part sum is formed in exact modular arithmetic, so c0, c1 and the key-switch
+// f_irows_tensor_sum_kernel / f_frows_sum_final_kernel, hybrid_fused.hip hybf_irows_tensor_sum_kernel / hybf_frows_sum_final_kernel).  The three-part sum is formed in exact modular arithmetic, so c0, c1 and the key-switch
 // target equal Oracle.tensor per term + poly_add / poly_sub; the rounding is that of one mod-down instead of `count`.
 struct MulTerm {  // sign * (a (x) b)
     CtView a, b;
@@ -68,7 +68,7 @@ struct MulSumItem {
     int first, count; // 1 <= count <= kMulSumMax
 };
 // The cap bounds the dependent walk (table entry -> pointers -> limbs, one round trip per term) that the first and the last kernel of the key
-// switch make per tile; the accumulators themselves fold every 8 terms and hold any count (fused_ks.hip tensor_sum).
+// switch make per tile; the accumulators themselves fold every 8 terms and hold any count (tensor_sum.hpp).
 constexpr int kMulSumMax = 32;
 struct RsItem {   // dst = rescale_to_next(expr), expr = ((src | sum of `count` terms srcs[first ...]) + add on c0) * mul
     CtView src, dst;
@@ -160,9 +160,11 @@ void b_mul_relin_rescale(Context &c, const BatchWs &w, const MulRsItem *d_items,
 void b_rescale(Context &c, const BatchWs &w, const RsItem *d_items, int B, int ell, hipStream_t s, const SumSrc *d_srcs = nullptr,
                const Handoff &h = Handoff{});
 // B sums of signed ct x ct products, each relinearised by ONE key switch: b_mul_relin's launch sequence (same count, same middle) with the
-// term-walking first and last kernels.  SEAL-layout keys only (aborts otherwise).  No destination may be an operand of the batch.
+// term-walking first and last kernels.  Grouped digits: hyb_mul_sum_relin.  No destination may be an operand of the batch.
 void b_mul_sum_relin(Context &c, const BatchWs &w, const MulSumItem *d_items, const MulTerm *d_terms, const u64 *relin_key, int B, int ell,
                      hipStream_t s);
+// the three parts of B sums in one launch, where no key-switch kernel forms them: items[b].dst = (T0, T1), target[b] = T2 ([B][ell][N])
+void b_tensor_sum(Context &c, const MulSumItem *d_items, const MulTerm *d_terms, u64 *target, int B, int ell, hipStream_t s);
 // hoisted rotations on SEAL-layout keys (hoist_ks.hip; option ks_hoist, dc_ct_rotate_hoisted): B hops over U <= B decompositions, digits taken
 // BEFORE the automorphism (oracle orc_rotate_ks_hybrid at one special prime).  d_items[b].slot indexes d_sources[0 .. U): items with the
 // identity element whose src is the source ciphertext.  w is sized as for B default hops.
@@ -195,6 +197,11 @@ void hyb_mul_relin(Context &c, const BatchWs &w, const MulItem *d_items, const u
 // b_mul_relin_rescale's grouped-digit form (hybrid_fused.hip hybf_mul_relin_rescale_tail): the rescale's lift rides the mod-down's correction,
 // one forward transform per kept limb.  Aborts unless ks_shape(c, B, ell).hyb_folds_rescale().  No destination may be an operand of the batch
 void hyb_mul_relin_rescale(Context &c, const BatchWs &w, const MulRsItem *d_items, const u64 *relin_key, int B, int ell, hipStream_t s);
+// b_mul_sum_relin's grouped-digit form (option hyb_lazy_relin, dc_ct_mul_sum_relin): d_items[b].dst = Oracle.keyswitch(T2, relin, T0, T1) of
+// the three-part sum T of the item's terms, at level ell >= 1.  hybrid_fused.hip hybf_mul_sum_relin_tail where hyb_lazy_sum_supported(c), the
+// un-fused sequence behind one tensor-sum launch otherwise.  Scratch as for B multiplies.  No destination may be an operand of the batch
+void hyb_mul_sum_relin(Context &c, const BatchWs &w, const MulSumItem *d_items, const MulTerm *d_terms, const u64 *relin_key, int B, int ell,
+                       hipStream_t s);
 void hyb_keyswitch(Context &c, const Workspace &w, CtView out, const u64 *base0, const u64 *base1, const u64 *target, const u64 *key, int ell,
                    hipStream_t s);
 // NTT-equivalents of one key switch at level ell: (l + 1)(l + 2) for SEAL's scheme, G (l + ksp) + 2 ksp + 2 l with grouped digits

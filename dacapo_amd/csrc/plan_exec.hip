@@ -450,7 +450,7 @@ void HEVM::build_plan()
         }
     }
 
-    // ---- 1b. lazy relinearisation (option ks_lazy_relin; SEAL-layout keys) ---------------------------------------------------------
+    // ---- 1b. lazy relinearisation (options ks_lazy_relin / hyb_lazy_relin) ------------------------------------------------------------
     // relin(sum_k s_k a_k (x) b_k) is ONE key switch of the summed three-part ciphertext (plan.hpp b_mul_sum_relin) where the program's mulcc
     // instructions run one each.  plan_relin.hpp finds the groups -- maximal trees of addcc / negate over mulcc results that nothing else reads,
     // at one level -- on the loaded instructions, as section 1a does, before any other folding (an add of a flattened stage has a rotation for
@@ -459,8 +459,10 @@ void HEVM::build_plan()
     // away and their values are never materialised.  A value counts as read by the program's end only through a RESULT register: a register
     // that merely still names an absorbed product when the program ends is not refreshed by such a run.  That is a different rounding than n
     // mulcc instructions (one mod-down instead of n): off by default, and the groups are exported (hevm_plan_relin_groups) for the oracle's
-    // replay.
-    if (ks_lazy_relin && !c.hybrid()) {
+    // replay.  Grouped digits (option hyb_lazy_relin; ks_lazy_relin is the SEAL-layout option and aborts there): the same pass, pop, replication
+    // and buckets; the step runs hyb_mul_sum_relin and, like every grouped-digit step, takes and offers no hand-off.  A group followed by its
+    // only rescale stays two steps under hyb_fold_rescale: that rule looks for a P_MULCC.
+    if (c.hybrid() ? hyb_lazy_relin : ks_lazy_relin) {
         auto node_pop = [&](int op) { return inst_pop(op, ops[(size_t)op].opcode == 6 ? P_SUM : P_NEG); }; // an addcc or a negate of a tree
         for (const RelinGroup &g : flow_relin_groups(flow, ops.data(), kMulSumMax)) {
             const int closing = node_pop(g.closing_op);

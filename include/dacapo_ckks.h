@@ -113,7 +113,8 @@ void dc_ct_relin(dc_context *ctx, uint64_t *dst, long dst_stride, const uint64_t
  * sign +1 is dc_ct_mul_relin exactly.  as / bs: HOST arrays of `count` device pointers to ciphertexts of poly stride `src_stride`; signs: HOST
  * array of +1 / -1.  1 <= count <= DC_CT_MUL_SUM_MAX; more aborts with a message (split the sum and dc_ct_add the parts).  as[k] may equal bs[k]
  * (a square), an operand may appear in several terms, dst may be an operand (it is then written through scratch and copied: one more launch).
- * SEAL-layout contexts only (a grouped-digit context aborts with a message).  Scratch is kept in the context.  The item table is copied
+ * Either key mode: on a grouped-digit context (dc_context_create_hybrid) it is one grouped-digit key switch, the oracle's keyswitch under
+ * set_hybrid(ks, alpha), level 1 and up.  Scratch is kept in the context.  The item table is copied
  * synchronously: the call waits for earlier work on `stream`. */
 #define DC_CT_MUL_SUM_MAX 32
 void dc_ct_mul_sum_relin(dc_context *ctx, uint64_t *dst, long dst_stride, const uint64_t *const *as, const uint64_t *const *bs,

@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """A/B of lazy relinearisation at the kernel-level ABI (dc_ct_mul_sum_relin; csrc/fused_ks.hip f_irows_tensor_sum_kernel /
 f_frows_sum_final_kernel), one box, ONE process, warm-up first:
-    python tools/legs/ks_lazy_relin_ab.py [--rounds 5] [--calls 50] [--steps 20] [--out profiles/ks_lazy_relin_ab.txt] [--skip-run]
+    python tools/legs/ks_lazy_relin_ab.py [--rounds 5] [--calls 50] [--steps 20] [--out profiles/ks_lazy_relin_ab.txt] [--skip-run] [--grouped]
+--grouped: the same two legs under grouped-digit keys (csrc/hybrid_fused.hip hybf_irows_tensor_sum_kernel / hybf_frows_sum_final_kernel;
+profiles/hyb_lazy_relin_ab.txt): (a) at N = 2^17, 31 + 9 primes, 4 digits of 8, l = 12 and l = 31; (b) on a VM with two special primes, option
+hyb_lazy_relin.
   (a) per sum, device events: n x dc_ct_mul_relin + (n - 1) x dc_ct_add against ONE dc_ct_mul_sum_relin for n = 2, 3, 8 products at N = 2^15,
 l = 2 and l = 13.  The two forms alternate, --rounds rounds of --calls sums each; mean and spread (min .. max) of the rounds, us per sum.
 dc_ct_mul_sum_relin's time includes its synchronous copy of the term table (the call waits for the stream), so back-to-back calls do not
@@ -26,16 +29,16 @@ def say(s):
     LINES.append(s + "\n")
 
 
-def op_leg(logN, K, levels, counts, rounds, calls):
+def op_leg(logN, K, levels, counts, rounds, calls, special=1, alpha=1):
     import numpy as np
 
     from dacapo_amd import lowlevel as ll
 
     L, N = ll.lib(), 1 << logN
-    ctx = ll.Context(logN, K)
+    ctx = ll.Context(logN, K, special=special, alpha=alpha)
     rng = np.random.default_rng(1)
     q = np.array(ctx.primes, dtype=np.uint64)
-    key = rng.integers(0, 1 << 59, size=(K - 1, 2, K, N), dtype=np.uint64) % q[None, None, :, None]  # timing only: any residues
+    key = rng.integers(0, 1 << 59, size=(ctx.key_digits, 2, K, N), dtype=np.uint64) % q[None, None, :, None]  # timing only: any residues
     dkey = ll.DeviceBuffer.from_host(key)
     del key
     e0, e1 = L.dc_event_create(), L.dc_event_create()
@@ -78,7 +81,7 @@ def op_leg(logN, K, levels, counts, rounds, calls):
                 f"difference {m['summed'] - m['separate']:+8.1f} us   ratio {m['summed'] / m['separate']:5.3f}   {verdict}")
 
 
-def run_leg(name, steps):
+def run_leg(name, steps, option="ks_lazy_relin", **vm_kw):
     import numpy as np
 
     from dacapo_amd import hevm_asm as ha
@@ -87,7 +90,7 @@ def run_leg(name, steps):
     fx = ha.read_fixture(ROOT / "tests" / "golden" / "suite" / name)
     vms = []
     for tag, lazy in (("off A", 0), ("on", 1), ("off B", 0)):
-        vm = runner.HEVM(fresh=True, logN=15, num_primes=14, vm_options={"ks_lazy_relin": lazy})
+        vm = runner.HEVM(fresh=True, logN=15, **(vm_kw or {"num_primes": 14}), vm_options={option: lazy})
         vm.load_mem(fx["cst"], fx["hevm"])
         for i, x in enumerate(fx["inputs"]):
             vm.setInput(i, x)
@@ -104,7 +107,7 @@ def run_leg(name, steps):
         rms = float(np.sqrt(np.mean((vm.getOutput() - fx["expected"]) ** 2)))
         mean[tag] = sum(ts) / len(ts)
         rs = vm.relin_stats()
-        say(f"run {name} ks_lazy_relin {tag:5s}: mean {mean[tag]:8.3f} ms ({min(ts):.3f} .. {max(ts):.3f})   groups {rs['groups']} products {rs['products']}   "
+        say(f"run {name} {option} {tag:5s}: mean {mean[tag]:8.3f} ms ({min(ts):.3f} .. {max(ts):.3f})   groups {rs['groups']} products {rs['products']}   "
             f"key switches {vm.stats()['keyswitches']:3d}   rms vs cleartext {rms:.3e}")
     off = 0.5 * (mean["off A"] + mean["off B"])
     say(f"run {name} on - off {mean['on'] - off:+8.3f} ms   off/off spread {abs(mean['off A'] - mean['off B']):6.3f} ms")
@@ -124,9 +127,14 @@ def main():
         return default
 
     rounds, calls, steps, out = int(opt("--rounds", 5)), int(opt("--calls", 50)), int(opt("--steps", 20)), opt("--out", None)
-    op_leg(15, 14, (2, 13), (2, 3, 8), rounds, calls)
-    if "--skip-run" not in args:
-        run_leg("Multivariate", steps)
+    if "--grouped" in args:  # config 4's geometry: N = 2^17, 31 + 9 primes, 4 digits of 8 (csrc/hybrid_fused.hip hybf_mul_sum_relin_tail)
+        op_leg(17, 40, (12, 31), (2, 3, 8), rounds, calls, special=9, alpha=8)
+        if "--skip-run" not in args:
+            run_leg("Multivariate", steps, "hyb_lazy_relin", num_primes=15, ks_special=2, ks_alpha=2)
+    else:
+        op_leg(15, 14, (2, 13), (2, 3, 8), rounds, calls)
+        if "--skip-run" not in args:
+            run_leg("Multivariate", steps)
     if out:
         Path(out).write_text("".join(LINES))
 
