@@ -56,6 +56,19 @@ constexpr int kConvChunk = LOGE == 3 ? 4 : 8;
 __device__ __forceinline__ u32 w_lo30(u64 w) { return (u32)w & 0x3FFFFFFFu; }
 __device__ __forceinline__ u32 w_hi30(u64 w) { return (u32)(w >> 30); }
 
+// Workgroup row blockIdx.y of a ROWS-phase grid with `rows` limbs per item (or polynomial): limb i of item z.
+// prime_major: the limbs of one prime are adjacent in launch order, so their twiddle tiles come out of L2 (ntt_kernels.hip).
+struct HfRow {
+    int i, z;
+};
+__device__ __forceinline__ HfRow hf_row(int rows, int prime_major)
+{
+    const int n = gridDim.y / rows;
+    const int i = prime_major ? blockIdx.y / n : blockIdx.y % rows;
+    const int z = prime_major ? blockIdx.y % n : blockIdx.y / rows;
+    return HfRow{ i, z };
+}
+
 // true for the first item of the batch that names this item's decomposition slot (wave-uniform; every wave of the workgroup agrees)
 __device__ __forceinline__ bool hf_first_of_slot(const KsItem *__restrict__ items, int b)
 {
@@ -79,9 +92,8 @@ __global__ __launch_bounds__(kTileThreads) void hybf_irows_kernel(const KsItem *
                                                                    int prime_major)
 {
     __shared__ __attribute__((aligned(16))) u64 lds[TileGeo<LOGE>::LDS_ELEMS];
-    // (prime_major: the B limbs of one prime adjacent in launch order -- their twiddle tiles come out of L2, ntt_kernels.hip)
-    const int B = gridDim.y / ell;
-    const int i = prime_major ? blockIdx.y / B : blockIdx.y % ell, b = prime_major ? blockIdx.y % B : blockIdx.y / ell, z = b * ell + i;
+    const HfRow r = hf_row(ell, prime_major);
+    const int i = r.i, b = r.z, z = b * ell + i;
     const size_t N = (size_t)1 << logN;
     const u64 *in;
     size_t slot = (size_t)b;
@@ -247,9 +259,8 @@ __global__ __launch_bounds__(kTileThreads) void hybf_frows_final_kernel(const u6
     __shared__ __attribute__((aligned(16))) u64 lds[TileGeo<LOGE>::LDS_ELEMS];
     constexpr int EC = 1 << LOGE, NP = num_passes<LOGE>(K);
     const size_t N = (size_t)1 << logN;
-    // (prime_major: the 2 B limbs of one prime adjacent in launch order -- their twiddle tiles come out of L2, ntt_kernels.hip)
-    const int polys = gridDim.y / ell;
-    const int i = prime_major ? blockIdx.y / polys : blockIdx.y % ell, z = prime_major ? blockIdx.y % polys : blockIdx.y / ell, b = z >> 1, c = z & 1;
+    const HfRow r = hf_row(ell, prime_major);
+    const int i = r.i, z = r.z, b = z >> 1, c = z & 1;
     const DModulus M = mods[i];
     const u64 pinv = dn[2 * ksp + L + i];
     const u64 *in = tmp + ((size_t)z * ell + i) * N, *ac = accq + ((size_t)z * ell + i) * N;
@@ -323,6 +334,10 @@ void hyb_launch_mac_groups(Context &c, const BatchWs &w, const KsItem *items, co
                            bool addend);
 void hyb_launch_mac_stages(Context &c, const BatchWs &w, const KsItem *items, const KsItem *stages, int G, int ell, hipStream_t s);
 
+// option hyb_fuse = 2: the two conversions as separate matrix-core launches, from the level where hyb_launch_conv takes that form.  One answer for
+// F3, F8 and F8': the rescale tail's lift reads a w.tmp that only the separate conversion writes
+static bool hybf_separate_conv(const Context &c, int ell) { return option(OPT_HYB_FUSE) == 2 && c.hyb_mfma && c.N >= 512 && ell >= 4; }
+
 // F2 ... F5: everything between F1 and the accumulators.  digits [U][ell][N] hold the inverse ROWS phase's output.
 template <int MODE>
 static void hybf_front(Context &c, const BatchWs &w, const void *items, KsItem rot_single, const u64 *key, int B, int U, int use_slots, int ell,
@@ -330,9 +345,8 @@ static void hybf_front(Context &c, const BatchWs &w, const void *items, KsItem r
 {
     const size_t N = c.N;
     const int E = c.hyb_ext(ell);
-    const bool separate_conv = option(OPT_HYB_FUSE) == 2 && c.hyb_mfma && N >= 512 && ell >= 4;
     launch_ntt_cols_inv(c, w.digits, (long)N, U * ell, nullptr, 0, ell, s, c.hyb_upmods(ell));                    // F2
-    if (separate_conv) {
+    if (hybf_separate_conv(c, ell)) {
         hyb_launch_conv(c, false, true, w.digits, w.ext, U, ell, s);
         launch_ntt(c, false, w.ext, (long)N, U * E, c.hyb_pidx(ell), 0, E, s);
     } else {
@@ -346,10 +360,9 @@ static void hybf_correction(Context &c, const BatchWs &w, u64 *accp, int B, int 
 {
     const size_t N = c.N;
     const int ksp = c.ksp, L = c.max_level();
-    const bool separate_conv = option(OPT_HYB_FUSE) == 2 && c.hyb_mfma && N >= 512 && ell >= 4;
     launch_ntt_rows_inv(c, accp, (long)N, 2 * B * ksp, nullptr, L, ksp, s);                                        // F6
     f7_icols_special(c, accp, 2 * B, s);                                                                           // F7
-    if (separate_conv) {
+    if (hybf_separate_conv(c, ell)) {
         hyb_launch_conv(c, true, true, accp, w.tmp, 2 * B, ell, s);
         launch_ntt_cols_fwd(c, w.tmp, (long)N, 2 * B * ell, nullptr, 0, ell, s);
     } else
@@ -511,8 +524,8 @@ __global__ __launch_bounds__(kTileThreads) void hybf_irows_tensor_sum_kernel(con
 {
     __shared__ __attribute__((aligned(16))) u64 lds[TileGeo<LOGE>::LDS_ELEMS];
     constexpr int EC = 1 << LOGE, NP = num_passes<LOGE>(K);
-    const int B = gridDim.y / ell;
-    const int i = prime_major ? blockIdx.y / B : blockIdx.y % ell, b = prime_major ? blockIdx.y % B : blockIdx.y / ell, z = b * ell + i;
+    const HfRow r = hf_row(ell, prime_major);
+    const int i = r.i, b = r.z, z = b * ell + i;
     const size_t N = (size_t)1 << logN;
     const MulSumItem it = items[b];
     const DModulus M = mods[i];
@@ -540,8 +553,8 @@ __global__ __launch_bounds__(kTileThreads) void hybf_frows_sum_final_kernel(cons
     __shared__ __attribute__((aligned(16))) u64 lds[TileGeo<LOGE>::LDS_ELEMS];
     constexpr int EC = 1 << LOGE, NP = num_passes<LOGE>(K);
     const size_t N = (size_t)1 << logN;
-    const int polys = gridDim.y / ell;
-    const int i = prime_major ? blockIdx.y / polys : blockIdx.y % ell, z = prime_major ? blockIdx.y % polys : blockIdx.y / ell, b = z >> 1, c = z & 1;
+    const HfRow r = hf_row(ell, prime_major);
+    const int i = r.i, z = r.z, b = z >> 1, c = z & 1;
     const DModulus M = mods[i];
     const MulSumItem it = items[b];
     const u64 pinv = dn[2 * ksp + L + i];
@@ -657,8 +670,8 @@ __global__ __launch_bounds__(kTileThreads) void hybf_irows_fold_kernel(u64 *__re
     __shared__ __attribute__((aligned(16))) u64 lds[TileGeo<LOGE>::LDS_ELEMS];
     constexpr int EC = 1 << LOGE, NP = num_passes<LOGE>(K);
     const size_t N = (size_t)1 << logN;
-    const int R = ksp + 1, polys = gridDim.y / R;
-    const int j = prime_major ? blockIdx.y / polys : blockIdx.y % R, z = prime_major ? blockIdx.y % polys : blockIdx.y / R;
+    const HfRow r = hf_row(ksp + 1, prime_major);
+    const int j = r.i, z = r.z;
     if (j < ksp) {
         const int p = L + j;
         u64 *a = accp + (((size_t)z * ksp + j) << logN);
@@ -829,8 +842,9 @@ __global__ __launch_bounds__(kTileThreads) void hybf_frows_fold_final_kernel(con
     __shared__ __attribute__((aligned(16))) u64 lds[TileGeo<LOGE>::LDS_ELEMS];
     constexpr int EC = 1 << LOGE, NP = num_passes<LOGE>(K);
     const size_t N = (size_t)1 << logN;
-    const int D = ell - 1, polys = gridDim.y / D;
-    const int i = prime_major ? blockIdx.y / polys : blockIdx.y % D, z = prime_major ? blockIdx.y % polys : blockIdx.y / D, c = z & 1;
+    const int D = ell - 1;
+    const HfRow r = hf_row(D, prime_major);
+    const int i = r.i, z = r.z, c = z & 1;
     const DModulus M = mods[i];
     const MulRsItem it = items[z >> 1];
     const u64 pinv = dn[2 * ksp + L + i];
@@ -857,7 +871,6 @@ void hybf_mul_relin_rescale_tail(Context &c, const BatchWs &w, const MulRsItem *
 {
     const size_t N = c.N;
     const int ksp = c.ksp, L = c.max_level(), D = ell - 1;
-    const bool separate_conv = option(OPT_HYB_FUSE) == 2 && c.hyb_mfma && N >= 512 && ell >= 4;
     u64 *accq = w.acc, *accp = w.acc + (size_t)B * 2 * ell * N, *rowd = w.ext;
     DC_LAUNCH(hybf_fold_target_kernel, dim3((unsigned)(N / 512), (unsigned)ell, (unsigned)B), dim3(256), 0, s, d_items, w.target, ell, N, c.d_mods);
     f1_irows<1>(c, nullptr, KsItem{}, w.target, w.digits, B, ell, 0, s);
@@ -866,7 +879,7 @@ void hybf_mul_relin_rescale_tail(Context &c, const BatchWs &w, const MulRsItem *
                                                                ksp, L, c.d_mods, c.d_pmod, c.d_itw, c.logN, (int)rows_prime_major(c)));        // F6'
     DC_GEO_SWITCH(c.k1, 2 * B * (ksp + 1), DC_LAUNCH((hybf_icols_fold_kernel<KK, LE>), grid, dim3(kTileThreads), 0, s, accp, rowd, ell, ksp, L,
                                                                c.d_hyb_dnmods, c.d_mods, c.d_hyb_hp, c.d_itw, c.logN));                        // F7'
-    if (separate_conv) {                                                                                                                        // F8'
+    if (hybf_separate_conv(c, ell)) {                                                                                                           // F8'
         hyb_launch_conv(c, true, true, accp, w.tmp, 2 * B, ell, s);
         DC_GEO_SWITCH(c.k1, 2 * B * D, DC_LAUNCH((hybf_fold_lift_fcols_kernel<KK, LE, false>), grid, dim3(kTileThreads), 0, s, accp, w.tmp, rowd, d_items,
                                                           ell, ksp, L, c.K, c.d_mods, c.d_hyb_dn, c.d_inv_last, c.d_half_mod, c.d_tw, c.logN));

@@ -132,6 +132,9 @@ __global__ __launch_bounds__(kHT) void hyb_modup_kernel(const u64 *__restrict__ 
     }
 }
 
+// a pair read through a Galois index g: an aligned pair of outputs reads an aligned pair of inputs, swapped where g is odd
+__device__ __forceinline__ u64x2 hyb_galois_pair(u64x2 v, u32 g) { return (g & 1u) ? u64x2{ v.y, v.x } : v; }
+
 // inner products with the key.  grid = (N/512, B, M).  MODE 0 rotation items (per-item key; every operand -- a raised limb of the item's
 // slot, or the NTT-form limb of src.c1 itself where the modulus belongs to the digit -- is read THROUGH the item's Galois permutation),
 // 1 ct x ct items (shared key), 2 one key switch by value,
@@ -187,7 +190,7 @@ __global__ __launch_bounds__(kHT) void hyb_mac_kernel(u64 *__restrict__ accq, u6
         u64x2 x = xn;
         const u64x2 y0 = y0n, y1 = y1n;
         if (g + 1 < G) fetch(g + 1, xn, y0n, y1n);
-        if (ROT && (gsrc & 1u)) x = u64x2{ x.y, x.x };
+        if (ROT) x = hyb_galois_pair(x, gsrc);
 #pragma unroll
         for (int e = 0; e < 2; e++) {
             a0[e].mac(x[e], y0[e]);
@@ -261,7 +264,7 @@ __global__ __launch_bounds__(kHT) void hyb_mac_group_kernel(u64 *__restrict__ ac
             u64x2 x = xn;
             const u64x2 y0 = y0n, y1 = y1n;
             if (g + 1 < G) fetch(g + 1, xn, y0n, y1n);
-            if (gsrc & 1u) x = u64x2{ x.y, x.x };
+            x = hyb_galois_pair(x, gsrc);
 #pragma unroll
             for (int e = 0; e < 2; e++) {
                 a0[e].mac(x[e], y0[e]);
@@ -358,7 +361,7 @@ __global__ __launch_bounds__(kHT) void hyb_mac_stage_kernel(u64 *__restrict__ ac
                 fetch(0, gsn, keyn, xn, y0n, y1n);
                 if (data) vn = *reinterpret_cast<const u64x2 *>(src.limb(0, mi, N) + (gsn & ~1u));
             }
-            if (gs & 1u) x = u64x2{ x.y, x.x };
+            x = hyb_galois_pair(x, gs);
 #pragma unroll
             for (int e = 0; e < 2; e++) {
                 a0[e].mac(x[e], y0[e]);

@@ -256,6 +256,7 @@ rows.append("| `ks_lazy_relin_ab.txt` | lazy relinearisation at the kernel-level
 rows.append("| `ks_lazy_relin_regs.txt` | compile-time figures, not runs: VGPRs, SGPRs, scratch, occupancy and LDS of `f_irows_tensor_sum_kernel` and `f_frows_sum_final_kernel` beside `f_irows_tensor_c2`'s kernel and `f_frows_final_kernel` modes 4 and 1, every tile geometry; `b_tensor_sum_kernel` beside `b_tensor_kernel` | `hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage -c fused_ks.hip` (and `batch_ops.hip`) |")
 rows.append("| `ks_mac_regs.txt` | compile-time figures, not runs: VGPRs, SGPRs, spills, scratch and LDS of `f_ks_gmac_kernel`, `f_ks_gsum_kernel`, `hyb_mac_kernel` and `hyb_mac_group_kernel` before and after their shared pieces moved to `ks_mac.hpp` / `galois.hpp`, both builds, with `identical` / `differs` per instantiation, and which pieces were left written out because of what they cost | `hipcc -S --cuda-device-only` of parent and branch, `python tools/experiments/asm_compare.py <parent dir> <branch dir> --table '<regex>'` |")
 rows.append("| `fused_tail_share.txt` | compile-time figures, not runs: every kernel of `fused_ks.hip` (and of `hybrid_fused.hip`, `hoist_ks.hip`, which include the touched header) against the parent's listing after the divide-and-round middle (plain / noise), the `a1·b1` loader, the rounding arithmetic and the merged-launch dispatch got one definition each, both builds, the renamed kernels paired by hand; and each shared form that was built and NOT kept (tensor terms, continuations, target loop, `base_folded`) with the VGPR figures that decided it | `hipcc -S --cuda-device-only` of parent and branch, `python tools/experiments/asm_compare.py <parent dir> <branch dir> --rename 'OLD=NEW' [--table '<regex>']` |")
+rows.append("| `hyb_body_share.txt` | compile-time figures, not runs: every kernel of every `.hip` of `dacapo_amd/csrc` against the parent's listing, both builds, after the grouped-digit key switch's row decode (`hf_row`), its Galois pair swap (`hyb_galois_pair`) and the predicate of its separate matrix-core conversion (`hybf_separate_conv`) got one definition each; and each shared form of `hybrid_fused.hip` / `hybrid_ks.hip` that was built and NOT kept because listings changed (the chunked `Acc3` conversion, the F9 head, the special-prime rows of the inverse phases, the tensor pair, the inner-product kernels' fetch, store and base term, named launchers for the two tails) with the per-instantiation VGPR / SGPR / LDS rows; what was not attempted; the line counts | `hipcc -S --cuda-device-only` of parent and branch, `python tools/experiments/asm_compare.py <parent dir> <branch dir> [--table '<regex>']` |")
 rows.append(f"| `plan_levels_ab.txt` | slack-aware levelling of the plan and the addend hoisted out of a rescale's folded sum (option `plan_level`): the headline plan under 0 (ASAP), 1 and 2 (the hoist alone) from the trace — steps by kind, waves, waves with more than one step, links, launches, live buffers, pool — then `run()` on three VMs with the option 0, 1, 0 in one process: {first_lines('plan_levels_ab.txt', 'run headline 1 - 0', 1)}; the parent commit's library with `plan_lanes` 1 and 2; `bench.py` on the parent's library and on this one: {first_lines('plan_levels_ab.txt', 'ms_per_step [0-9.]+  value', 3)}; kernel-trace runs of both: {first_lines('plan_levels_ab.txt', 'last run.. ', 2)}; the decision | `python tools/legs/plan_levels_ab.py --out profiles/plan_levels_ab.txt`; `python tools/legs/plan_levels_ab.py --lanes`; `python bench.py --gpus 1 --steps 10 --warmup 3`; `rocprofv3 --kernel-trace --stats -- python3 tools/legs/headline_only.py 3 [--opt plan_level=1]`, `tools/summarize/timeline_gaps.py` |")
 rows.append(f"| `plan_builder_refactor.txt` | the plan builder's refactor (one owner for a plan's device memory, each rule once, four leaf blocks out of `build_plan`), parent commit against branch: the plan traces of the headline program and of a convolution-shaped program under ten option sets, byte for byte: {first_lines('plan_builder_refactor.txt', '^every plan|DIFFERENCES', 1)}; every kernel's listing, both builds: {first_lines('plan_builder_refactor.txt', 'kernels in 30 listings', 1)}; `bench.py` with the parent's library and the branch's alternating on one box: {first_lines('plan_builder_refactor.txt', '^parent mean', 1)}; load and first `run()` times; test counts; line counts | `python tools/legs/plan_identity.py PARENT_LIB BRANCH_LIB --out …`; `python tools/experiments/asm_compare.py PARENT_DIR BRANCH_DIR`; `DACAPO_AMD_LIB=… python bench.py --gpus 1 --steps 40 --warmup 5 --no-cpu-baseline` |")
 rows.append(f"| `io_batch_ab.txt` | all streams' inputs and results at once (`hevm_encrypt_batch`, `hevm_decrypt_result_batch`) against the sequential calls, 8 streams of the headline fixture at N = 2^15 / 14 primes, one process, forms alternating, from host and from device memory, with `hevm_last_io_stats`: {first_lines('io_batch_ab.txt', 'one setInputs, host', 1)} | `python tools/legs/io_batch_ab.py --out profiles/io_batch_ab.txt` |")
