@@ -117,6 +117,7 @@ dc_context *dc_context_create_hybrid_primes(int logN, const uint64_t *primes, in
 }
 int dc_context_key_digits(const dc_context *ctx) { return ctx->c->key_digits(); }
 int dc_context_max_level(const dc_context *ctx) { return ctx->c->max_level(); }
+int dc_context_conv_matrix_cores(const dc_context *ctx, int ell) { return ctx->c->conv_matrix_cores(ell) ? 1 : 0; }
 void dc_context_destroy(dc_context *ctx)
 {
     if (ctx && ctx->item_ring) (void)hipFree(ctx->item_ring);

@@ -280,7 +280,10 @@ Context::Context(int logN_, int K_, int bits, const u64 *primes_or_null, int ksp
         // B fragment of lane l: column l & 15, k = 16 (l >> 4) + j in byte j, k = 8 t + p.
         // (round 5: up to 12 special primes -- the mod-down's inputs 8..11 go through a second, 32-deep MFMA; their B fragments, 8 bytes per
         // lane, follow the level's main table: [block][plane][lane])
-        hyb_mfma = alpha <= 8 && ksp <= 12 && option(OPT_HYB_MFMA) != 0;
+        // More than 8 inputs (digits of 9..16 primes on the way up, 13..16 special primes on the way down) are a dot product of two K-chunks:
+        // k = 8 t + p as before, chunk k / 64, and chunk 1's fragments -- same lane and byte rule on k % 64 -- follow the level's chunk 0 in
+        // the same [group][block][plane][lane] order (hyb_conv_mfma_wide_kernel)
+        hyb_mfma = option(OPT_HYB_MFMA) != 0;
         if (hyb_mfma) {
             auto balanced = [](u64 v, int8_t *out8) {
                 const u64 C = 0x8080808080808080ull, b = (v + C) ^ C;
@@ -292,7 +295,8 @@ Context::Context(int logN_, int K_, int bits, const u64 *primes_or_null, int ksp
                 const int M = ell + ksp, nb = hyb_up_blocks(ell), G = hyb_groups(ell);
                 hyb_bup_off[(size_t)ell] = bup.size();
                 const size_t base = bup.size();
-                bup.resize(base + (size_t)G * nb * 8 * 64 * 16, 0);
+                const size_t chunk = (size_t)G * nb * 8 * 64 * 16;
+                bup.resize(base + (alpha > 8 ? 2 : 1) * chunk, 0);
                 const u64 *upl = up.data() + hyb_up_off[(size_t)ell];
                 for (int g = 0; g < G; g++) {
                     const int lo = g * alpha, hi = std::min(lo + alpha, ell), a = hi - lo;
@@ -304,9 +308,9 @@ Context::Context(int logN_, int K_, int bits, const u64 *primes_or_null, int ksp
                             for (int pp = 0; pp < 8; pp++) {
                                 int8_t d8[8];
                                 balanced(V, d8);
-                                const int k = 8 * t + pp, lane = (k / 16) * 16 + col, j = k % 16;
+                                const int k = 8 * t + pp, lane = ((k % 64) / 16) * 16 + col, j = k % 16;
                                 for (int r = 0; r < 8; r++)
-                                    bup[base + ((((size_t)g * nb + blk) * 8 + r) * 64 + lane) * 16 + j] = d8[r];
+                                    bup[base + (k / 64) * chunk + ((((size_t)g * nb + blk) * 8 + r) * 64 + lane) * 16 + j] = d8[r];
                                 V = h_mulmod(V, 256 % m, m);
                             }
                         }
@@ -316,7 +320,7 @@ Context::Context(int logN_, int K_, int bits, const u64 *primes_or_null, int ksp
                 const int nd = hyb_dn_blocks(ell);
                 hyb_bdn_off[(size_t)ell] = bdn.size();
                 const size_t bd = bdn.size(), tail = bd + (size_t)nd * 8 * 64 * 16;
-                bdn.resize(tail + (ksp > 8 ? (size_t)nd * 8 * 64 * 8 : 0), 0);
+                bdn.resize(tail + (ksp > 12 ? (size_t)nd * 8 * 64 * 16 : ksp > 8 ? (size_t)nd * 8 * 64 * 8 : 0), 0);
                 for (int i = 0; i < ell; i++) {
                     const u64 m = primes[(size_t)i];
                     for (int j2 = 0; j2 < ksp; j2++) {
@@ -327,6 +331,9 @@ Context::Context(int logN_, int K_, int bits, const u64 *primes_or_null, int ksp
                             if (j2 < 8) { // main chunk, v_mfma_i32_16x16x64_i8: lane = 16 (k / 16) + column, byte k % 16, k = 8 j + p
                                 const int k = 8 * j2 + pp, lane = (k / 16) * 16 + (i % 16), j = k % 16;
                                 for (int r = 0; r < 8; r++) bdn[bd + ((((size_t)(i / 16)) * 8 + r) * 64 + lane) * 16 + j] = d8[r];
+                            } else if (ksp > 12) { // chunk 1, a second v_mfma_i32_16x16x64_i8: the main chunk's rule on k = 8 (j - 8) + p
+                                const int k = 8 * (j2 - 8) + pp, lane = (k / 16) * 16 + (i % 16), j = k % 16;
+                                for (int r = 0; r < 8; r++) bdn[tail + ((((size_t)(i / 16)) * 8 + r) * 64 + lane) * 16 + j] = d8[r];
                             } else {      // tail, v_mfma_i32_16x16x32_i8: lane = 16 (k / 8) + column, byte k % 8, k = 8 (j - 8) + p
                                 const int lane = (j2 - 8) * 16 + (i % 16);
                                 for (int r = 0; r < 8; r++) bdn[tail + ((((size_t)(i / 16)) * 8 + r) * 64 + lane) * 8 + pp] = d8[r];

@@ -96,11 +96,17 @@ struct Context {
     int *d_hyb_pidx = nullptr; // per level: prime index of every raised limb, group by group
     std::vector<int> hyb_pidx_off;
     u64 *d_hyb_dn = nullptr; // phat_inv[ksp], half_p[ksp], half_q[L], pinv[L], w_dn[ksp][L]   (L = max_level())
-    // matrix-core form of the two base conversions (hybrid_ks.hip, alpha <= 8 and ksp <= 8): the constant matrices as int8 B fragments of
-    // v_mfma_i32_16x16x64_i8.  Per level: [group][block of 16 output moduli][8 digit planes][64 lanes][16 bytes]; mod-down: one "group".
+    // matrix-core form of the two base conversions (hybrid_ks.hip; every shape the context accepts: alpha <= 16, ksp <= 16): the constant
+    // matrices as int8 B fragments of v_mfma_i32_16x16x64_i8.  Per level: [group][block of 16 output moduli][8 digit planes][64 lanes][16 bytes]
+    // for inputs 0..7 (K-chunk 0); mod-down: one "group".  Behind a level's chunk 0, in the same order: the mod-up's chunk 1 (inputs 8..15,
+    // when alpha > 8); the mod-down's 32-deep tail (inputs 8..11, 8 bytes per lane, when 8 < ksp <= 12) or its chunk 1 (when ksp > 12).
     int8_t *d_hyb_bup = nullptr, *d_hyb_bdn = nullptr;
     std::vector<size_t> hyb_bup_off, hyb_bdn_off;
-    bool hyb_mfma = false;
+    bool hyb_mfma = false; // option hyb_mfma when the context was created: the tables above exist
+    // THE rule "the base conversions of a key switch at level ell run on the matrix cores" (hyb_launch_conv, and the fused sequence's choice
+    // between separate conversions and loaders, both ask here).  Below 4 primes a conversion has at most a 3 x 11 matrix: the vector kernels
+    // are faster there -- 115 vs 127 us per hop at level 1, N = 2^17
+    bool conv_matrix_cores(int ell) const { return hyb_mfma && N >= 512 && ell >= 4; }
     int hyb_up_blocks(int ell) const { return (ell + ksp - 1 + 15) / 16; }  // blocks of 16 "other" moduli (the smallest digit has 1 prime)
     int hyb_dn_blocks(int ell) const { return (ell + 15) / 16; }
     // fused sequence (hybrid_fused.hip): the per-input constants of the two conversions ride on the inverse transforms' last stage -- copies

@@ -336,7 +336,7 @@ void hyb_launch_mac_stages(Context &c, const BatchWs &w, const KsItem *items, co
 
 // option hyb_fuse = 2: the two conversions as separate matrix-core launches, from the level where hyb_launch_conv takes that form.  One answer for
 // F3, F8 and F8': the rescale tail's lift reads a w.tmp that only the separate conversion writes
-static bool hybf_separate_conv(const Context &c, int ell) { return option(OPT_HYB_FUSE) == 2 && c.hyb_mfma && c.N >= 512 && ell >= 4; }
+static bool hybf_separate_conv(const Context &c, int ell) { return option(OPT_HYB_FUSE) == 2 && c.conv_matrix_cores(ell); }
 
 // F2 ... F5: everything between F1 and the accumulators.  digits [U][ell][N] hold the inverse ROWS phase's output.
 template <int MODE>

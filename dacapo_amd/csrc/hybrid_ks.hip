@@ -551,7 +551,7 @@ __global__ __launch_bounds__(kHT) void hyb_conv_mfma_kernel(const u64 *__restric
         bt = btab;
     }
     // A fragments: this lane's two inputs t = 8 ch + 2 kb, + 1 of its row, times the conversion's per-input constant, as balanced bytes
-    static_assert(CH == 1 || DOWN, "only the mod-down has more than 8 inputs");
+    static_assert(CH == 1 || DOWN, "the 32-deep tail serves the mod-down's inputs 8..11; wider conversions: hyb_conv_mfma_wide_kernel");
     constexpr int kBias = kPlaneBias << (CH - 1);
     v4i A[kConvStrip / 16];
     long A2[CH > 1 ? kConvStrip / 16 : 1]; // the tail chunk: input 8 + kb of this lane's row, 8 balanced bytes
@@ -643,6 +643,121 @@ __global__ __launch_bounds__(kHT) void hyb_conv_mfma_kernel(const u64 *__restric
     }
 }
 
+// ---- conversions with 9..16 inputs: two full K-chunks per tile ------------------------------------------------------------------------
+// A digit of 9..16 primes on the way up, 13..16 special primes on the way down: an int8 dot product of length 8 a <= 128 = two
+// v_mfma_i32_16x16x64_i8 per (16 coefficients, 16 moduli, plane) into the same accumulator -- chunk 0 holds inputs 0..7, chunk 1 inputs 8..15;
+// inputs at or beyond a (a partial last digit, a level of fewer primes than a digit) are zero fragments.
+// Arithmetic: that of the 32-deep tail above, whose bound already covers 128 byte products per plane.  |byte product| <= 2^14, so
+// |sum| <= 2^21: the accumulators start at 2^21 (kPlaneBias << 1), every plane value is in [0, 2^22], T' = sum_r c'_r 2^(8r) < 2^78.01 and
+// T' >> 60 < 2^19, so hyb_recombine's single fold still lands below 2q (2^60 + 2^19 d, d < 2^28); the constant the biases add is
+// hyb_plane_bias_mod(Mo, 1), subtracted through e as there.
+// Registers: the A side doubles (lane (col, kb) holds inputs 8 c + 2 kb, + 1 of chunk c: two v4i per tile, 32 VGPRs for the strip's four
+// tiles); the B side does NOT live in registers -- a second 64-deep MFMA with its operands held across the tiles was 200 VGPRs and two waves
+// per SIMD (see above).  The workgroup stages the 2 x 8 x 64 fragments of a block of 16 output moduli in LDS (16 KiB, once per block, shared
+// by its four waves), and each MFMA takes its B operand from there with one 16-byte LDS load: what stays live across a tile is A (32) and the
+// eight plane accumulators (32).  Stores and output ranges: hyb_conv_mfma_kernel's.
+// bt1 - bt0 = `chunk1` fragments: chunk 1 of a level follows its chunk 0 (context.hip).
+template <bool DOWN, bool PRE>
+__global__ __launch_bounds__(kHT) void hyb_conv_mfma_wide_kernel(const u64 *__restrict__ in, u64 *__restrict__ out, int ell, int ksp, int alpha, int L,
+                                                                  int E, size_t N, const DModulus *__restrict__ mods, const u64 *__restrict__ cst,
+                                                                  const v4i *__restrict__ btab, int nblk, int chunk1)
+{
+    __shared__ v4i Bs[2 * 8 * 64]; // [chunk][plane][lane]
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, col = lane & 15, kb = lane >> 4;
+    const size_t n0 = ((size_t)blockIdx.x * 4 + wave) * kConvStrip;
+    int a, lo, in_prime0, n_out;
+    const u64 *inp;
+    u64 *outp;
+    const v4i *bt;
+    if (!DOWN) {
+        const int g = blockIdx.y, b = blockIdx.z, M = ell + ksp;
+        lo = g * alpha;
+        a = min(lo + alpha, ell) - lo;
+        in_prime0 = lo;
+        n_out = M - a;
+        inp = in + ((size_t)b * ell + lo) * N;
+        outp = out + ((size_t)b * E + (size_t)g * (M - alpha)) * N;
+        bt = btab + (size_t)g * nblk * 8 * 64;
+    } else {
+        const int z = blockIdx.z;
+        lo = 0, a = ksp, in_prime0 = L, n_out = ell;
+        inp = in + (size_t)z * ksp * N;
+        outp = out + (size_t)z * ell * N;
+        bt = btab;
+    }
+    constexpr int kBias = kPlaneBias << 1;
+    v4i A[2][kConvStrip / 16];
+    const u64 C8 = 0x8080808080808080ull;
+#pragma unroll
+    for (int ch = 0; ch < 2; ch++) {
+        u64 y[kConvStrip / 16][2];
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            const int t = 8 * ch + 2 * kb + h, tt = t < a ? t : 0;
+            const DModulus mi = mods[in_prime0 + tt];
+            const u64 mul = DOWN ? cst[tt] : cst[lo + tt]; // phat_inv[j] | qhat_inv[i]
+            const u64 add = DOWN ? cst[ksp + tt] : 0;      // floor(P/2) mod p_j | -
+#pragma unroll
+            for (int tile = 0; tile < kConvStrip / 16; tile++) {
+                u64 x = 0;
+                if (t < a) {
+                    x = inp[(size_t)t * N + n0 + (size_t)tile * 16 + col];
+                    if (DOWN && !PRE) x = addmod(x, add, mi.q);
+                    if (!PRE) x = mulmod(x, mul, mi);
+                    x = (x + C8) ^ C8;
+                }
+                y[tile][h] = x;
+            }
+        }
+#pragma unroll
+        for (int tile = 0; tile < kConvStrip / 16; tile++)
+            A[ch][tile] = v4i{ (int)(u32)y[tile][0], (int)(u32)(y[tile][0] >> 32), (int)(u32)y[tile][1], (int)(u32)(y[tile][1] >> 32) };
+    }
+    for (int blk = 0; blk < nblk && blk * 16 < n_out; blk++) { // (n_out is the workgroup's: every wave takes the same trips)
+        __syncthreads(); // every wave has read the previous block's fragments
+#pragma unroll
+        for (int i = 0; i < 8 * 64; i += kHT) {
+            Bs[i + threadIdx.x] = bt[(size_t)blk * 8 * 64 + i + threadIdx.x];
+            Bs[8 * 64 + i + threadIdx.x] = bt[(size_t)chunk1 + (size_t)blk * 8 * 64 + i + threadIdx.x];
+        }
+        __syncthreads();
+        const int e = blk * 16 + col;
+        const bool valid = e < n_out;
+        int pm;
+        u64 post = 0;
+        if (!DOWN) {
+            const int mi2 = e < lo ? e : e + a;
+            pm = mi2 < ell ? mi2 : L + (mi2 - ell);
+        } else {
+            pm = e;
+            post = valid ? cst[2 * ksp + e] : 0; // floor(P/2) mod q_i
+        }
+        const DModulus Mo = mods[valid ? pm : 0];
+        const u64 k0 = addmod(hyb_plane_bias_mod(Mo, 1), post, Mo.q);
+        const u64 eb = k0 ? Mo.q - k0 : 0; // -(K0 + post) mod m, < 2^60
+#pragma unroll
+        for (int tile = 0; tile < kConvStrip / 16; tile++) {
+            int lb = lane;
+            asm volatile("" : "+v"(lb)); // (a per-tile value as far as the optimiser can tell: the B operands are read from LDS where the MFMA
+                                         // consumes them instead of living in 64 registers across the tiles)
+            v4i c[8];
+#pragma unroll
+            for (int r = 0; r < 8; r++) {
+                c[r] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[0][tile], Bs[r * 64 + lb], v4i{ kBias, kBias, kBias, kBias }, 0, 0, 0);
+                c[r] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[1][tile], Bs[(8 + r) * 64 + lb], c[r], 0, 0, 0);
+            }
+            if (valid) { // this lane: rows 4 kb .. 4 kb + 3 of the tile, column `col`
+                u64 v[4];
+#pragma unroll
+                for (int j = 0; j < 4; j++) v[j] = hyb_recombine(c, j, Mo, eb);
+                u64 *o = outp + (size_t)e * N + n0 + (size_t)tile * 16 + 4 * kb;
+                *reinterpret_cast<u64x2 *>(o) = u64x2{ v[0], v[1] };
+                *reinterpret_cast<u64x2 *>(o + 2) = u64x2{ v[2], v[3] };
+            }
+        }
+    }
+}
+
 // the two base conversions (matrix cores when the context has their operand tables and the level is high enough, else the vector kernels).
 // `prescaled`: inputs already multiplied by the per-input constant (fused sequence).  count = decompositions (up) / polynomials (down).
 // OUTPUT RANGE (contract): the matrix-core form of the 60-bit build writes LAZY residues -- congruent to the converted value, one fold, below
@@ -655,8 +770,7 @@ void hyb_launch_conv(Context &c, bool down, bool prescaled, const u64 *in, u64 *
 {
     const size_t N = c.N;
     const int ksp = c.ksp, alpha = c.alpha, L = c.max_level(), G = c.hyb_groups(ell), E = c.hyb_ext(ell);
-    // (below 4 primes a conversion has at most a 3 x 11 matrix: the vector kernels are faster there -- 115 vs 127 us per hop at level 1, N = 2^17)
-    const bool mfma = c.hyb_mfma && N >= 4 * kConvStrip && ell >= 4;
+    const bool mfma = c.conv_matrix_cores(ell);
     const unsigned gc = (unsigned)(N / (4 * kConvStrip)), gx = (unsigned)(N / (2 * kHT));
     if (prescaled && !mfma) {
         fprintf(stderr, "[dacapo_amd] hyb_launch_conv: pre-scaled inputs need the matrix-core form\n");
@@ -664,29 +778,47 @@ void hyb_launch_conv(Context &c, bool down, bool prescaled, const u64 *in, u64 *
     }
     const v4i *bup = reinterpret_cast<const v4i *>(c.d_hyb_bup + (mfma ? c.hyb_bup_off[(size_t)ell] : 0));
     const v4i *bdn = reinterpret_cast<const v4i *>(c.d_hyb_bdn + (mfma ? c.hyb_bdn_off[(size_t)ell] : 0));
+    // The form follows the launch's widest conversion: a <= 8 inputs one K-chunk; the mod-down's 9..12 one chunk and the 32-deep tail; 9..16
+    // otherwise two chunks.  (The mod-up's 9..12 take the two-chunk form too, not a tail of their own: one form fewer, and not measured apart.)
+    const int widest = down ? ksp : std::min(alpha, ell);
+    const bool wide = widest > (down ? 12 : 8);
     if (!down) {
-        if (mfma && prescaled)
+        const int nb = c.hyb_up_blocks(ell);
+        if (mfma && wide && prescaled)
+            DC_LAUNCH((hyb_conv_mfma_wide_kernel<false, true>), dim3(gc, (unsigned)G, (unsigned)count), dim3(kHT), 0, s, in, out, ell, ksp, alpha, L, E,
+                               N, c.d_mods, c.hyb_up(ell), bup, nb, G * nb * 8 * 64);
+        else if (mfma && wide)
+            DC_LAUNCH((hyb_conv_mfma_wide_kernel<false, false>), dim3(gc, (unsigned)G, (unsigned)count), dim3(kHT), 0, s, in, out, ell, ksp, alpha, L, E,
+                               N, c.d_mods, c.hyb_up(ell), bup, nb, G * nb * 8 * 64);
+        else if (mfma && prescaled)
             DC_LAUNCH((hyb_conv_mfma_kernel<false, true>), dim3(gc, (unsigned)G, (unsigned)count), dim3(kHT), 0, s, in, out, ell, ksp, alpha, L, E,
-                               N, c.d_mods, c.hyb_up(ell), bup, c.hyb_up_blocks(ell));
+                               N, c.d_mods, c.hyb_up(ell), bup, nb);
         else if (mfma)
             DC_LAUNCH((hyb_conv_mfma_kernel<false, false>), dim3(gc, (unsigned)G, (unsigned)count), dim3(kHT), 0, s, in, out, ell, ksp, alpha, L, E,
-                               N, c.d_mods, c.hyb_up(ell), bup, c.hyb_up_blocks(ell));
+                               N, c.d_mods, c.hyb_up(ell), bup, nb);
         else
             DC_LAUNCH(hyb_modup_kernel, dim3(gx, (unsigned)G, (unsigned)count), dim3(kHT), 0, s, in, out, ell, ksp, alpha, L, E, N, c.d_mods,
                                c.hyb_up(ell));
     } else {
-        if (mfma && prescaled && ksp > 8)
+        const int nd = c.hyb_dn_blocks(ell);
+        if (mfma && wide && prescaled)
+            DC_LAUNCH((hyb_conv_mfma_wide_kernel<true, true>), dim3(gc, 1, (unsigned)count), dim3(kHT), 0, s, in, out, ell, ksp, alpha, L, E, N,
+                               c.d_mods, c.d_hyb_dn, bdn, nd, nd * 8 * 64);
+        else if (mfma && wide)
+            DC_LAUNCH((hyb_conv_mfma_wide_kernel<true, false>), dim3(gc, 1, (unsigned)count), dim3(kHT), 0, s, in, out, ell, ksp, alpha, L, E, N,
+                               c.d_mods, c.d_hyb_dn, bdn, nd, nd * 8 * 64);
+        else if (mfma && prescaled && ksp > 8)
             DC_LAUNCH((hyb_conv_mfma_kernel<true, true, 2>), dim3(gc, 1, (unsigned)count), dim3(kHT), 0, s, in, out, ell, ksp, alpha, L, E, N,
-                               c.d_mods, c.d_hyb_dn, bdn, c.hyb_dn_blocks(ell));
+                               c.d_mods, c.d_hyb_dn, bdn, nd);
         else if (mfma && ksp > 8)
             DC_LAUNCH((hyb_conv_mfma_kernel<true, false, 2>), dim3(gc, 1, (unsigned)count), dim3(kHT), 0, s, in, out, ell, ksp, alpha, L, E, N,
-                               c.d_mods, c.d_hyb_dn, bdn, c.hyb_dn_blocks(ell));
+                               c.d_mods, c.d_hyb_dn, bdn, nd);
         else if (mfma && prescaled)
             DC_LAUNCH((hyb_conv_mfma_kernel<true, true>), dim3(gc, 1, (unsigned)count), dim3(kHT), 0, s, in, out, ell, ksp, alpha, L, E, N,
-                               c.d_mods, c.d_hyb_dn, bdn, c.hyb_dn_blocks(ell));
+                               c.d_mods, c.d_hyb_dn, bdn, nd);
         else if (mfma)
             DC_LAUNCH((hyb_conv_mfma_kernel<true, false>), dim3(gc, 1, (unsigned)count), dim3(kHT), 0, s, in, out, ell, ksp, alpha, L, E, N,
-                               c.d_mods, c.d_hyb_dn, bdn, c.hyb_dn_blocks(ell));
+                               c.d_mods, c.d_hyb_dn, bdn, nd);
         else
             DC_LAUNCH(hyb_moddown_kernel, dim3(gx, (unsigned)count), dim3(kHT), 0, s, in, out, ell, ksp, L, N, c.d_mods, c.d_hyb_dn);
     }

@@ -49,6 +49,7 @@ def _bind(path):
         L.dc_context_create_hybrid_primes.argtypes = [i32, vp, i32, i32, i32]
         L.dc_context_key_digits.argtypes = [vp]
         L.dc_context_max_level.argtypes = [vp]
+        L.dc_context_conv_matrix_cores.argtypes = [vp, i32]
         L.dc_context_destroy.argtypes = [vp]
         L.dc_context_logn.argtypes = [vp]
         L.dc_context_num_primes.argtypes = [vp]

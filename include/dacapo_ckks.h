@@ -42,6 +42,10 @@ dc_context *dc_context_create_hybrid(int logN, int num_primes, int special, int 
 dc_context *dc_context_create_hybrid_primes(int logN, const uint64_t *primes, int num_primes, int special, int alpha);
 int dc_context_key_digits(const dc_context *ctx);
 int dc_context_max_level(const dc_context *ctx);
+/* 1 when the two base conversions (ModUp, ModDown) of a grouped-digit key switch at level `ell` run on the matrix cores
+ * (v_mfma_i32_16x16x64_i8; every digit size and special-prime count the context accepts, up to 16 each), 0 when they run on the vector
+ * units: option hyb_mfma = 0 when the context was created, a level below 4 primes, or a context without grouped digits.  Never aborts. */
+int dc_context_conv_matrix_cores(const dc_context *ctx, int ell);
 void dc_context_destroy(dc_context *ctx);
 int dc_context_logn(const dc_context *ctx);
 int dc_context_num_primes(const dc_context *ctx);
